@@ -41,10 +41,6 @@ import os
 import sys
 import time
 
-# the fast E-step runs five kernels side by side; HIP's default of 4 hardware queues per process makes two
-# of its streams share one (must be set before the HIP runtime starts, i.e. before torch is imported)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -315,6 +311,13 @@ def make_line(args, fast, world, bins, total_bins, lens, n_local_segs, kern, dia
     return out
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: what a caller of the timed path received from its last timed step, one float64 DIR/<name>.npy each."""
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(x, dtype=np.float64))
+
+
 def median_ms(fn, n, sync):
     """median / min wall time in ms of n calls of fn(i), each followed by sync()"""
     ts = []
@@ -405,11 +408,11 @@ def group_engine_run(hip, segs, devices, moving, steps, warmup, mode):
             g.estep(*moving[i % len(moving)])
         t0 = time.perf_counter()
         for i in range(steps):
-            g.estep(*moving[(warmup + i) % len(moving)])
+            last = g.estep(*moving[(warmup + i) % len(moving)])
         dt = time.perf_counter() - t0
         info = g.info()
         return {"selfcheck": sc, "ms_per_step": dt / steps * 1e3, "first_call_ms": first, "steps": steps, "warmup": warmup, "devices": list(devices),
-                "reduce": {0: "single shard", 1: "RCCL all-reduce (group.hip)", 2: "host sum in shard order", 3: "ordered per-segment sum"}[info["last_reduce"]]}
+                "reduce": {0: "single shard", 1: "RCCL all-reduce (group.hip)", 2: "host sum in shard order", 3: "ordered per-segment sum"}[info["last_reduce"]]}, last
     finally:
         g.close()
 
@@ -499,7 +502,11 @@ def main():
     ap.add_argument("--group-extra", type=int, default=1, help="also time the C library's own multi-GPU engine beside the headline (0 = skip)")
     ap.add_argument("--boot-extra", type=int, default=1, help="also run config 4 (16 bootstrap replicates, -N2) through psmc_boot (0 = skip)")
     ap.add_argument("--opt", action="append", default=[], help="library option key=value (chunk, warmup, ...)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last timed step (A, E, LL, ...) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from psmc_amd import hip, sim
@@ -576,6 +583,7 @@ def main():
                     t = sh.stats.cpu(); dist.all_reduce(t); sh.stats.copy_(t)
             else:
                 r = sh.es.estep(pa, pe, p0)          # exact: ordered host sum (bit-identical to khmm.c)
+                sh.last = r
                 if dist is not None:
                     t = torch.from_numpy(np.concatenate([r["A"].ravel(), r["E"].ravel(), [r["LL"]]]))
                     t = t if single_gpu_test else t.cuda()
@@ -609,7 +617,9 @@ def main():
         else:
             segs = sim.simulate_genome(a, e, a0, lens, seed=43)
         total_bins = int(sum(len(x) for x in segs))
-        res = group_engine_run(hip, segs, devices, moving, args.steps, args.warmup, mode)
+        res, last = group_engine_run(hip, segs, devices, moving, args.steps, args.warmup, mode)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {k: last[k] for k in ("A", "E", "A0", "LL")})
         ms = res["ms_per_step"]
         gbs = total_bins * BYTES_PER_BIN / (ms * 1e-3) / 1e9
         out = {"metric": "genome bins/sec through forward-backward (n=64)", "value": total_bins / (ms * 1e-3), "unit": "bins/s", "n_gpus": len(devices),
@@ -639,6 +649,13 @@ def main():
         first_ms = (time.perf_counter() - t0) * 1e3
     dt = timed(step, moving, args.steps, args.warmup)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:   # before the steps below overwrite them
+        if mode == hip.MODE_FAST:
+            n = N_STATES
+            st = sh.stats.cpu().numpy()
+            dump_outputs(args.dump_outputs, {"A": st[:n * n].reshape(n, n), "E": st[n * n:n * n + 2 * n].reshape(2, n), "LL": st[-1]})
+        else:
+            dump_outputs(args.dump_outputs, {k: sh.last[k] for k in ("A", "E", "A0", "LL")})
     value = total_bins / (dt / args.steps)
     # per-kernel durations (HIP events recorded by the library on the streams the kernels ran on); measured on separate
     # steps of the same cycle so that the event reads do not perturb the timed region
@@ -853,7 +870,7 @@ def main():
                 sh.close()
             except Exception:
                 pass
-            ge = group_engine_run(hip, segs, [local], moving, args.steps, max(args.warmup, 10), mode)   # a fresh context: past its learning steps
+            ge, _ = group_engine_run(hip, segs, [local], moving, args.steps, max(args.warmup, 10), mode)   # a fresh context: past its learning steps
             ge["value"] = total_bins / (ge["ms_per_step"] * 1e-3); ge["vs_headline"] = ms_per_step / ge["ms_per_step"]
             out["group_engine"] = ge
         except Exception as ex_:

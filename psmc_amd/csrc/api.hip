@@ -4,12 +4,6 @@
 // psmc_hip_ctx.h holds the context they share.
 #include "psmc_hip_ctx.h"
 
-// The fast E-step keeps four streams busy (forward chain, backward chain, counts, walks) beside the
-// caller's.  HIP hands a process 4 hardware queues by default and streams beyond that share one -- a
-// kernel then waits for an unrelated one.  Ask for 8 before the runtime starts (no effect, and no harm,
-// if the host program initialised HIP earlier or set the variable itself).
-__attribute__((constructor)) static void psmc_hip_more_queues() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
-
 static void destroy_kids(psmc_hip_ctx *c);
 
 // The five streams of a context, on the whole device or -- psmc_hip_set_cu_range -- masked to a range of its compute units.

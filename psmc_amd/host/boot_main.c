@@ -87,10 +87,6 @@ int main(int argc, char *argv[])
 	int n_rep = 0, i = 1;
 	long seed0 = 1;
 	const char *pattern = 0, *main_out = 0, *main_in = 0;
-	{ /* before the first HIP call: the main run's stream and the batch's must not share a hardware queue (a larger value the user exported stands) */
-		const char *q = getenv("GPU_MAX_HW_QUEUES");
-		if (!q || atoi(q) < 16) setenv("GPU_MAX_HW_QUEUES", "16", 1);
-	}
 	for (; i < argc; ++i) {
 		if (!strcmp(argv[i], "--")) { ++i; break; }
 		if (!strcmp(argv[i], "-R") && i + 1 < argc) n_rep = atoi(argv[++i]);

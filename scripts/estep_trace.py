@@ -2,7 +2,6 @@
 """Per-E-step trace over 30 moving-parameter E-steps: ms, repair rounds / tiles, the plan (mean warm-ups, glued tiles); 30 M-bin genome (share 1)
 or rank 0's share of N GPUs.  (Written for the adaptive warm-ups of round 3, profiles/r03_adaptive_warmup_trace.txt; round 6 built them again on top of merging repairs.)"""
 import json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Config 5 alone (30 M bins x 128 states, fast mode) for the profilers: N full-count E-steps, then N factored ones."""
 import json, os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -11,7 +11,6 @@ import ctypes as C
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -79,15 +79,6 @@ def oracle():
     return orc.Oracle()
 
 
-@pytest.fixture(scope="session")
-def reference():
-    import orc
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference checkout not present (GPU box)")
-    orc.build_oracle(with_ref=True)
-    return orc.Reference()
-
-
 FAST_METRICS = []   # psmc_amd.parity.fast_error_metrics of every fast-vs-reference comparison of the session (check_fast)
 
 

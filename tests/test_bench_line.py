@@ -69,3 +69,10 @@ def test_replayed_traffic_is_guarded_by_the_kernel_sources(tmp_path):
     assert bench.replayed_traffic(str(p), 123, "k_bwd_count4f_struct")[0] is None          # another workload
     assert bench.replayed_traffic(str(p), 30000001, "k_nothing")[0] is None                 # another kernel
     assert bench.replayed_traffic(str(tmp_path / "absent.json"), 30000001, "k")[0] is None
+
+
+def test_bench_rejects_fewer_than_one_timed_step():
+    """--steps sets the number of timed steps and ms_per_step is divided by it: zero is refused before anything runs."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr, r.stderr

@@ -206,3 +206,31 @@ def test_bench_two_ranks_on_one_device():
         assert "error" not in g, g
         assert g["bins_total"] == bins and g["devices"] == [0, 0] and g["value"] > 0
         assert g["selfcheck"]["shards"] == 2 and g["selfcheck"]["path"] == "host_sum", g   # two shards on one device: no communicator
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(hip, golden, tmp_path):
+    """bench.py --dump-outputs writes A, E and LL of the LAST timed step as float64 .npy files: what an exact E-step gives at that
+    step's parameters.  The timed steps cycle through the EM trajectory, so step warmup + steps - 1 runs set (warmup + steps - 1) % 25;
+    the steps bench.py runs after the timed ones (kernel timings, steady state) use other sets."""
+    import json
+    import sys
+    from psmc_amd import sim
+    steps, warmup, bins, n_seg = 4, 2, 3_000_000, 9
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--bins", str(bins), "--segments", str(n_seg),
+           "--cpu-sample", "0", "--exact-extra", "0", "--n128-extra", "0", "--shard-extra", "0", "--group-extra", "0", "--boot-extra", "0",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads(r.stdout.strip().splitlines()[-1])
+    assert j["steps"] == steps and j["ms_per_step"] > 0
+    out = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("A", "E", "LL")}
+    assert all(v.dtype == np.float64 for v in out.values())
+    assert out["A"].shape == (64, 64) and out["E"].shape == (2, 64) and out["LL"].shape == ()
+    p = golden.params("n64_curve")   # bench.py draws its genome from these parameters
+    segs = sim.simulate_genome(p["a"], p["e"], p["a0"], sim.human_like_lengths(bins, n_seg=n_seg), seed=43)
+    ex = hip.HipEStep(64, mode=hip.MODE_EXACT)
+    ex.load_segments(segs)
+    rx = ex.estep(*moving_params()[(warmup + steps - 1) % 25])
+    ex.close()
+    assert relmax(out["A"], rx["A"]) < TOL_STATS and relmax(out["E"], rx["E"]) < TOL_STATS
+    assert abs(float(out["LL"]) - rx["LL"]) <= TOL_LL * abs(rx["LL"])

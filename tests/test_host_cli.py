@@ -2,18 +2,23 @@
 .psmc writer, decoding output) against the reference's golden outputs, byte for
 byte.  On CPU the E-step backend is the oracle, injected by a test-only main
 (tests/host_oracle_main.c); on the GPU box the real `psmc` binary is run."""
+import atexit
 import ctypes as C
 import glob
 import gzip
 import os
+import shutil
 import subprocess
+import tempfile
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "psmc_amd", "host")
 CLI = os.path.join(ROOT, "tests", "golden", "cli")
-BUILD = "/tmp/psmc_test_build"
+REF_CHECKS = os.path.join(ROOT, "tests", "golden", "ref_checks")   # the reference's side, from tests/golden/make_golden_ref_checks.py
+BUILD = tempfile.mkdtemp(prefix="psmc_test_build_")   # one per run: a fixed path in the shared temp dir belongs to whoever made it first
+atexit.register(shutil.rmtree, BUILD, True)
 
 
 def golden_cases():
@@ -74,20 +79,20 @@ def test_host_logic_byte_identical(oracle_psmc, name):
         assert len(a) == len(b)
 
 
-@pytest.mark.parametrize("args", [["-N25", "-t15", "-r5", "-p", "4+25*2+4+6", "small.psmcfa"], ["-N30", "-t15", "-r5", "-p", "4+5*3+4", "t10k.psmcfa"],
-                                  ["-N8", "-t15", "-r5", "-T", "0.1", "-p", "4+5*3+4", "small.psmcfa"]])
+LONG_EM_ARGS = [["-N25", "-t15", "-r5", "-p", "4+25*2+4+6", "small.psmcfa"], ["-N30", "-t15", "-r5", "-p", "4+5*3+4", "t10k.psmcfa"],
+                ["-N8", "-t15", "-r5", "-T", "0.1", "-p", "4+5*3+4", "small.psmcfa"]]   # (make_golden_ref_checks.py runs the same list)
+
+
+@pytest.mark.parametrize("args", LONG_EM_ARGS)
 def test_long_em_runs_equal_the_reference_binary(oracle_psmc, args):
     """The host driver (model.c's interval factors expanded to the matrix, mstep.c's Hooke-Jeeves search, run.c's output) over 25-30
-    EM rounds -- tens of thousands of objective calls, each deciding the next trial point with `<` -- against the reference's own
-    binary built from its sources (oracle/_ref/psmc_ref): the same bytes.  Skipped where that binary did not travel."""
-    ref = os.path.join(ROOT, "oracle", "_ref", "psmc_ref")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/psmc_ref not built (make -C oracle ref needs /root/reference)")
+    EM rounds -- tens of thousands of objective calls, each deciding the next trial point with `<` -- against what the reference's own
+    binary built from its sources (oracle/_ref/psmc_ref) wrote for the same command line: the same bytes."""
     a = args[:-1] + [os.path.join(CLI, args[-1])]
-    want = subprocess.run([ref] + a, capture_output=True, text=True)
+    want = gzip.open(os.path.join(REF_CHECKS, "long_em_%d.psmc.gz" % LONG_EM_ARGS.index(args)), "rt").read()
     got = subprocess.run([oracle_psmc] + a, capture_output=True, text=True)
-    assert want.returncode == 0 and got.returncode == 0, (want.stderr[-500:], got.stderr[-500:])
-    assert got.stdout == want.stdout and want.stdout.count("\nRD\t") >= 9
+    assert got.returncode == 0, got.stderr[-500:]
+    assert got.stdout == want and want.count("\nRD\t") >= 9
 
 
 @pytest.mark.parametrize("factored", ["0", "1"])
@@ -214,21 +219,32 @@ def test_usable_cpus_follow_the_cgroup_quota(host):
     assert n == want and n >= 1
 
 
-def test_model_update_equals_reference_on_random_parameters(reference):
+def ref_checks():
+    return np.load(os.path.join(REF_CHECKS, "ref_checks.npz"))
+
+
+def sha256_of(*arrays):
+    """as make_golden_ref_checks.py digests the reference's outputs: the float64 bytes of the arrays in turn"""
+    import hashlib
+    h = hashlib.sha256()
+    for x in arrays:
+        h.update(np.ascontiguousarray(x, dtype=np.float64).tobytes())
+    return h.hexdigest()
+
+
+def test_model_update_equals_reference_on_random_parameters():
     """model.c (the interval factors and their expansion to a / e / a0) against the reference's psmc_update_hmm (core.c:61-133, through
     oracle/_ref) on random parameter vectors -- orders of magnitude apart in theta, rho, max_t and the lambdas, so that the closed form
-    of the mean coalescence time also leaves its interval and takes the fallback (core.c:113-114): every double the same."""
+    of the mean coalescence time also leaves its interval and takes the fallback (core.c:113-114): every double the same (the digest
+    of the reference's a, e[:2], a0 is stored for each vector)."""
     from psmc_amd import hostlib
-    rng = np.random.default_rng(20260927)
+    g = ref_checks()
     for pattern in ("4+5*3+4", "4+25*2+4+6", "64*2", "1*10", "3+2*17+15*1+1*12"):
-        n_free = reference.parse_pattern(pattern)[1]
+        params, want = g["model.%s.params" % pattern], g["model.%s.sha256" % pattern]
+        assert len(params) == len(want) == 40
         for trial in range(40):
-            theta = 10.0 ** rng.uniform(-4, -0.5); rho = 10.0 ** rng.uniform(-5, -0.5); max_t = 10.0 ** rng.uniform(-0.3, 1.7)
-            lam = 10.0 ** rng.uniform(-2.5, 2.5, size=n_free) if trial % 3 else 10.0 ** rng.uniform(-0.3, 0.3, size=n_free)
-            params = np.concatenate([[theta, rho, max_t], lam])
-            want = reference.hmm_params(pattern, params)
-            a, e, a0 = hostlib.hmm_params(pattern, params)
-            assert a.tobytes() == want["a"].tobytes() and e[:2].tobytes() == want["e"][:2].tobytes() and a0.tobytes() == want["a0"].tobytes(), (pattern, trial)
+            a, e, a0 = hostlib.hmm_params(pattern, params[trial])
+            assert sha256_of(a, e[:2], a0) == want[trial], (pattern, trial)
 
 
 def test_pattern_kats(host, golden):
@@ -275,19 +291,21 @@ def test_reader_matches_reference_decode(host):
         assert host.psmc_symbol_of(C.c_ubyte(c)) == (0 if c in hom else 1 if c in het else 2)
 
 
-def test_reference_reader_agrees_on_odd_input(host, reference, tmp_path):
-    """FASTQ-style records, blank lines, lower case, '>' inside a line, CR characters."""
+def test_reference_reader_agrees_on_odd_input(host, tmp_path):
+    """FASTQ-style records, blank lines, lower case, '>' inside a line, CR characters: what the reference's reader made of them."""
     txt = ">a desc\nTTKKN\n\nnnkt\r\n@b\nTKTK+\n+\nIIII\n>c\nKK>d x\nTTTT\n"
     p = tmp_path / "odd.psmcfa"
     p.write_text(txt)
-    ref = reference.read_psmcfa(str(p))
+    g = ref_checks()
+    off = np.concatenate([[0], np.cumsum(g["odd.L"])])
+    ref_segs = [g["odd.seq"][off[i]:off[i + 1]] for i in range(len(g["odd.L"]))]
     inp = Input()
     assert host.psmc_input_read(str(p).encode(), C.byref(inp)) == 0
-    assert inp.n_seg == len(ref["segs"])
-    for i, s in enumerate(ref["segs"]):
+    assert inp.n_seg == len(ref_segs)
+    for i, s in enumerate(ref_segs):
         got = np.ctypeslib.as_array(inp.seg[i].sym, shape=(inp.seg[i].L,)) if inp.seg[i].L else np.zeros(0, np.uint8)
         assert np.array_equal(got, s), i
-    assert inp.sum_called == ref["sum_L"] and inp.sum_het == ref["sum_n"]
+    assert inp.sum_called == int(g["odd.sum_L"]) and inp.sum_het == int(g["odd.sum_n"])
 
 
 def test_hooke_jeeves_kat(host, golden):
@@ -305,7 +323,7 @@ def test_hooke_jeeves_kat(host, golden):
     assert np.allclose(x0, x, atol=1e-6) and abs(fx - float(golden.kats["kmin.fx"])) < 1e-9
 
 
-def test_hooke_jeeves_equals_reference_search_bit_for_bit(host, reference):
+def test_hooke_jeeves_equals_reference_search_bit_for_bit(host):
     """mstep.c's search (sweep / advance / shrink) against the reference's kmin_hj (kmin.c:48-107, through oracle/_ref) on the SAME
     compiled objective (tests/host_hj_check.c = the quadratic of oracle/ref_shim.c), random centres and starts incl. zeros (a zero
     coordinate gets the absolute step r): every coordinate of the end point and the returned value, bit for bit."""
@@ -316,13 +334,13 @@ def test_hooke_jeeves_equals_reference_search_bit_for_bit(host, reference):
     lib = C.CDLL(so)
     lib.mine_kmin_quad.restype = C.c_double
     lib.mine_kmin_quad.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
-    rng = np.random.default_rng(7)
-    for trial in range(60):
-        n = int(rng.integers(1, 30))
-        centre = rng.normal(size=n) * 10.0 ** rng.uniform(-2, 2)
-        x0 = rng.normal(size=n) * 10.0 ** rng.uniform(-2, 2)
-        x0[rng.random(n) < 0.15] = 0.0
-        xr, fr = reference.kmin_quad(x0.copy(), centre.copy())
+    g = ref_checks()
+    off = np.concatenate([[0], np.cumsum(g["hj.n"])])
+    assert len(g["hj.n"]) == 60
+    for trial, n in enumerate(g["hj.n"]):
+        n = int(n)
+        sl = slice(off[trial], off[trial + 1])
+        centre, x0, xr, fr = g["hj.centre"][sl], g["hj.x0"][sl], g["hj.x"][sl], g["hj.fx"][trial]
         xm = x0.copy()
         fm = lib.mine_kmin_quad(n, xm.ctypes.data_as(C.POINTER(C.c_double)), centre.ctypes.data_as(C.POINTER(C.c_double)), 50000)
         assert xm.tobytes() == np.asarray(xr).tobytes() and np.float64(fm).tobytes() == np.float64(fr).tobytes(), trial

@@ -2,16 +2,20 @@
 M-step, writer, decoding, bootstrap driver) built with -fsanitize=address,undefined and with -fsanitize=thread, the
 CPU oracle as E-step backend (tests/host_oracle_main.c, tests/host_oracle_boot_main.c), run over the golden command
 lines: byte-identical output AND no sanitizer report.  CPU only; a few seconds per case."""
+import atexit
 import glob
 import gzip
 import os
+import shutil
 import subprocess
+import tempfile
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "psmc_amd", "host")
 CLI = os.path.join(ROOT, "tests", "golden", "cli")
-BUILD = "/tmp/psmc_test_build"
+BUILD = tempfile.mkdtemp(prefix="psmc_test_build_")   # one per run: a fixed path in the shared temp dir belongs to whoever made it first
+atexit.register(shutil.rmtree, BUILD, True)
 SRC = [os.path.join(HOST, f) for f in ("pattern.c", "input.c", "model.c", "mstep.c", "run.c", "sim.c", "boot.c")]
 
 
