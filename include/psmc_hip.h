@@ -92,6 +92,11 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *  "merge1"        auto     1: bulk forward sweep and backward warm-up pass in ONE grid, so that the dispatcher puts
  *                           their waves on distinct SIMDs, and the dependent chain walks -> chains -> run tiles -> back
  *                           half on one stream; 0: side by side on streams of their own.  auto: 1 with one round
+ *  "phase1"        auto     fused back half, 64 states, four tiles per wave, bulk passes on streams of their own (not "merge1"): 1 = the blocks of
+ *                           the bulk forward sweep and of the backward warm-up pass form ONE work queue, longest first, that a persistent
+ *                           grid of "phase1_waves" waves per SIMD pulls from; 0 = two launches, dealt out by the dispatcher.  Bit-identical.
+ *                           auto: 1
+ *  "phase1_waves"  2        waves per SIMD of that grid (1..4)
  *  "coarse"        auto     a bulk sweep item spans up to this many consecutive tiles of a segment: ONE speculative warm-up per item
  *                           and direction (the forward sweep runs through its tiles, the backward pass of phase 1 walks the item and
  *                           leaves every tile's start vector), so the back half keeps its ~4096 tiles while phase 1 pays half the

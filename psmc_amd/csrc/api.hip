@@ -148,7 +148,7 @@ extern "C" void psmc_hip_destroy(psmc_hip_ctx *c)
 	if (c->parent) { // a batch child owns its plan only: streams, events, staging, observations and tables are the parent's
 		// (d_seg*: a child that took the exact fallback of psmc_hip_estep -- 65..128 states, a matrix without the PSMC form)
 		void *mine[] = {c->d_seg_off, c->d_seg_len, c->d_work, c->d_chunks, c->d_entry, c->d_bexit, c->d_Cpart, c->d_Epart, c->d_LLpart,
-		                c->d_stage, c->d_stats, c->d_warm, c->d_bentry, c->d_dirty, c->d_cnt, c->d_gate, c->d_touch, c->d_items, c->d_ftiles, c->d_Kcol,
+		                c->d_stage, c->d_stats, c->d_warm, c->d_bentry, c->d_dirty, c->d_cnt, c->d_gate, c->d_queue, c->d_touch, c->d_items, c->d_ftiles, c->d_Kcol,
 		                c->d_segA, c->d_segE, c->d_segA0, c->d_chk};
 		for (void *p : mine) if (p) (void)hipFree(p);
 		if (c->h_cnt) (void)hipHostFree(c->h_cnt);
@@ -169,7 +169,7 @@ extern "C" void psmc_hip_destroy(psmc_hip_ctx *c)
 	if (!c->obs_borrowed && c->d_obs) (void)hipFree(c->d_obs);
 	void *ptrs[] = {c->d_seg_off, c->d_seg_len, c->d_work, c->d_par, c->d_f, c->d_b, c->d_s, c->d_segA, c->d_segE,
 	                c->d_segA0, c->d_chk, c->d_chunks, c->d_entry, c->d_bexit, c->d_Cpart, c->d_Epart, c->d_LLpart,
-	                c->d_stage, c->d_stats, c->d_warm, c->d_bentry, c->d_dirty, c->d_cnt, c->d_gate, c->d_touch, c->d_sb, c->d_items, c->d_ftiles, c->d_Kcol,
+	                c->d_stage, c->d_stats, c->d_warm, c->d_bentry, c->d_dirty, c->d_cnt, c->d_gate, c->d_queue, c->d_touch, c->d_sb, c->d_items, c->d_ftiles, c->d_Kcol,
 	                c->d_bw_seg, c->d_bw_par, c->d_bw_tab, c->d_bpar, c->d_s_all, c->d_cu_mask, c->d_lkp, c->d_lkoff, c->d_b2};
 	for (void *p : ptrs) if (p) (void)hipFree(p);
 	if (c->h_par) (void)hipHostFree(c->h_par);
@@ -206,6 +206,8 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "prev_start") { c->prev_start = v != 0 ? 1 : 0; c->prev_ok = false; c->plan_dirty = true; c->chunk_cap = 0; }
 	else if (k == "warm_shift") { if (v < 0 || v > 4) return PSMC_HIP_EINVAL; c->warm_shift = (int)v; c->warm_shift_set = true; c->plan_dirty = true; }
 	else if (k == "merge1") { if (v < -1 || v > 1) return PSMC_HIP_EINVAL; c->merge1 = (int)v; c->plan_dirty = true; }
+	else if (k == "phase1") { if (v < -1 || v > 1) return PSMC_HIP_EINVAL; c->phase1 = (int)v; }
+	else if (k == "phase1_waves") { if (v < 1 || v > 4) return PSMC_HIP_EINVAL; c->phase1_waves = (int)v; }
 	else if (k == "lanes8") { if (v < -1 || v > 1) return PSMC_HIP_EINVAL; c->lanes8 = (int)v; }
 	else if (k == "gap_tiles") { c->gap_tiles = v != 0 ? 1 : 0; c->plan_dirty = true; c->items_dirty = true; }
 	else if (k == "coarse") { if (v < -1 || v > 16) return PSMC_HIP_EINVAL; c->coarse = (int)v; c->plan_dirty = true; c->items_dirty = true; }

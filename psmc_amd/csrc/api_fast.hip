@@ -312,6 +312,35 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 		c->n_fix_f = (int)fx.size() / 2;
 		if (!fx.empty()) HIPCHK(c, hipMemcpy(c->d_items + (size_t)30 * nc, fx.data(), sizeof(int) * fx.size(), hipMemcpyHostToDevice));
 	}
+	{ // phase1 = 1 (estep_struct.hip k_phase1_queue): the blocks of the bulk forward sweep and of the backward warm-up pass as one queue,
+	  // longest first.  A block's cost is the steps of its longest row times the time a step of its kind takes at two waves per SIMD
+	  // (profiles/r06_phase1_wave_trace.txt: 0.504 us forward, which stores its table, 0.534 us backward); ties keep the forward block first
+		const int n4f = c->n_items_f - c->n_long_f, n4b = c->n_items_b - c->n_long_b - c->n_B_b;
+		std::vector<std::pair<long long, int>> qk;
+		for (int k = 0; 4 * k < n4f; ++k) {
+			long long st = 0;
+			for (int i = c->n_long_f + 4 * k; i < std::min(c->n_long_f + 4 * k + 4, c->n_items_f); ++i) {
+				const Chunk &h = c->chunks[kf[i].second.first], &l = c->chunks[kf[i].second.first + kf[i].second.second - 1];
+				st = std::max(st, (long long)(l.hi - std::max(1, h.lo - chunk_warm_f(h, W)) + 1));
+			}
+			qk.push_back({-st * 504, 2 * k});
+		}
+		for (int k = 0; 4 * k < n4b; ++k) {
+			long long st = 0;
+			for (int i = c->n_long_b + 4 * k; i < std::min(c->n_long_b + 4 * k + 4, c->n_long_b + n4b); ++i) {
+				const Chunk &lo = c->chunks[kb[i].second.first], &top = c->chunks[kb[i].second.first + kb[i].second.second - 1];
+				const int q = std::min(top.hi + chunk_warm_b(top, W) + 1, top.L); // the warm-up pass runs down to the top of its top tile, coarse: of its lowest
+				st = std::max(st, (long long)(q - (coarse > 1 ? std::min(lo.hi, lo.L - 1) : std::min(top.hi, top.L - 1))));
+			}
+			qk.push_back({-st * 534, 2 * k + 1});
+		}
+		std::stable_sort(qk.begin(), qk.end(), [](const std::pair<long long, int> &x, const std::pair<long long, int> &y) { return x.first < y.first; });
+		std::vector<int> qv(qk.size());
+		for (size_t i = 0; i < qk.size(); ++i) qv[i] = qk[i].second;
+		if (c->queue_cap < qv.size()) { int rc; if ((rc = dev_alloc(c, &c->d_queue, qv.size()))) return rc; c->queue_cap = qv.size(); }
+		c->n_queue = (int)qv.size();
+		if (!qv.empty()) HIPCHK(c, hipMemcpy(c->d_queue, qv.data(), sizeof(int) * qv.size(), hipMemcpyHostToDevice));
+	}
 	// Walk lists and transfer-matrix chains.  A run of >= kc_min tiles is a "chain run": a walk delivers the start vector
 	// of its head tile (the usual speculative warm-up, nothing more: walk item with count <= 0, see k_walk1_struct; round 1
 	// and most of round 2 also walked THROUGH the head tile, 3712 dependent steps whose result nobody read -- measured
@@ -563,6 +592,14 @@ int enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double
 		c->prev_ok = false;
 	}
 	p.d_gate = (c->gate >= 0 ? c->gate != 0 : coarse > 1) ? c->d_gate : nullptr;
+	// phase 1's bulk blocks from one work queue (estep_struct.hip k_phase1_queue): the fused back half of a 64-state model, four tiles per wave,
+	// the bulk passes on streams of their own (not merge1, whose one grid already spreads them)
+	if (c->phase1 != 0 && c->use_struct && p.fused == 1 && c->ns == 64 && !p.lanes8 && !p.merge1 && c->overlap && c->n_queue > 0) {
+		int cus = c->cu_count;
+		if (cus <= 0 && (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0)) return fail(c, PSMC_HIP_EDEVICE, "hipDeviceGetAttribute");
+		p.d_queue = c->d_queue; p.n_queue = c->n_queue; p.d_qhead = c->d_gate + 2;
+		p.q_grid = std::min(c->n_queue, 4 * cus * c->phase1_waves); // (four SIMDs per compute unit)
+	}
 	p.coarse = coarse; p.d_singles_b = c->d_items + 24 * (size_t)p.n_chunks; p.n_singles_b = c->n_singles_b;
 	p.n_B_b = c->n_B_b; p.runs_in_b = c->runs_in_b ? 1 : 0; p.n_list_a = c->n_list_a; p.n_list_b = c->n_list_b; p.d_ftiles = c->d_ftiles; p.count_group = c->count_group;
 	c->timing_two_launches = p.fused == 1 && p.n_list_b > 0;

@@ -550,6 +550,7 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 	(void)hipMemsetAsync(p.d_warm, 0, 2 * sizeof(unsigned long long), sm);
 	(void)hipMemsetAsync(p.d_touch_f, 0, 3 * sizeof(int) * (size_t)p.n_chunks, sm); // touch_f | touch_b | fmerge
 	if (p.d_gate) (void)hipMemsetAsync(p.d_gate, 0, 2 * sizeof(int), sm); // started-counters of the walks and of the bulk grid
+	if (p.q_grid > 0) (void)hipMemsetAsync(p.d_qhead, 0, sizeof(int), sm); // head of phase 1's work queue
 	if (p.ev[0]) (void)hipEventRecord(p.ev[0], sm);
 	(void)hipEventRecord(p.evx[0], sm);
 	if (ov) (void)hipStreamWaitEvent(sa, p.evx[0], 0); // parameters uploaded, flags cleared
@@ -585,7 +586,7 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 		if (p.n_kc > 0) { // long runs: transfer matrices of their tiles (a stream of their own), then the chain
 			if (ov) (void)hipStreamWaitEvent(sk, p.evx[0], 0);
 			// ... and the matrices wait until the bulk grid has been dispatched (merged: both directions; else the forward sweep)
-			if (gated && sk != sm) launch_gate(sk, p.d_gate + 1, std::min(2048, mg ? (p.n_items_f - ff0 + rw - 1) / rw + (p.n_items_b - fb0 - p.n_B_b + rw - 1) / rw : (p.structured ? (p.n_items_f - ff0 + rw - 1) / rw : 0)));
+			if (gated && sk != sm) launch_gate(sk, p.d_gate + 1, std::min(2048, mg ? (p.n_items_f - ff0 + rw - 1) / rw + (p.n_items_b - fb0 - p.n_B_b + rw - 1) / rw : (p.q_grid > 0 ? p.q_grid : (p.structured ? (p.n_items_f - ff0 + rw - 1) / rw : 0))));
 			launch_kchain(p, sk, sw, p.evx[8]);
 		}
 		(void)hipEventRecord(p.evx[6], sw);
@@ -607,7 +608,8 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 		if (p.ev[7]) (void)hipEventRecord(p.ev[7], sm);
 		launch_sweeps(p, sm, ff0, p.n_items_f - ff0, fb0, p.n_items_b - fb0, false);
 		if (p.ev[6]) (void)hipEventRecord(p.ev[6], sm);
-	} else if (p.structured) launch_fwd_struct(p, sm, 0, ff0, p.n_items_f - ff0);
+	} else if (p.q_grid > 0) launch_phase1_queue(p, sm, ff0, p.n_items_f - ff0, fb0, p.n_items_b - fb0 - p.n_B_b); // both bulk passes (api_fast.hip)
+	else if (p.structured) launch_fwd_struct(p, sm, 0, ff0, p.n_items_f - ff0);
 	else launch_fwd<false>(p, sm);
 	if (!mg && p.merge) launch_fwd_struct(p, sm, 6, 0, p.n_fix_f); // the fix pass over the bulk tiles (estep_struct.hip FwdCtl)
 	if (!mg) (void)hipEventRecord(p.evx[1], sm);
@@ -623,7 +625,7 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 		// Fused backward + counts (estep_fused.hip): a warm-up-only pass of the 4-tiles-per-wave sweep leaves
 		// every bulk tile's start vector (beside the forward sweep, or in its grid); then one wave per group of four
 		// tiles walks them backwards and feeds the matrix cores.  bt never reaches HBM.
-		if (!mg) launch_bwd_struct(p, sa, 4, fb0, p.n_items_b - fb0 - p.n_B_b);
+		if (!mg && p.q_grid <= 0) launch_bwd_struct(p, sa, 4, fb0, p.n_items_b - fb0 - p.n_B_b); // (queue: in the grid above)
 		// fused == 2 (item lists): the tiles of backward runs are a side pass on the transfer-matrix stream; it reads X of tiles
 		// that may belong to the BULK forward sweep (a tile can be glued backward only), so it follows that sweep as well as
 		// the run tiles.  (Until round 2 it followed the run tiles only and could read a bulk tile's X of the PREVIOUS E-step;

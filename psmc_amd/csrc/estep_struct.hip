@@ -560,6 +560,39 @@ __global__ __launch_bounds__(64) void k_bwd_struct(const double *__restrict__ sp
 	bwd_struct_body<REPAIR, NPL, LPT>(blockIdx.x, sp, e, obs, chunks, items, n_items, W, T, flags, bt, sb, bentry, bexit, touch_b);
 }
 
+// ------------------------------------------------------------------ phase 1 from a work queue ("phase1" = 1)
+// The bulk forward sweep and the backward warm-up pass of the fused back half as ONE persistent grid of a fixed number of
+// waves (two per SIMD by default) that pull their blocks from a queue the host sorted by estimated issue cost, longest first
+// (api_fast.hip build_items).  The separate launches deal their waves out at dispatch time, with no knowledge of how long a
+// block runs or of the other stream's grid: a few SIMDs got a third or fourth wave and set the end of the phase.  An item is a
+// block of the launch it replaces, computed by the same body from the same block index: which wave runs it changes nothing.
+// q[i] = kind (0 forward, 1 backward) | block << 1.
+template <bool CK>
+__global__ __launch_bounds__(64) void k_phase1_queue(const double *__restrict__ sp, const double *__restrict__ e,
+                                                       const double *__restrict__ a0, const uint8_t *__restrict__ obs,
+                                                       const Chunk *__restrict__ chunks, const SweepItem *__restrict__ items_f, int n_f,
+                                                       const SweepItem *__restrict__ items_b, int n_b, int W, int T, int flags_f,
+                                                       int flags_b, double *__restrict__ f, double *__restrict__ invd,
+                                                       double *__restrict__ entry, double *__restrict__ bt, double *__restrict__ sb,
+                                                       double *__restrict__ bentry, double *__restrict__ bexit, int *__restrict__ touch_f,
+                                                       int *__restrict__ touch_b, const int *__restrict__ q, int n_q,
+                                                       int *__restrict__ head, int *__restrict__ started, const FwdCtl ctl)
+{
+	announce_start(started);
+	for (;;) {
+		int i = 0;
+		if (threadIdx.x == 0) i = atomicAdd(head, 1);
+		i = __builtin_amdgcn_readfirstlane(i);
+		if (i >= n_q) break;
+		const int w = q[i];
+		__builtin_amdgcn_s_setprio(0); // (the bodies raise it for themselves)
+		if ((w & 1) == 0)
+			fwd_struct_body<false, 4, CK>(w >> 1, sp, e, a0, obs, chunks, items_f, n_f, W, T, flags_f, f, invd, entry, touch_f, ctl);
+		else
+			bwd_struct_body<false, 4>(w >> 1, sp, e, obs, chunks, items_b, n_b, W, T, flags_b, bt, sb, bentry, bexit, touch_b);
+	}
+}
+
 // Both directions' walks over the glued runs in ONE launch (blocks [0, nbf) forward, the rest backward):
 // a process only gets a handful of hardware queues, and a walk that shares one with another stream's
 // kernel would wait for it.
@@ -1095,6 +1128,21 @@ void launch_bwd_struct(const EstepLaunch &p, hipStream_t st, int which, int firs
 	else { if (rep) PSMC_LB(true, 4); else PSMC_LB(false, 4); }
 	PSMC_DBG("launch_bwd_struct", which, first, n_items);
 #undef PSMC_LB
+}
+// the queue grid of phase 1 (k_phase1_queue): forward items [ff, ff+nf) as launch_fwd_struct(which 0) would run them, backward items
+// [fb, fb+nb) as launch_bwd_struct(which 4); 64 states, four tiles per wave
+void launch_phase1_queue(const EstepLaunch &p, hipStream_t st, int ff, int nf, int fb, int nb)
+{
+	if (p.n_queue <= 0 || p.q_grid <= 0) return;
+	const int flags_f = (p.ckpt ? SWEEP_CKPT : 0) | (p.coarse > 1 ? SWEEP_COARSE : 0);
+	const int flags_b = p.coarse > 1 ? (SWEEP_WALK | SWEEP_COARSE) : SWEEP_TOP_ONLY;
+	const FwdCtl ctl = {p.d_prevx, p.tol, nullptr, nullptr, p.d_fmerge, p.d_finv};
+#define PSMC_LQ(CK) hipLaunchKernelGGL(k_phase1_queue<CK>, dim3(p.q_grid), dim3(64), 0, st, p.d_sp, p.d_e, p.d_a0, p.d_obs, p.d_chunks, \
+		(const SweepItem *)p.d_items_f + ff, nf, (const SweepItem *)p.d_items_b + fb, nb, p.warmup, p.tile_len, flags_f, flags_b, p.d_f, p.d_s, \
+		p.d_entry, p.d_b, p.d_sb, p.d_bentry, p.d_bexit, p.d_touch_f, p.d_touch_b, p.d_queue, p.n_queue, p.d_qhead, p.d_gate ? p.d_gate + 1 : nullptr, ctl)
+	if (p.ckpt) PSMC_LQ(true); else PSMC_LQ(false);
+#undef PSMC_LQ
+	PSMC_DBG("launch_phase1_queue", nf, nb, p.q_grid);
 }
 void launch_compact(const EstepLaunch &p, hipStream_t st, bool bwd)
 {

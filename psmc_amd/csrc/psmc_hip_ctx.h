@@ -50,6 +50,11 @@ struct psmc_hip_ctx {
 	int gate = -1;             // "gate": order the dispatch of phase 1's grids walks -> bulk -> transfer matrices (estep_struct.hip k_gate); -1 = with coarse
 	                           // items (measured: without them the bulk grid is the critical path and walks that land late, stacked on few SIMDs, slow fewer of its waves)
 	int *d_gate = nullptr;
+	int phase1 = -1;           // "phase1": 1 = phase 1's bulk blocks (forward sweep, backward warm-up pass) from one work queue, longest first, pulled by a
+	                           // persistent grid (estep_struct.hip k_phase1_queue); 0 = two launches on streams of their own; -1 = by the plan
+	int phase1_waves = 2;      // "phase1_waves": waves per SIMD of that grid
+	int *d_queue = nullptr;    // the queue (build_items), n_queue entries
+	size_t queue_cap = 0; int n_queue = 0;
 	int coarse = -1;           // "coarse": a bulk sweep item spans up to this many consecutive tiles of a segment: ONE speculative warm-up per item and
 	                           // direction, the backward pass walks the item and leaves every tile's start vector (build_items); -1 = by the plan
 	int coarse_used = 1, items_coarse = -1;

@@ -80,6 +80,8 @@ struct EstepLaunch {
 	int lanes8;                       // 64 states: the bulk sweeps of phase 1 run eight tiles per wave (estep_struct.hip launch_fwd_struct)
 	int *d_gate;                      // [0] walk blocks started, [1] bulk blocks started: the gates that order the DISPATCH of phase 1's grids (estep_struct.hip
 	                                  // k_gate); null: no gates
+	const int *d_queue; int n_queue;  // phase1 = 1: the bulk blocks of phase 1 as one work queue, longest first (kind | block << 1: api_fast.hip build_items)
+	int q_grid; int *d_qhead;         // ... the persistent grid that pulls them (k_phase1_queue) and its head word; q_grid 0: separate launches
 	int coarse;                       // > 1: a bulk item spans up to this many tiles (one speculation per item; the backward pass of the fused /
 	                                  // factored plans WALKS its item and leaves every tile's start vector): api_fast.hip build_items
 	const int *d_singles_b; int n_singles_b; // coarse > 1, factored back half: every tile outside the backward runs as a one-tile item
@@ -166,6 +168,7 @@ void launch_gate(hipStream_t st, const int *ctr, int want);
 int walk_blocks(const EstepLaunch &p);
 void launch_kchain(const EstepLaunch &p, hipStream_t st_cols, hipStream_t st_chain, hipEvent_t ev_cols);
 void launch_sweeps(const EstepLaunch &p, hipStream_t st, int ff, int nf, int fb, int nb, bool top_only);
+void launch_phase1_queue(const EstepLaunch &p, hipStream_t st, int ff, int nf, int fb, int nb);
 void launch_bwd_count(const EstepLaunch &p, hipStream_t st, int list, bool redo, bool all_from_bentry = false);
 void launch_bwd_acc(const EstepLaunch &p, hipStream_t st, int which, int first, int n);
 void launch_reduce_factored(const EstepLaunch &p, hipStream_t st);
