@@ -285,25 +285,45 @@ int psmc_hip_fast_info(psmc_hip_ctx *ctx, int out[8]);
  * with "fuse" = 0 (the fused back half never stores bt), all of f only without checkpointing. */
 int psmc_hip_get_tables(psmc_hip_ctx *ctx, int seg, double *f, double *b, double *s);
 
-/* Posterior decoding of one segment on the device after an exact E-step: replaces
+/* Posterior decoding of one segment on the device after an exact E-step (fast mode: see below): replaces
  * hmm_post_decode (khmm.c:264-281) + the max-posterior bookkeeping of aux.c:165-182.
  * path[u-1] = argmax_k f[u][k]*b[u][k]*s[u] (first maximum wins), maxp[u-1] = its value;
  * 12 bytes per bin leave the GPU instead of the 2*8*n of the tables. */
 int psmc_hip_decode(psmc_hip_ctx *ctx, int seg, int32_t *path, double *maxp);
 
-/* Full posterior decoding of one segment on the device after an exact E-step: replaces the -D branch of psmc_decode
+/* Full posterior decoding of one segment on the device after an exact E-step (fast mode: see below): replaces the -D branch of psmc_decode
  * (aux.c:183-200).  post[(u-1)*n + l] = f[u][l]*b[u][l]*s[u] (hmm_post_state, khmm.c:285-292); recomb[u-1] = 1 -
  * sum_l f[u][l]*a[l][l]*b[u+1][l]*e[o_{u+1}][l] for u < L and 0 at u = L (aux.c:189-193) -- every product left to
  * right, the sum in state order: the reference's doubles.  Either output may be NULL.  8*(n+1) bytes per bin leave the
  * GPU instead of the 16*n + 8 of the tables. */
 int psmc_hip_posterior(psmc_hip_ctx *ctx, int seg, double *post, double *recomb);
 
-/* Posterior-weighted counts of one segment on the device: replaces the -c branch of psmc_decode (aux.c:202-219).
+/* Posterior-weighted counts of one segment on the device (fast mode: see below): replaces the -c branch of psmc_decode (aux.c:202-219).
  * cnt1 = the segment's record of a cntcpg file (l positions x n_cnt int32, utils/cntcpg.c); cnt (n*n_cnt, in/out)
  * are the running totals, cnt[k*n_cnt + j] += post[u][k] * cnt1[(u-1)*n_cnt + j] for u = 1..min(L, l) in position
  * order -- call once per segment in input order with the same cnt, as the reference's loop does.  Only
  * 4*n_cnt bytes per bin go to the GPU and n*n_cnt doubles come back. */
 int psmc_hip_post_counts(psmc_hip_ctx *ctx, int seg, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt);
+
+/* The reference's scaling factors s[u] of one segment (hmm_forward, khmm.c:170-186; the PR line of -s, aux.c:159-164), L doubles.
+ * Exact mode (and more than 128 states, and the exact fallback below): a copy of the table, the doubles psmc_hip_get_tables
+ * returns as s.  Fast mode: s_u = sum X_u / sum X_{u-1} / inv_u from the fast forward table, X_{u-1} being a tile's own start
+ * vector at its first position and s_1 = sum_k a0_k e_k(o_1); within 1e-11 relative of the exact value. */
+int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
+
+/* Decoding on a FAST context (up to 128 states): psmc_hip_decode, _posterior, _post_counts and _scales read what the last
+ * single E-step (psmc_hip_estep / _estep_device) left:
+ *   - the fast tables X and bt -- the dense sweeps (any matrix, <= 64 states) or the structured ones with the unfused back half
+ *     ("fuse" = 0 up to 64 states, "fuse128" = 0 for 65..128): scale-free kernels (estep_post_fast.hip) compute
+ *     gamma_u(k) = X_u(k) bt_u(k) / e_k(o_u) normalised over k, i.e. the posterior of k_expect_mfma, not the reference's doubles.
+ *     Tolerances against an exact context given the same parameters: posterior rows, maxp and recomb within 1e-9 absolute;
+ *     scales 1e-11 relative; post_counts 1e-9 relative on every cell >= 1e-6 of the largest; the path equal wherever the two
+ *     largest exact posteriors differ by more than 2e-9 (a near-tie may go either way);
+ *   - the exact tables (65..128 states and a matrix without the PSMC form: fast mode ran the exact kernels): the exact
+ *     kernels, the reference's doubles;
+ *   - PSMC_HIP_ESTATE after the fused or the factored back half (no bt: set "fuse" / "fuse128" to 0 first), after a batch,
+ *     or before any single E-step; PSMC_HIP_ENOTSUP after an E-step whose forward fix pass ran ("merge" = 1).
+ * A decoding call reads the tables only: it changes nothing a later E-step uses (plan, glue, warm-ups). */
 
 /* ---- one E-step sharded over several GPUs of the node (replaces em.c:36-55 + the serial
  * hmm_add_expect of khmm.c:346-359 by per-device E-steps and ONE exchange per EM iteration).  One process; devices[]
@@ -339,7 +359,7 @@ int  psmc_hip_group_selfcheck(psmc_hip_group *g, int out[4]);
  * shards' vectors, 3 ordered per-segment sum (exact mode) */
 int  psmc_hip_group_info(psmc_hip_group *g, int *n_shards, int32_t *shard_of_seg, int *last_reduce);
 /* the context and local index holding segment `seg` after a group E-step, for psmc_hip_get_tables / _decode /
- * _posterior / _post_counts (psmc_decode, aux.c:150-231) */
+ * _posterior / _post_counts / _scales (psmc_decode, aux.c:150-231) */
 int  psmc_hip_group_route(psmc_hip_group *g, int seg, psmc_hip_ctx **ctx, int *local_seg);
 /* psmc_hip_estep_factored with the result left in HBM: [SL|SU|DG|CL|CU | E | LL], 7n + 1 doubles, asynchronous on
  * `stream` like psmc_hip_estep_device */

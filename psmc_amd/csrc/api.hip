@@ -663,7 +663,10 @@ extern "C" int psmc_hip_estep(psmc_hip_ctx *c, const double *a, const double *e,
 	// 65..128 states and a matrix without the two rank-1 triangles (psmc_cap_matrix, a foreign HMM): the tiled dense
 	// sweeps keep one lane per state, so the dense fallback there is the exact path (two states per lane, the matrix in
 	// LDS, one wave per segment) -- slower, any matrix, and trivially inside the fast-mode tolerance
-	if (rc == PSMC_HIP_ENOTSUP && c->ns == 128 && !c->use_struct) return estep_exact(c, a, e, a0, A, E, A0, LL, chk);
+	if (rc == PSMC_HIP_ENOTSUP && c->ns == 128 && !c->use_struct) {
+		rc = estep_exact(c, a, e, a0, A, E, A0, LL, chk);
+		if (rc == 0) { c->dec_kind = DEC_EXACT; c->dec_serial = c->tab_serial; }
+	}
 	return rc;
 }
 
@@ -688,10 +691,57 @@ extern "C" int psmc_hip_get_tables(psmc_hip_ctx *c, int seg, double *f, double *
 	return PSMC_HIP_OK;
 }
 
+// Which tables the decoding entry points of context c read (the exact ones: exact mode, more than 128 states, or the exact
+// fallback of a fast E-step), and for the fast tables the segment's first tile in the plan of the E-step that wrote them.
+// Returns DEC_EXACT, DEC_FAST, or a PSMC_HIP_E* code (message set).  Reads nothing but the context.
+static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_tile)
+{
+	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return DEC_EXACT;
+	char msg[256];
+	if (!c->d_f || c->tables_batch || c->dec_kind == DEC_NONE || c->dec_serial != c->tab_serial) {
+		snprintf(msg, sizeof msg, "%s: no single E-step yet", who);
+		return fail(c, PSMC_HIP_ESTATE, msg);
+	}
+	if (c->dec_kind == DEC_EXACT) return DEC_EXACT;
+	if (c->dec_kind == DEC_MERGED) {
+		snprintf(msg, sizeof msg, "%s: not after an E-step with the forward fix pass (merge=1: its forward table carries per-tile factors)", who);
+		return fail(c, PSMC_HIP_ENOTSUP, msg);
+	}
+	if (c->dec_kind != DEC_FAST || !c->have_b) {
+		snprintf(msg, sizeof msg, "%s: the last fast E-step kept no backward table (fused or factored back half); run it with fuse=0 (<= 64 states) / fuse128=0 (65..128)", who);
+		return fail(c, PSMC_HIP_ESTATE, msg);
+	}
+	for (size_t t = 0; t < c->chunks.size(); ++t)
+		if (c->chunk_seg[t] == seg) { *first_tile = (int)t; return DEC_FAST; }
+	snprintf(msg, sizeof msg, "%s: segment %d was not in the selection of the last E-step", who, seg);
+	return fail(c, PSMC_HIP_ESTATE, msg);
+}
+
+// the parameter block's pieces the fast decoding kernels read (fill_params / fill_common)
+static const double *par_e(const psmc_hip_ctx *c) { return c->ns == 128 ? c->d_par + 32768 : c->d_par + 4 * 4096; }
+static const double *par_a0(const psmc_hip_ctx *c) { return par_e(c) + 3 * c->ns; }
+static const double *par_re(const psmc_hip_ctx *c) { return c->ns == 128 ? c->d_par + psmc_hip_ctx::RE128_OFF : c->d_par + 4 * 4096 + 192 + 64; }
+
 extern "C" int psmc_hip_decode(psmc_hip_ctx *c, int seg, int32_t *path, double *maxp)
 {
 	if (!c || seg < 0 || seg >= c->n_seg || !path) return fail(c, PSMC_HIP_EINVAL, "decode: bad argument");
-	if (c->mode != PSMC_HIP_MODE_EXACT && c->ns <= 128) return fail(c, PSMC_HIP_ENOTSUP, "decode: exact mode only");
+	int first = 0;
+	const int src = decode_source(c, seg, "decode", &first);
+	if (src < 0) return src;
+	if (src == DEC_FAST) {
+		HIPCHK(c, hipSetDevice(c->device));
+		const int L = c->L[seg];
+		int32_t *dp = nullptr; double *dm = nullptr;
+		if (hipMalloc((void **)&dp, sizeof(int32_t) * (size_t)L) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
+		if (hipMalloc((void **)&dm, sizeof(double) * (size_t)L) != hipSuccess) { (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
+		int rc = launch_post_fast(c->stream, c->d_f, c->d_b, c->d_sb, par_re(c), c->d_par, c->d_obs, c->off[seg], L, c->n, c->ns, nullptr, nullptr, dp, dm);
+		hipError_t e1 = hipMemcpyAsync(path, dp, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, c->stream);
+		hipError_t e2 = maxp ? hipMemcpyAsync(maxp, dm, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+		hipError_t e3 = hipStreamSynchronize(c->stream);
+		(void)hipFree(dp); (void)hipFree(dm);
+		if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "decode");
+		return PSMC_HIP_OK;
+	}
 	if (!c->d_f || !c->have_b || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "decode: no single E-step yet");
 	HIPCHK(c, hipSetDevice(c->device));
 	const int L = c->L[seg];
@@ -711,7 +761,24 @@ extern "C" int psmc_hip_decode(psmc_hip_ctx *c, int seg, int32_t *path, double *
 extern "C" int psmc_hip_posterior(psmc_hip_ctx *c, int seg, double *post, double *recomb)
 {
 	if (!c || seg < 0 || seg >= c->n_seg || (!post && !recomb)) return fail(c, PSMC_HIP_EINVAL, "posterior: bad argument");
-	if (c->mode != PSMC_HIP_MODE_EXACT && c->ns <= 128) return fail(c, PSMC_HIP_ENOTSUP, "posterior: exact mode only");
+	int first = 0;
+	const int src = decode_source(c, seg, "posterior", &first);
+	if (src < 0) return src;
+	if (src == DEC_FAST) {
+		HIPCHK(c, hipSetDevice(c->device));
+		const int L = c->L[seg], n = c->n;
+		double *dp = nullptr, *dr = nullptr;
+		if (post && hipMalloc((void **)&dp, sizeof(double) * (size_t)L * n) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
+		if (recomb && hipMalloc((void **)&dr, sizeof(double) * (size_t)L) != hipSuccess) { if (dp) (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
+		int rc = launch_post_fast(c->stream, c->d_f, c->d_b, c->d_sb, par_re(c), c->d_par, c->d_obs, c->off[seg], L, n, c->ns, dp, dr, nullptr, nullptr);
+		hipError_t e1 = post ? hipMemcpyAsync(post, dp, sizeof(double) * (size_t)L * n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+		hipError_t e2 = recomb ? hipMemcpyAsync(recomb, dr, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+		hipError_t e3 = hipStreamSynchronize(c->stream);
+		if (dp) (void)hipFree(dp);
+		if (dr) (void)hipFree(dr);
+		if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "posterior");
+		return PSMC_HIP_OK;
+	}
 	if (!c->d_f || !c->have_b || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "posterior: no single E-step yet");
 	HIPCHK(c, hipSetDevice(c->device));
 	const int L = c->L[seg], n = c->n;
@@ -733,7 +800,27 @@ extern "C" int psmc_hip_posterior(psmc_hip_ctx *c, int seg, double *post, double
 extern "C" int psmc_hip_post_counts(psmc_hip_ctx *c, int seg, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt)
 {
 	if (!c || seg < 0 || seg >= c->n_seg || !cnt || l < 0 || n_cnt < 1 || (l > 0 && !cnt1)) return fail(c, PSMC_HIP_EINVAL, "post_counts: bad argument");
-	if (c->mode != PSMC_HIP_MODE_EXACT && c->ns <= 128) return fail(c, PSMC_HIP_ENOTSUP, "post_counts: exact mode only");
+	int first = 0;
+	const int src = decode_source(c, seg, "post_counts", &first);
+	if (src < 0) return src;
+	if (src == DEC_FAST) {
+		HIPCHK(c, hipSetDevice(c->device));
+		const int L = c->L[seg], n = c->n, min_l = L < l ? L : l;
+		if (min_l == 0) return PSMC_HIP_OK;
+		const size_t n_part = (size_t)post_counts_fast_blocks(min_l) * n_cnt * c->ns;
+		int32_t *d1 = nullptr; double *dc = nullptr, *dpart = nullptr;
+		if (hipMalloc((void **)&d1, sizeof(int32_t) * (size_t)min_l * n_cnt) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
+		if (hipMalloc((void **)&dc, sizeof(double) * (size_t)n * n_cnt) != hipSuccess) { (void)hipFree(d1); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
+		if (hipMalloc((void **)&dpart, sizeof(double) * n_part) != hipSuccess) { (void)hipFree(d1); (void)hipFree(dc); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
+		hipError_t e0 = hipMemcpyAsync(d1, cnt1, sizeof(int32_t) * (size_t)min_l * n_cnt, hipMemcpyHostToDevice, c->stream);
+		hipError_t e1 = hipMemcpyAsync(dc, cnt, sizeof(double) * (size_t)n * n_cnt, hipMemcpyHostToDevice, c->stream);
+		int rc = launch_post_counts_fast(c->stream, c->d_f, c->d_b, par_re(c), c->d_obs, c->off[seg], L, min_l, d1, n_cnt, n, c->ns, dpart, dc);
+		hipError_t e2 = hipMemcpyAsync(cnt, dc, sizeof(double) * (size_t)n * n_cnt, hipMemcpyDeviceToHost, c->stream);
+		hipError_t e3 = hipStreamSynchronize(c->stream);
+		(void)hipFree(d1); (void)hipFree(dc); (void)hipFree(dpart);
+		if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "post_counts");
+		return PSMC_HIP_OK;
+	}
 	if (!c->d_f || !c->have_b || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "post_counts: no single E-step yet");
 	HIPCHK(c, hipSetDevice(c->device));
 	const int L = c->L[seg], n = c->n, min_l = L < l ? L : l;
@@ -749,5 +836,28 @@ extern "C" int psmc_hip_post_counts(psmc_hip_ctx *c, int seg, const int32_t *cnt
 	hipError_t e3 = hipStreamSynchronize(c->stream);
 	(void)hipFree(d1); (void)hipFree(dc);
 	if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "post_counts");
+	return PSMC_HIP_OK;
+}
+
+extern "C" int psmc_hip_scales(psmc_hip_ctx *c, int seg, double *s)
+{
+	if (!c || seg < 0 || seg >= c->n_seg || !s) return fail(c, PSMC_HIP_EINVAL, "scales: bad argument");
+	int first = 0;
+	const int src = decode_source(c, seg, "scales", &first);
+	if (src < 0) return src;
+	if (!c->d_f || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "scales: no single E-step yet");
+	HIPCHK(c, hipSetDevice(c->device));
+	const int L = c->L[seg];
+	if (src == DEC_EXACT) { // the exact tables hold s itself (the same doubles psmc_hip_get_tables returns)
+		HIPCHK(c, hipMemcpy(s, c->d_s + c->off[seg], sizeof(double) * (size_t)L, hipMemcpyDeviceToHost));
+		return PSMC_HIP_OK;
+	}
+	double *ds = nullptr;
+	if (hipMalloc((void **)&ds, sizeof(double) * (size_t)L) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
+	int rc = launch_scales_fast(c->stream, c->d_f, c->d_s, c->d_entry, par_a0(c), par_e(c), c->d_obs, c->off[seg], L, c->chunk_used, first, c->ns, ds);
+	hipError_t e1 = hipMemcpyAsync(s, ds, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream);
+	hipError_t e2 = hipStreamSynchronize(c->stream);
+	(void)hipFree(ds);
+	if (rc || e1 != hipSuccess || e2 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "scales");
 	return PSMC_HIP_OK;
 }

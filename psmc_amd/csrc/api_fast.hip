@@ -522,6 +522,7 @@ int enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double
 	HIPCHK(c, hipSetDevice(c->device));
 	if (c->n_seg < 1) return fail(c, PSMC_HIP_ESTATE, "estep: no segments loaded");
 	int rc;
+	c->dec_kind = DEC_NONE; // (until this E-step has succeeded)
 	const unsigned long long serial0 = dbg_root(c)->tab_serial; // has anybody used the tables since this context's last fast E-step?
 	if ((rc = ensure_tables(c, false))) return rc;
 	c->tables_batch = false;
@@ -657,6 +658,8 @@ int enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double
 	if (c->use_struct && c->adapt && c->merge_used && c->h_mis) adapt_warmups(c); // (only where falling short is cheap)
 	if (c->use_struct && c->learn) learn_groups(c);
 	if (c->use_struct) { c->prev_ok = true; c->prev_serial = dbg_root(c)->tab_serial; c->prev_f = c->d_f; c->prev_ckpt = p.ckpt; }
+	c->dec_kind = c->merge_used ? DEC_MERGED : (p.fused != 0 ? DEC_NO_BT : DEC_FAST);
+	c->dec_serial = dbg_root(c)->tab_serial;
 	return 0;
 }
 

@@ -23,6 +23,13 @@ using namespace psmc;
 
 #define HMM_TINY_H 1e-25
 
+// psmc_hip_ctx::dec_kind: the tables the decoding entry points of a fast context (<= 128 states) would read
+constexpr int DEC_NONE = 0;   // no single E-step since the tables were last used otherwise (or it failed)
+constexpr int DEC_FAST = 1;   // the fast tables X and bt (dense sweeps, or the structured ones with the unfused back half): estep_post_fast.hip
+constexpr int DEC_EXACT = 2;  // the exact tables (65..128 states, a matrix without the PSMC form: fast mode ran the exact kernels)
+constexpr int DEC_NO_BT = 3;  // the fused or factored back half: no backward table
+constexpr int DEC_MERGED = 4; // the forward fix pass ("merge"): its X carries per-tile factors
+
 struct psmc_hip_ctx {
 	int n = 0, ns = 64, device = 0, mode = PSMC_HIP_MODE_EXACT; // ns: states padded to 64 or 128
 	std::string err;
@@ -34,6 +41,9 @@ struct psmc_hip_ctx {
 	int struct_tiles = 8192;   // "struct_tiles": tiles aimed at when the structured sweeps are used (4 per wave)
 	bool use_struct = false, planned_struct = false;
 	int last_fused = 0, last_ckpt = 0; // what the last fast E-step ran: EstepLaunch::fused / ckpt
+	// what the last single E-step of a fast context left for the decoding entry points (api.hip decode_source), and the table
+	// serial it left it at: any later use of the tables (another E-step, a batch) makes it stale
+	int dec_kind = 0; unsigned long long dec_serial = 0;
 	bool want_factored = false; // this call asked for the factored statistics (psmc_hip_estep_factored)
 	int kc_sub = 4;            // "kc_sub": k_kcol2_struct cuts a tile's steps into this many ranges, one matrix (and one pair of waves) each; default: by the plan
 	int kcol_prio = 2;         // "kcol_prio": wave priority of k_kcol2_struct

@@ -178,6 +178,14 @@ int launch_post_full(hipStream_t st, const double *a, const double *e, const uin
                      const double *s, int64_t off, int L, int n, int ns, double *post, double *recomb);
 int launch_post_counts(hipStream_t st, const double *f, const double *b, const double *s, int64_t off, int min_l,
                        const int32_t *cnt1, int n_cnt, int n, int ns, double *cnt);
+// estep_post_fast.hip: posterior decoding from a fast E-step's X / bt tables (scale-free; see the file)
+int launch_post_fast(hipStream_t st, const double *f, const double *b, const double *sb, const double *re, const double *a,
+                     const uint8_t *obs, int64_t off, int L, int n, int ns, double *post, double *recomb, int32_t *path, double *maxp);
+int launch_scales_fast(hipStream_t st, const double *f, const double *invd, const double *entry, const double *a0, const double *e,
+                       const uint8_t *obs, int64_t off, int L, int T, int first, int ns, double *s);
+int post_counts_fast_blocks(int min_l); // partials (n_cnt x ns doubles each) launch_post_counts_fast needs in `part`
+int launch_post_counts_fast(hipStream_t st, const double *f, const double *b, const double *re, const uint8_t *obs, int64_t off,
+                            int L, int min_l, const int32_t *cnt1, int n_cnt, int n, int ns, double *part, double *cnt);
 int run_selftest(hipStream_t stream, unsigned *d_flags);
 int run_microbench(hipStream_t stream, double *d_out);
 int run_pipe_probe(hipStream_t stream, double *d_out, int n_waves, unsigned mask, int rounds);

@@ -28,7 +28,7 @@ EXPORTS = [
     "psmc_hip_last_error", "psmc_hip_set_option", "psmc_hip_load_segments",
     "psmc_hip_load_segments_device", "psmc_hip_select", "psmc_hip_estep",
     "psmc_hip_estep_segments", "psmc_hip_estep_batch", "psmc_hip_estep_batch_cb", "psmc_hip_reserve_batch_tables", "psmc_hip_batch_info", "psmc_hip_estep_device", "psmc_hip_fast_diag", "psmc_hip_fast_repairs", "psmc_hip_fast_info", "psmc_hip_estep_factored",
-    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts",
+    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales",
     "psmc_hip_group_selfcheck", "psmc_hip_fast_plan",
     "psmc_hip_group_create", "psmc_hip_group_destroy", "psmc_hip_group_last_error", "psmc_hip_group_set_option",
     "psmc_hip_group_load_segments", "psmc_hip_group_estep", "psmc_hip_group_estep_factored", "psmc_hip_group_info",
@@ -319,14 +319,17 @@ class HipEStep:
         return f, b, s
 
     def decode(self, seg):
-        """(path, maxp): posterior-argmax state and its probability per bin (khmm.c:264-281), exact mode."""
+        """(path, maxp): posterior-argmax state and its probability per bin (khmm.c:264-281).  Exact mode: the reference's
+        doubles; fast mode: from the last E-step's X and bt tables (it must have kept bt: fuse=0 / fuse128=0), within the
+        tolerances of include/psmc_hip.h."""
         L = int(self.lens[seg])
         path = np.zeros(L, dtype=np.int32); mp = np.zeros(L)
         self._chk(self.lib.psmc_hip_decode(self.h, int(seg), path.ctypes.data_as(_i32p), _p(mp)), "decode")
         return path, mp
 
     def posterior(self, seg, want_post=True, want_recomb=True):
-        """(post (L, n), recomb (L,)): full posterior and the DF line's recombination probability (aux.c:183-200), exact mode."""
+        """(post (L, n), recomb (L,)): full posterior and the DF line's recombination probability (aux.c:183-200); exact mode
+        bit for bit, fast mode within 1e-9 absolute (see decode)."""
         L = int(self.lens[seg])
         post = np.zeros((L, self.n)) if want_post else None
         rec = np.zeros(L) if want_recomb else None
@@ -335,12 +338,22 @@ class HipEStep:
         return post, rec
 
     def post_counts(self, seg, cnt1, cnt):
-        """cnt (n, n_cnt) += posterior-weighted counts of segment `seg` (cnt1: (l, n_cnt) int32), aux.c:202-219; in place."""
+        """cnt (n, n_cnt) += posterior-weighted counts of segment `seg` (cnt1: (l, n_cnt) int32), aux.c:202-219; in place.
+        Fast mode: from the fast tables (see decode), block partials added in a fixed order."""
         cnt1 = np.ascontiguousarray(cnt1, dtype=np.int32)
         assert cnt.dtype == np.float64 and cnt.flags.c_contiguous and cnt.shape == (self.n, cnt1.shape[1])
         self.lib.psmc_hip_post_counts.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int32, C.c_int32, _dp]
         self._chk(self.lib.psmc_hip_post_counts(self.h, int(seg), cnt1.ctypes.data_as(_i32p), cnt1.shape[0], cnt1.shape[1], _p(cnt)), "post_counts")
         return cnt
+
+    def scales(self, seg):
+        """s (L,): the reference's scaling factors hd->s[1..L] (khmm.c:170-186), the PR line of -s.  Exact mode: the table
+        itself; fast mode: from the X table, within 1e-11 relative."""
+        L = int(self.lens[seg])
+        s = np.zeros(L)
+        self.lib.psmc_hip_scales.argtypes = [C.c_void_p, C.c_int, _dp]
+        self._chk(self.lib.psmc_hip_scales(self.h, int(seg), _p(s)), "scales")
+        return s
 
     def timing(self):
         ms = np.zeros(7)

@@ -12,13 +12,26 @@ typedef struct {
 	int mode, device; char *devs;
 	const uint8_t **sym; int32_t *L;
 	psmc_hip_ctx *x_ctx; psmc_hip_group *x_grp; int n_fallbacks;
+	/* decoding (prepare_decode): the parameters of the last E-step, and whether the exact twin holds its tables */
+	int decoding, on_twin; double *pa, *pe, *pa0;
 } hip_be;
 
-/* the per-segment readers go to the context that holds the segment's tables */
+/* the per-segment readers go to the context that holds the segment's tables: the exact twin's after a fallback */
 static int route(hip_be *h, int seg, psmc_hip_ctx **c, int *local)
 {
+	if (h->on_twin) {
+		if (!h->x_grp) { *c = h->x_ctx; *local = seg; return 0; }
+		return psmc_hip_group_route(h->x_grp, seg, c, local);
+	}
 	if (!h->grp) { *c = h->ctx; *local = seg; return 0; }
 	return psmc_hip_group_route(h->grp, seg, c, local);
+}
+
+static const char *hb_error(void *self)
+{
+	hip_be *h = (hip_be *)self;
+	if (h->on_twin) return h->x_grp ? psmc_hip_group_last_error(h->x_grp) : psmc_hip_last_error(h->x_ctx);
+	return h->grp ? psmc_hip_group_last_error(h->grp) : psmc_hip_last_error(h->ctx);
 }
 
 static int hb_load(void *self, int n_seg, const uint8_t *const *sym, const int32_t *L)
@@ -37,12 +50,14 @@ static int hb_load(void *self, int n_seg, const uint8_t *const *sym, const int32
  * more slowly than anything the plan allows for) used to end the run.  The statistics are a well-defined quantity all the same:
  * this ONE E-step is repeated by the exact kernels -- a twin context / group in exact mode over the same segments, made on first
  * need -- with a note on stderr; the run goes on in fast mode.  (khmm.c:145-324 has no such failure mode.) */
-static int exact_once(hip_be *h, const double *a, const double *e, const double *a0, double *A, double *E, double *LL)
+static int exact_once(hip_be *h, const double *a, const double *e, const double *a0, double *A, double *E, double *LL, int quiet)
 {
 	int rc = 0;
-	fprintf(stderr, "psmc: fast E-step did not converge (%s); repeating this E-step with the exact kernels\n",
-	        h->grp ? psmc_hip_group_last_error(h->grp) : psmc_hip_last_error(h->ctx));
+	if (!quiet) /* (quiet: the caller has said why) */
+		fprintf(stderr, "psmc: fast E-step did not converge (%s); repeating this E-step with the exact kernels\n",
+		        h->grp ? psmc_hip_group_last_error(h->grp) : psmc_hip_last_error(h->ctx));
 	if (!h->x_ctx && !h->x_grp) {
+		h->on_twin = 0; /* (a twin that cannot be made holds no tables) */
 		if (h->grp) {
 			int list[64], n_list = 0;
 			char *dup = strdup(h->devs ? h->devs : "0");
@@ -57,7 +72,9 @@ static int exact_once(hip_be *h, const double *a, const double *e, const double 
 		if (rc) { fprintf(stderr, "psmc: cannot set up the exact E-step (%s)\n", psmc_hip_strerror(rc)); return rc; }
 	}
 	++h->n_fallbacks;
-	return h->x_grp ? psmc_hip_group_estep(h->x_grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->x_ctx, a, e, a0, A, E, 0, LL, h->chk);
+	rc = h->x_grp ? psmc_hip_group_estep(h->x_grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->x_ctx, a, e, a0, A, E, 0, LL, h->chk);
+	h->on_twin = rc == 0; /* the decoding that follows reads the twin's tables */
+	return rc;
 }
 
 static void tri_sums(int n, const double *A, double *sums)
@@ -74,8 +91,15 @@ static int hb_estep(void *self, const double *a, const double *e, const double *
                     double *chk)
 {
 	hip_be *h = (hip_be *)self;
+	if (h->decoding) { /* kept for the exact twin, should the fast tables turn out not to be decodable (hb_decoded) */
+		const size_t n = (size_t)h->n_states;
+		if (!h->pa) { h->pa = (double *)malloc(sizeof(double) * n * n); h->pe = (double *)malloc(sizeof(double) * 2 * n); h->pa0 = (double *)malloc(sizeof(double) * n); }
+		if (!h->pa || !h->pe || !h->pa0) return PSMC_HIP_ENOMEM;
+		memcpy(h->pa, a, sizeof(double) * n * n); memcpy(h->pe, e, sizeof(double) * 2 * n); memcpy(h->pa0, a0, sizeof(double) * n);
+	}
+	h->on_twin = 0;
 	int rc = h->grp ? psmc_hip_group_estep(h->grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->ctx, a, e, a0, A, E, 0, LL, h->chk);
-	if (rc == PSMC_HIP_ECONVERGE && h->mode == PSMC_HIP_MODE_FAST) rc = exact_once(h, a, e, a0, A, E, LL);
+	if (rc == PSMC_HIP_ECONVERGE && h->mode == PSMC_HIP_MODE_FAST) rc = exact_once(h, a, e, a0, A, E, LL, 0);
 	if (rc) return rc;
 	for (int i = 0; i < h->n_seg; ++i) { /* the diagnostic of khmm.c:239-240 */
 		if (h->chk[i] > 1.0 + 1e-6 || h->chk[i] < 1.0 - 1e-6) fprintf(stderr, "++ Underflow may have happened (%lg).\n", h->chk[i]);
@@ -86,13 +110,14 @@ static int hb_estep(void *self, const double *a, const double *e, const double *
 static int hb_estep_factored(void *self, const double *a, const double *e, const double *a0, double *sums, double *E, double *LL)
 {
 	hip_be *h = (hip_be *)self;
+	h->on_twin = 0;
 	int rc = h->grp ? psmc_hip_group_estep_factored(h->grp, a, e, a0, sums, E, LL) : psmc_hip_estep_factored(h->ctx, a, e, a0, sums, E, LL);
 	if (rc != PSMC_HIP_ENOTSUP && rc != PSMC_HIP_ECONVERGE) return rc;
 	/* a matrix without the two rank-1 triangles (e.g. -C): full counts, triangular sums on the host; tile boundaries that
 	 * did not converge: the exact kernels once (exact_once), sums of their A */
 	const int n = h->n_states;
 	double *A = (double *)calloc((size_t)n * n, sizeof(double));
-	if (rc == PSMC_HIP_ECONVERGE) rc = exact_once(h, a, e, a0, A, E, LL);
+	if (rc == PSMC_HIP_ECONVERGE) rc = exact_once(h, a, e, a0, A, E, LL, 0);
 	else rc = hb_estep(self, a, e, a0, A, E, LL, 0);
 	if (rc == 0) tri_sums(n, A, sums);
 	free(A);
@@ -103,29 +128,48 @@ static int hb_tables(void *self, int seg, double *f, double *b, double *s)
 	psmc_hip_ctx *c; int l; int rc = route((hip_be *)self, seg, &c, &l);
 	return rc ? rc : psmc_hip_get_tables(c, l, f, b, s);
 }
-static int hb_decode(void *self, int seg, int32_t *path, double *maxp)
+/* PSMC_HIP_DECODE=fast: the decoding E-step keeps the backward table (the fused and factored back halves never store it) */
+static int hb_prepare_decode(void *self)
 {
-	psmc_hip_ctx *c; int l; int rc = route((hip_be *)self, seg, &c, &l);
-	return rc ? rc : psmc_hip_decode(c, l, path, maxp);
+	hip_be *h = (hip_be *)self;
+	if (h->mode != PSMC_HIP_MODE_FAST) return 0;
+	h->decoding = 1;
+	int rc = h->grp ? psmc_hip_group_set_option(h->grp, "fuse", 0) : psmc_hip_set_option(h->ctx, "fuse", 0);
+	if (rc == 0) rc = h->grp ? psmc_hip_group_set_option(h->grp, "fuse128", 0) : psmc_hip_set_option(h->ctx, "fuse128", 0);
+	return rc;
 }
-static int hb_posterior(void *self, int seg, double *post, double *recomb)
+/* a decoding call on the fast tables that answers PSMC_HIP_ENOTSUP (a plan whose forward table the kernels cannot read, e.g.
+ * "merge" through PSMC_HIP_OPTIONS): the exact twin repeats the E-step with the same parameters and the call goes there */
+static int hb_decoded(hip_be *h, int rc)
 {
-	psmc_hip_ctx *c; int l; int rc = route((hip_be *)self, seg, &c, &l);
-	return rc ? rc : psmc_hip_posterior(c, l, post, recomb);
+	if (rc != PSMC_HIP_ENOTSUP || h->on_twin || !h->decoding || !h->pa) return rc;
+	const size_t n = (size_t)h->n_states;
+	double *A = (double *)malloc(sizeof(double) * n * n), *E = (double *)malloc(sizeof(double) * 2 * n), LL;
+	if (!A || !E) { free(A); free(E); return PSMC_HIP_ENOMEM; }
+	fprintf(stderr, "psmc: the fast tables cannot be decoded (%s); repeating the decoding E-step with the exact kernels\n", hb_error(h));
+	rc = exact_once(h, h->pa, h->pe, h->pa0, A, E, &LL, 1);
+	free(A); free(E);
+	return rc ? rc : -1000; /* -1000: call again, on the twin */
 }
-static int hb_post_counts(void *self, int seg, const int32_t *cnt1, int32_t l1, int32_t n_cnt, double *cnt)
-{
-	psmc_hip_ctx *c; int l; int rc = route((hip_be *)self, seg, &c, &l);
-	return rc ? rc : psmc_hip_post_counts(c, l, cnt1, l1, n_cnt, cnt);
-}
-static const char *hb_error(void *self) { hip_be *h = (hip_be *)self; return h->grp ? psmc_hip_group_last_error(h->grp) : psmc_hip_last_error(h->ctx); }
+#define HB_DECODE_CALL(call) \
+	hip_be *h = (hip_be *)self; \
+	for (;;) { \
+		psmc_hip_ctx *c; int l; int rc = route(h, seg, &c, &l); \
+		if (rc == 0) rc = (call); \
+		if ((rc = hb_decoded(h, rc)) != -1000) return rc; \
+	}
+static int hb_decode(void *self, int seg, int32_t *path, double *maxp) { HB_DECODE_CALL(psmc_hip_decode(c, l, path, maxp)) }
+static int hb_posterior(void *self, int seg, double *post, double *recomb) { HB_DECODE_CALL(psmc_hip_posterior(c, l, post, recomb)) }
+static int hb_post_counts(void *self, int seg, const int32_t *cnt1, int32_t l1, int32_t n_cnt, double *cnt) { HB_DECODE_CALL(psmc_hip_post_counts(c, l, cnt1, l1, n_cnt, cnt)) }
+static int hb_scales(void *self, int seg, double *s) { HB_DECODE_CALL(psmc_hip_scales(c, l, s)) }
+#undef HB_DECODE_CALL
 static void hb_destroy(void *self)
 {
 	hip_be *h = (hip_be *)self;
 	if (h->x_ctx) psmc_hip_destroy(h->x_ctx);
 	if (h->x_grp) psmc_hip_group_destroy(h->x_grp);
 	if (h->grp) psmc_hip_group_destroy(h->grp); else psmc_hip_destroy(h->ctx);
-	free(h->chk); free((void *)h->sym); free(h->L); free(h->devs); free(h);
+	free(h->chk); free((void *)h->sym); free(h->L); free(h->devs); free(h->pa); free(h->pe); free(h->pa0); free(h);
 }
 
 
@@ -162,7 +206,7 @@ int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_fa
 	if (rc) { if (h->grp) psmc_hip_group_destroy(h->grp); free(h->devs); free(h); return rc; }
 	be->self = h; be->load = hb_load; be->estep = hb_estep; be->tables = hb_tables; be->decode = hb_decode;
 	be->estep_factored = use_factored ? hb_estep_factored : 0; be->error = hb_error; be->destroy = hb_destroy;
-	be->posterior = hb_posterior; be->post_counts = hb_post_counts;
+	be->posterior = hb_posterior; be->post_counts = hb_post_counts; be->prepare_decode = hb_prepare_decode; be->scales = hb_scales;
 	return 0;
 }
 

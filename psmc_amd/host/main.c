@@ -2,6 +2,8 @@
  * the E-step bound to libpsmc_hip.so.  There is no CPU E-step in this binary:
  * without a visible AMD GPU it exits with an error.
  *   PSMC_HIP_MODE=exact (default: .psmc byte-identical to the reference) | fast
+ *   PSMC_HIP_DECODE=fast             with PSMC_HIP_MODE=fast and -d/-D/-c/-s: stay in fast mode and decode from the fast
+ *                                    tables (without it such a run is an exact run throughout)
  *   PSMC_HIP_DEVICE=<index>          one GPU
  *   PSMC_HIP_DEVICES=<i>,<j>,...     the segments of every E-step sharded over these GPUs (psmc_hip_group_*: LPT
  *                                    partition, one RCCL all-reduce of the statistics per EM iteration in fast mode,
@@ -45,8 +47,13 @@ int main(int argc, char *argv[])
 	const char *mode_s = getenv("PSMC_HIP_MODE"), *dev_s = getenv("PSMC_HIP_DEVICE");
 	int mode = (mode_s && strcmp(mode_s, "fast") == 0) ? PSMC_HIP_MODE_FAST : PSMC_HIP_MODE_EXACT;
 	if ((o.decode || o.print_prob || o.cnt_file) && mode == PSMC_HIP_MODE_FAST) {
-		fprintf(stderr, "psmc: decoding needs the exact forward/backward tables; using PSMC_HIP_MODE=exact\n");
-		mode = PSMC_HIP_MODE_EXACT;
+		const char *dec_s = getenv("PSMC_HIP_DECODE");
+		if (dec_s && strcmp(dec_s, "fast") == 0) /* opt-in: decode from the fast E-step's tables (include/psmc_hip.h: tolerances) */
+			fprintf(stderr, "psmc: PSMC_HIP_DECODE=fast: fast E-steps throughout; the decoding reads the fast forward/backward tables\n");
+		else {
+			fprintf(stderr, "psmc: decoding needs the exact forward/backward tables; using PSMC_HIP_MODE=exact\n");
+			mode = PSMC_HIP_MODE_EXACT;
+		}
 	}
 	{ /* the O(N) objective goes with the fast E-step unless asked otherwise */
 		const char *fm = getenv("PSMC_FAST_MSTEP");

@@ -102,6 +102,11 @@ typedef struct psmc_estep_backend {
 	int  (*posterior)(void *self, int seg, double *post, double *recomb);
 	/* optional (may be NULL): cnt[n*n_cnt] += posterior-weighted counts of one segment's cntcpg record (aux.c:202-219) */
 	int  (*post_counts)(void *self, int seg, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt);
+	/* optional (may be NULL): called once by the decoding before its E-step, so that the backend can make that E-step keep
+	 * what the decoding entry points read (the HIP backend in fast mode: the backward table) */
+	int  (*prepare_decode)(void *self);
+	/* optional (may be NULL): the scaling factors s[L] of one segment (the PR line of -s, aux.c:159-164) without the tables */
+	int  (*scales)(void *self, int seg, double *s);
 } psmc_estep_backend;
 
 /* ---- run state + driver (main.c, em.c, aux.c) */
