@@ -15,15 +15,20 @@ workload, mapped to (a, e, a0) by the host library), cycling through the 25 roun
 as in an EM run, the tile plan a context learned meets new parameters every
 iteration.  The headline `value` is measured that way; `steady_state` (the same
 parameters every step: the best case, what round 1 of this repo reported) is
-given beside it.
+given beside it in a --full run.
 
-    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong]
+A plain run does only what the headline needs: it sets up, warms up, times the
+steps, writes --dump-outputs and prints the line.  `--full` goes on after the
+timed steps with everything that takes runs of its own: per-kernel timings and
+the roofline, `steady_state`, the device probes and the extras below.
+
+    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --engine group --gpus N        # ONE process: the C library's own sharding (psmc_hip_group_*, what
                                                    # the psmc binary runs with PSMC_HIP_DEVICES=0,1,..): LPT in C, one host
                                                    # thread per device, RCCL all-reduce via group.hip
 
-Extras on the same line (N=1): `shard_sweep` (the E-step on rank 0's LPT share of the genome at 1/2/4/8 GPUs and on the
+Extras on the same line (--full, N=1): `shard_sweep` (the E-step on rank 0's LPT share of the genome at 1/2/4/8 GPUs and on the
 500 k-bin input of config 2, with the strong-scaling curve those times predict), `group_engine` (the product's own
 multi-GPU path, see above; with N>1 it is measured beside the torch.distributed number), `boot` (config 4 through the
 psmc_boot binary, 16 replicates), `factored_stats`, `exact_mode`, `n128` (config 5).
@@ -32,8 +37,8 @@ Scaling.  Segments are independent given the parameters (em.c:36-55); the one
 exchange per step is the RCCL all-reduce of n*n+2n+1 doubles that replaces
 hmm_add_expect (khmm.c:346).  Default "weak": every rank holds its own
 genome-sized shard.  `--scaling strong` is config 3 proper: ONE 30 M-bin genome,
-its segments spread over the ranks by longest-processing-time-first; with N>1 the
-default run also reports that as `strong_scaling` beside the headline.
+its segments spread over the ranks by longest-processing-time-first; with N>1 a
+--full run also reports that as `strong_scaling` beside the headline.
 """
 import argparse
 import json
@@ -224,9 +229,32 @@ def factored_roofline(bins, kern, dt_step):
     return r
 
 
+def headline_line(args, world, bins, total_bins, lens, n_local_segs, diag, value, ms_per_step, traj_src, n_moving, stats_numel):
+    """The JSON line of a plain run: the headline and the workload it was measured on, nothing that needs a run of its own."""
+    return {
+        "metric": "genome bins/sec through forward-backward (n=64)",
+        "value": value, "unit": "bins/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "configs[2]: whole-genome .psmcfa-like batch, %d bins x %d states in %d segments "
+                               "%s, -p %s, one E-step (EM iteration) per step, parameters of a different EM round every step"
+                               % (int(lens.sum()), N_STATES, len(lens), "per GPU" if args.scaling == "weak" else "sharded over the GPUs", PATTERN),
+                   "mode": args.mode, "bins_per_gpu": bins, "bins_total": total_bins, "n_states": N_STATES, "segments": n_local_segs,
+                   "longest_segment": int(lens.max()),
+                   "parameters": ("fixed (n64_curve)" if args.fixed_params else "cycle of %d EM rounds: %s" % (n_moving, traj_src)),
+                   "sharding": ("segments/GPU + 1 RCCL all-reduce(%d f64)/step" % stats_numel) if world > 1 else "single GPU",
+                   **({"tiles": diag.get("n_chunks"), "speculative_overlap_bins": diag.get("warmup"),
+                       "structured_sweeps": diag.get("structured"), "tile_bins": diag.get("tile_len"),
+                       "sweep_items": [diag.get("items_fwd"), diag.get("items_bwd")],
+                       "repair_rounds": [diag.get("fwd_rounds"), diag.get("bwd_rounds")],
+                       "repaired_tiles": [diag.get("fwd_tiles"), diag.get("bwd_tiles")],
+                       "boundary_err": max(diag.get("warm_err_fwd", 0), diag.get("warm_err_bwd", 0))} if diag else {})},
+    }
+
+
 def make_line(args, fast, world, bins, total_bins, lens, n_local_segs, kern, diag, value, ms_per_step, traj_src, n_moving, stats_numel):
-    """The JSON line of the contract from what was measured (pure function: tests/test_bench_line.py feeds it fake
-    measurements for every plan the library can report)."""
+    """The JSON line of a --full run from what was measured: the headline line plus the roofline (pure function:
+    tests/test_bench_line.py feeds it fake measurements for every plan the library can report)."""
     # dominant KERNEL (one launch): the speculative forward / backward sweep or the expect kernel
     if fast:
         if diag.get("back_half") == 1:  # forward sweep, then backward sweep + counts in one kernel (estep_fused.hip)
@@ -255,24 +283,8 @@ def make_line(args, fast, world, bins, total_bins, lens, n_local_segs, kern, dia
     tfl = bins * flop_b / (fused_ms * 1e-3) / 1e12 if fused_ms > 0 else 0.0
     # HBM bytes per launch from the rocprofv3 PMC pass of this same command (profiles/, scripts/lease.sh prof), guarded by the sources' hash
     traffic, traffic_note = replayed_traffic(os.path.join(ROOT, "profiles", "pmc_traffic.json"), bins, dom)
-    out = {
-        "metric": "genome bins/sec through forward-backward (n=64)",
-        "value": value, "unit": "bins/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "configs[2]: whole-genome .psmcfa-like batch, %d bins x %d states in %d segments "
-                               "%s, -p %s, one E-step (EM iteration) per step, parameters of a different EM round every step"
-                               % (int(lens.sum()), N_STATES, len(lens), "per GPU" if args.scaling == "weak" else "sharded over the GPUs", PATTERN),
-                   "mode": args.mode, "bins_per_gpu": bins, "bins_total": total_bins, "n_states": N_STATES, "segments": n_local_segs,
-                   "longest_segment": int(lens.max()),
-                   "parameters": ("fixed (n64_curve)" if args.fixed_params else "cycle of %d EM rounds: %s" % (n_moving, traj_src)),
-                   "sharding": ("segments/GPU + 1 RCCL all-reduce(%d f64)/step" % stats_numel) if world > 1 else "single GPU",
-                   **({"tiles": diag.get("n_chunks"), "speculative_overlap_bins": diag.get("warmup"),
-                       "structured_sweeps": diag.get("structured"), "tile_bins": diag.get("tile_len"),
-                       "sweep_items": [diag.get("items_fwd"), diag.get("items_bwd")],
-                       "repair_rounds": [diag.get("fwd_rounds"), diag.get("bwd_rounds")],
-                       "repaired_tiles": [diag.get("fwd_tiles"), diag.get("bwd_tiles")],
-                       "boundary_err": max(diag.get("warm_err_fwd", 0), diag.get("warm_err_bwd", 0))} if diag else {})},
+    out = headline_line(args, world, bins, total_bins, lens, n_local_segs, diag, value, ms_per_step, traj_src, n_moving, stats_numel)
+    out.update({
         "roofline": {**({"bound": "mfma", "kernel": dom, "launches_per_step": diag.get("fused_launches", 1),
                          "achieved": tfl, "peak": F64_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": tfl / F64_PEAK_TFLOPS, "alg_flop_per_bin": flop_b,
@@ -307,7 +319,7 @@ def make_line(args, fast, world, bins, total_bins, lens, n_local_segs, kern, dia
                                    "forward and backward sweep kernels run side by side and share the HBM; the counts "
                                    "kernel (K=bins GEMM, 2*n^2 flop/bin on v_mfma_f64_16x16x4) reaches %.1f of 78.6 TFLOP/s") %
                                   (bins * 2 * N_STATES * N_STATES / (kern["expect"] * 1e-3) / 1e12 if kern.get("expect", 0) > 0 else 0.0)},
-    }
+    })
     return out
 
 
@@ -504,6 +516,9 @@ def main():
     ap.add_argument("--opt", action="append", default=[], help="library option key=value (chunk, warmup, ...)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write what the timed path computed in its last timed step (A, E, LL, ...) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: per-kernel timings and the roofline, steady state, "
+                         "device probes, strong scaling and the extras that --cpu-sample and the --*-extra options select")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -634,7 +649,7 @@ def main():
                "roofline": {"bound": "hbm", "kernel": "whole E-step (per-kernel rooflines: --engine dist)", "achieved": gbs, "peak": HBM_PEAK_GBS * len(set(devices)), "unit": "GB/s",
                             "frac": gbs / (HBM_PEAK_GBS * len(set(devices))), "alg_bytes_per_bin": BYTES_PER_BIN, "traffic": None},
                "first_call_ms": res["first_call_ms"]}
-        if len(devices) == 1 and args.cpu_sample > 0:
+        if args.full and len(devices) == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(a, e, a0, segs, args.cpu_sample)
         print(json.dumps(out), flush=True)
         return
@@ -657,6 +672,19 @@ def main():
         else:
             dump_outputs(args.dump_outputs, {k: sh.last[k] for k in ("A", "E", "A0", "LL")})
     value = total_bins / (dt / args.steps)
+    if not args.full:   # a plain run ends with the headline: everything below runs the GPU again
+        if rank == 0:
+            out = headline_line(args, world, sh.bins, total_bins, lens, len(segs), es.fast_diag() if mode == hip.MODE_FAST else {},
+                                value, ms_per_step, traj_src, len(moving), sh.stats.numel())
+            if comm is not None:
+                out["config"]["comm"] = comm
+            if first_ms is not None:
+                out["first_call_ms"] = first_ms
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # per-kernel durations (HIP events recorded by the library on the streams the kernels ran on); measured on separate
     # steps of the same cycle so that the event reads do not perturb the timed region
     kern = {}

@@ -2,7 +2,7 @@
 # One parametrised GPU-lease script (replaces the single-use gpu_r02_*.sh / r03/*.sh of the build sessions).  Run it on the GPU
 # box:  gpurun --timeout N -- 'bash scripts/lease.sh <task> [args]'.  Everything is written under gpurun_out/.
 #   suite [pytest args]           the GPU test suite (PSMC_HIP_POISON=vary in the environment: every device allocation poisoned)
-#   bench [bench.py args]         the driver's bench command (default: --steps 20 --warmup 5) + a digest of the line
+#   bench [bench.py args]         bench.py --full with these arguments (default: --steps 20 --warmup 5) + a digest of the line
 #   sweep CFG [CFG ...]           scripts/shard_sweep.py, one --cfg per argument ("" = defaults); env SHARES (8,4,2,1), CHR (500000),
 #                                 REPEAT (1: A B A B ... when > 1), FACTORED (0), STATES (64; 128 = config 5), WARMUP (10), STEPS (12)
 #   timeline SHARES CHR           rocprofv3 --kernel-trace of a few E-steps, kernel timeline of the last one (every kernel); env CFG (options), FACTORED, TAG (output suffix)
@@ -54,13 +54,14 @@ do_suite() {
 }
 do_bench() {
   [ $# -eq 0 ] && set -- --steps 20 --warmup 5
+  set -- --full "$@"   # the digest reads the roofline and the extras
   s=$(date +%s); timeout 900 python bench.py "$@" > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "bench rc=$? in $(( $(date +%s) - s )) s"; tail -2 gpurun_out/bench.err | cut -c1-300
   digest gpurun_out/bench.json
 }
 do_prof() {
   rm -rf $R/gpurun_out/prof/bench* $R/gpurun_out/prof/n128* $R/gpurun_out/pmc/*
   cd /tmp
-  BARGS="--cpu-sample 0 --exact-extra 0 --n128-extra 0 --boot-extra 0 --shard-extra 0 --group-extra 0"
+  BARGS="--full --cpu-sample 0 --exact-extra 0 --n128-extra 0 --boot-extra 0 --shard-extra 0 --group-extra 0"
   timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof -o bench -- python $R/bench.py --steps 5 --warmup 1 $BARGS > $R/gpurun_out/prof/bench.json 2> $R/gpurun_out/prof/bench.err; echo "stats bench rc=$?"
   timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof -o n128 -- python $R/scripts/n128_run.py 6 > $R/gpurun_out/prof/n128.json 2> $R/gpurun_out/prof/n128.err; echo "stats n128 rc=$?"
   for C in FETCH_SIZE WRITE_SIZE; do

@@ -10,7 +10,7 @@ bins = int(sys.argv[2]) if len(sys.argv) > 2 else 30000003
 # gpurun_out/pmc/n128_*_counter_collection.csv and writes profiles/<tag>_n128_* and profiles/pmc_traffic_n128.json
 NAME = os.environ.get("PROF_NAME", "bench")
 SUFFIX = "" if NAME == "bench" else "_" + NAME
-CMD = os.environ.get("PROF_CMD", "python bench.py --steps 5 --warmup 1 --cpu-sample 0 --exact-extra 0")
+CMD = os.environ.get("PROF_CMD", "python bench.py --steps 5 --warmup 1 --full --cpu-sample 0 --exact-extra 0")
 STATES = int(os.environ.get("PROF_STATES", "64"))
 
 def short(nm):

@@ -76,3 +76,19 @@ def test_bench_rejects_fewer_than_one_timed_step():
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "--steps" in r.stderr, r.stderr
+
+
+def test_plain_line_is_the_headline_alone():
+    """A plain run prints the headline and its workload: the same fields a --full run gives them, and nothing measured by
+    runs of their own (no roofline, which needs per-kernel timings)."""
+    import bench
+    args = argparse.Namespace(steps=20, warmup=5, scaling="weak", mode="fast", fixed_params=0)
+    lens = np.array([2490000, 2429561] + [285000] * 88)
+    bins = int(lens.sum())
+    plain = bench.headline_line(args, 1, bins, bins, lens, 90, dict(DIAG), bins / 14.65e-3, 14.65, "test trajectory", 25, 4225)
+    full = bench.make_line(args, True, 1, bins, bins, lens, 90, dict(KERN), dict(DIAG), bins / 14.65e-3, 14.65, "test trajectory", 25, 4225)
+    json.dumps(plain)
+    assert "roofline" not in plain and set(full) - set(plain) == {"roofline"}
+    for k in plain:
+        assert plain[k] == full[k], k
+    assert plain["ms_per_step"] == 14.65 and plain["unit"] == "bins/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64"

@@ -182,12 +182,12 @@ def test_shard_sized_inputs_one_round_plan(hip, golden, genome, workload):
 def test_bench_two_ranks_on_one_device():
     """The driver's N > 1 command line (torch.distributed.run, one rank per GPU) on a box with one GPU: BENCH_SINGLE_GPU_TEST=1 puts
     both ranks on device 0 (gloo instead of RCCL).  Checks the contract line, the strong-scaling extra and the child process that
-    runs the C library's own multi-device engine (psmc_hip_group_*) beside it."""
+    runs the C library's own multi-device engine (psmc_hip_group_*) beside it: a --full run."""
     import json
     import sys
     env = dict(os.environ, BENCH_SINGLE_GPU_TEST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29631",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--bins", "3000000", "--segments", "9"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--bins", "3000000", "--segments", "9", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -208,17 +208,18 @@ def test_bench_two_ranks_on_one_device():
         assert g["selfcheck"]["shards"] == 2 and g["selfcheck"]["path"] == "host_sum", g   # two shards on one device: no communicator
 
 
-def test_bench_dump_outputs_are_the_last_timed_step(hip, golden, tmp_path):
-    """bench.py --dump-outputs writes A, E and LL of the LAST timed step as float64 .npy files: what an exact E-step gives at that
-    step's parameters.  The timed steps cycle through the EM trajectory, so step warmup + steps - 1 runs set (warmup + steps - 1) % 25;
-    the steps bench.py runs after the timed ones (kernel timings, steady state) use other sets."""
+def bench_dump(hip, golden, tmp_path, full):
+    """bench.py --dump-outputs on a 3 M-bin genome -> its JSON line.  The dumped arrays are checked against an exact E-step at
+    the parameters of the last timed step: the timed steps cycle through the EM trajectory, so step warmup + steps - 1 runs
+    set (warmup + steps - 1) % 25."""
     import json
     import sys
     from psmc_amd import sim
     steps, warmup, bins, n_seg = 4, 2, 3_000_000, 9
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--bins", str(bins), "--segments", str(n_seg),
-           "--cpu-sample", "0", "--exact-extra", "0", "--n128-extra", "0", "--shard-extra", "0", "--group-extra", "0", "--boot-extra", "0",
            "--dump-outputs", str(tmp_path)]
+    if full:
+        cmd += ["--full", "--cpu-sample", "0", "--exact-extra", "0", "--n128-extra", "0", "--shard-extra", "0", "--group-extra", "0", "--boot-extra", "0"]
     r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads(r.stdout.strip().splitlines()[-1])
@@ -234,3 +235,18 @@ def test_bench_dump_outputs_are_the_last_timed_step(hip, golden, tmp_path):
     ex.close()
     assert relmax(out["A"], rx["A"]) < TOL_STATS and relmax(out["E"], rx["E"]) < TOL_STATS
     assert abs(float(out["LL"]) - rx["LL"]) <= TOL_LL * abs(rx["LL"])
+    return j
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(hip, golden, tmp_path):
+    """bench.py --dump-outputs writes A, E and LL of the LAST timed step as float64 .npy files: what an exact E-step gives at that
+    step's parameters.  A plain run stops there: its line carries nothing that needs steps of its own."""
+    j = bench_dump(hip, golden, tmp_path, full=False)
+    assert "roofline" not in j and "steady_state" not in j and "first_call_ms" in j
+
+
+def test_bench_full_run_dumps_the_last_timed_step(hip, golden, tmp_path):
+    """In a --full run the steps after the timed ones (kernel timings, steady state) use other parameter sets: the dump is
+    still the last timed step."""
+    j = bench_dump(hip, golden, tmp_path, full=True)
+    assert "roofline" in j and "steady_state" in j
