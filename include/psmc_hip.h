@@ -15,7 +15,9 @@
  * fast mode runs the structured sweeps for matrices of the PSMC form and psmc_hip_estep falls back to the exact kernels for
  * any other matrix; 129..1024 (`psmc -p "100*2"`): the wide exact kernels of estep_wide.hip whatever the mode -- psmc_hip_estep,
  * _estep_segments, _estep_batch, the table readers and the decoding entry points; the device-resident and factored fast entry
- * points return PSMC_HIP_ENOTSUP there);
+ * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 a fast-mode context of 129..256 states runs
+ * psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip (PSMC-form matrices; full
+ * counts, batch, tables and decoding stay exact);
  * row-major FP64; a[k*n+l]=P(k->l) (khmm.h:34); e[b*n+k], b=0 hom / 1 het
  * (khmm.h:34; the missing-data row e[2][*]=1 of khmm.c:21 is implied);
  * a0[k] (khmm.h:36); observations are bytes 0/1/2 exactly as psmc_read_seq
@@ -31,13 +33,15 @@ extern "C" {
 #define PSMC_HIP_MODE_EXACT 0 /* bit-identical to khmm.c (ordered sums, no FMA) */
 #define PSMC_HIP_MODE_FAST  1 /* tiled speculative sweeps, FMA/MFMA, tree reductions; stats within 1e-10 */
 
-#define PSMC_HIP_MAX_STATES 1024 /* exact mode; the fast kernels cover up to 128 states (beyond: a fast-mode context runs the exact ones) */
+#define PSMC_HIP_MAX_STATES 1024 /* exact mode; the fast kernels cover up to 128 states (beyond: a fast-mode context runs the exact ones),
+                                    and the factored statistics up to 256 with the option "wide_fast" */
 
 #define PSMC_HIP_OK        0
 #define PSMC_HIP_EINVAL   -1 /* bad argument (NULL, n out of range, empty segment ...) */
 #define PSMC_HIP_ENOMEM   -2 /* host or device allocation failed */
 #define PSMC_HIP_EDEVICE  -3 /* HIP runtime error; see psmc_hip_last_error() */
-#define PSMC_HIP_ENOTSUP  -4 /* not supported in this build (n > 1024; the device-resident / factored fast entry points with n > 128, or with n > 64 and a matrix without the PSMC form) */
+#define PSMC_HIP_ENOTSUP  -4 /* not supported in this build (n > 1024; the device-resident / factored fast entry points with n > 128 -- the
+                                factored ones with n > 256 when "wide_fast" is set -- or with n > 64 and a matrix without the PSMC form) */
 #define PSMC_HIP_ESTATE   -5 /* call order violated (no segments loaded ...) */
 #define PSMC_HIP_ECONVERGE -6 /* fast mode: tile boundaries did not converge within max_rounds */
 
@@ -68,6 +72,15 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *  "warmup"        3072     bins a tile starts outside itself (from the stationary vector) in each direction
  *  "warm_tol"      1e-12    agreement demanded between the vector a tile built on and what its neighbour computed
  *  "max_rounds"    4096     verify / repair rounds before PSMC_HIP_ECONVERGE
+ *  "wide_fast"     0        1: a fast-mode context of 129..256 states runs psmc_hip_estep_factored[_device] on the fast kernels of
+ *                           estep_wide_fast.hip (one tile per wave, 64 lanes x 3 or 4 states; PSMC-form matrices, else ENOTSUP; more
+ *                           than 256 states: ENOTSUP).  It reads "chunk" (0 = about 4096 tiles, at least 256 bins), "warmup" (16384
+ *                           bins unless set: shorter warm-ups leave tiles whose repair walks a whole segment), "warm_tol",
+ *                           "max_rounds" and "learn" (1: a repair walks on through the failing tiles after it in the same round;
+ *                           0: one tile per wave and round); with "structured" = 0 it answers ENOTSUP, as the factored statistics
+ *                           do up to 128 states.  It keeps an X table of its own: 8 x 192 or 8 x 256 bytes per bin
+ *                           (46 / 61 GB at 30 M bins), beside the exact tables.  psmc_hip_estep, the batch, the table readers and the
+ *                           decoding entry points stay on the exact kernels, bit for bit.  Exact mode and <= 128 states: no effect
  *  "merge"         0        1: a forward FIX pass between the forward sweep and the back half (64 states, fused back half): every tile's start
  *                           vector is checked there, and a tile that fails is rewritten from the true vector until its trajectory has the
  *                           direction of the stored one again (the factor between the two parts is kept for the counts and the likelihood) --
@@ -254,7 +267,8 @@ int psmc_hip_fast_diag(psmc_hip_ctx *ctx, double *warm_err_fwd, double *warm_err
 /* How much repair the speculation needed: verify/repair rounds and the total
  * number of tile re-runs, forward and backward, out[0..3]; out[4] = tiles
  * the forward fix pass rewrote in part ("merge"),
- * out[5] = 1 when a second pass of the counts had to run. */
+ * out[5] = 1 when a second pass of the counts had to run, 2 when the E-step was one of the wide path ("wide_fast", 129..256
+ * states: out[0..3] are then its verify / repair rounds and the head tiles the repairs started from, out[4] = 0). */
 int psmc_hip_fast_repairs(psmc_hip_ctx *ctx, int out[6]);
 /* Diagnostic: the plan the NEXT fast E-step of this context will run with: out = {tiles, tile length in bins, mean forward
  * warm-up of the speculating tiles in bins, mean backward warm-up, longest forward, longest backward, tiles glued to their
@@ -265,13 +279,14 @@ int psmc_hip_fast_plan(psmc_hip_ctx *ctx, double out[8]);
  * N x N counts.  The EM objective needs of A only  SL_k = sum_{l<k} A[k][l],  SU_k = sum_{l>k} A[k][l],
  * DG_k = A[k][k],  CL_l = sum_{k>l} A[k][l],  CU_l = sum_{k<l} A[k][l]  (psmc_amd/host/mstep.c); they come out
  * of the backward sweep in O(N) per bin.  sums = SL | SU | DG | CL | CU (5n), E as in psmc_hip_estep (2n).
- * PSMC_HIP_ENOTSUP when the matrix does not have the form.  Replaces em.c:33-55 + the reads of hmm_Q. */
+ * PSMC_HIP_ENOTSUP when the matrix does not have the form.  129..256 states: with the option "wide_fast" only (see there).
+ * Replaces em.c:33-55 + the reads of hmm_Q. */
 int psmc_hip_estep_factored(psmc_hip_ctx *ctx, const double *a, const double *e, const double *a0, double *sums,
                             double *E, double *LL);
 
 /* Diagnostic: out = {structured sweeps used (0/1), tile length in bins, forward sweep items,
  * backward sweep items, back half (0: bt table + counts kernel, 1: backward sweep fused with the counts, 2: factored
- * statistics), checkpointed X (0/1), launches of the fused back half (2 with the two-phase plan), phase 1 as one grid
+ * statistics, 3: the factored statistics of the wide path, "wide_fast": items = tiles), checkpointed X (0/1), launches of the fused back half (2 with the two-phase plan), phase 1 as one grid
  * ("merge1": 0/1)} of the last fast-mode E-step (items = runs of glued tiles).  The O(N) structured
  * sweeps are chosen automatically when a[][] has the two rank-1
  * triangles psmc_update_hmm builds (core.c:112-122); otherwise the dense sweeps run. */

@@ -162,6 +162,7 @@ extern "C" void psmc_hip_destroy(psmc_hip_ctx *c)
 		return;
 	}
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	free_wide_fast(c);
 	if (c->stream2) (void)hipStreamSynchronize(c->stream2);
 	if (c->stream3) (void)hipStreamSynchronize(c->stream3);
 	if (c->stream4) (void)hipStreamSynchronize(c->stream4);
@@ -197,7 +198,7 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	if (k == "batch_first") { if (v < 0 || v > 1e6) return PSMC_HIP_EINVAL; c->batch_first = (int)v; return PSMC_HIP_OK; } // (names a replicate context: they all stay)
 	destroy_kids(c); // replicate contexts of a batch copied the options when they were made: start them afresh
 	if (k == "chunk") { if (v < 0) return PSMC_HIP_EINVAL; c->chunk = (int)v; c->plan_dirty = true; }
-	else if (k == "warmup") { if (v < 0) return PSMC_HIP_EINVAL; c->warmup = (int)v; c->plan_dirty = true; }
+	else if (k == "warmup") { if (v < 0) return PSMC_HIP_EINVAL; c->warmup = (int)v; c->warmup_set = true; c->plan_dirty = true; }
 	else if (k == "max_rounds") c->max_rounds = (int)v;
 	else if (k == "structured") { c->struct_opt = v != 0 ? 1 : 0; }
 	else if (k == "learn") { c->learn = v != 0 ? 1 : 0; }
@@ -226,6 +227,7 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "batch_bins") { if (v < 0) return PSMC_HIP_EINVAL; c->batch_bins = (int64_t)v; }
 	else if (k == "overlap") c->overlap = v != 0 ? 1 : 0;
 	else if (k == "warm_tol") c->warm_tol = v;
+	else if (k == "wide_fast") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_fast = (int)v; }
 	else if (k == "rep_impl") c->rep_impl = v < 0 ? -1 : (v != 0 ? 1 : 0);
 	else return PSMC_HIP_EINVAL;
 	return PSMC_HIP_OK;
@@ -315,7 +317,7 @@ extern "C" int psmc_hip_select(psmc_hip_ctx *c, int n_sel, const int32_t *idx)
 // Does a[][] have the PSMC form  a[k][l] = P_k qa_l (l<k),  R_k c_l (l>k)  (core.c:112-122)?
 // Numerical factorisation with qa_0 = c_{n-1} = 1, then a check of EVERY off-diagonal entry to
 // 64 ulp and of dd = diag - P.qa - R.c >= 0.  sp = P | R | qa | c | dd (64 each, zero padded).
-static bool factor_structure(int n, int S, const double *a /* stride S */, double *sp /* 5 * S */)
+bool factor_structure(int n, int S, const double *a /* stride S */, double *sp /* 5 * S */)
 {
 	double *P = sp, *R = sp + S, *qa = sp + 2 * S, *cc = sp + 3 * S, *dd = sp + 4 * S;
 	memset(sp, 0, 5 * (size_t)S * sizeof(double));

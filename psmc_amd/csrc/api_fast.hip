@@ -691,8 +691,8 @@ extern "C" int psmc_hip_fast_diag(psmc_hip_ctx *c, double *wf, double *wb, int *
 	memcpy(&c->warm_err[0], &w[0], 8); memcpy(&c->warm_err[1], &w[1], 8);
 	if (wf) *wf = c->warm_err[0];
 	if (wb) *wb = c->warm_err[1];
-	if (n_chunks) *n_chunks = (int)c->chunks.size();
-	if (warmup_used) *warmup_used = c->warmup;
+	if (n_chunks) *n_chunks = (int)(c->wf_ran ? c->wf_chunks.size() : c->chunks.size());
+	if (warmup_used) *warmup_used = c->wf_ran ? c->wf_W : c->warmup;
 	return PSMC_HIP_OK;
 }
 
@@ -711,6 +711,7 @@ extern "C" int psmc_hip_estep_factored(psmc_hip_ctx *c, const double *a, const d
 	if (!c || !a || !e || !a0) return fail(c, PSMC_HIP_EINVAL, "estep_factored: bad argument");
 	if (c->mode != PSMC_HIP_MODE_FAST) return fail(c, PSMC_HIP_ENOTSUP, "estep_factored: fast mode only");
 	HIPCHK(c, hipSetDevice(c->device));
+	if (c->ns > 128 && c->wide_fast) return estep_factored_wide(c, a, e, a0, sums, E, LL); // 129..256 states (api_wide_fast.hip)
 	int rc;
 	if ((rc = ensure_fast_buffers(c))) return rc; // d_stats must exist before the first enqueue (the plan follows stage_params)
 	c->want_factored = true;
@@ -736,6 +737,7 @@ extern "C" int psmc_hip_estep_factored_device(psmc_hip_ctx *c, const double *a, 
 	if (c->mode != PSMC_HIP_MODE_FAST) return fail(c, PSMC_HIP_ENOTSUP, "estep_factored_device: fast mode only");
 	HIPCHK(c, hipSetDevice(c->device));
 	c->timing_valid = false;
+	if (c->ns > 128 && c->wide_fast) return estep_wide_fast(c, a, e, a0, (double *)d_stats, (hipStream_t)stream);
 	c->want_factored = true;
 	const int rc = enqueue_fast(c, a, e, a0, (double *)d_stats, (hipStream_t)stream);
 	c->want_factored = false;
@@ -745,6 +747,11 @@ extern "C" int psmc_hip_estep_factored_device(psmc_hip_ctx *c, const double *a, 
 extern "C" int psmc_hip_fast_info(psmc_hip_ctx *c, int out[8])
 {
 	if (!c || !out) return PSMC_HIP_EINVAL;
+	if (c->wf_ran) { // the wide path (129..256 states): one tile per wave, no items
+		const int nc = (int)c->wf_chunks.size();
+		out[0] = 1; out[1] = c->wf_T; out[2] = nc; out[3] = nc; out[4] = 3; out[5] = 0; out[6] = 1; out[7] = 0;
+		return PSMC_HIP_OK;
+	}
 	out[0] = c->use_struct ? 1 : 0; out[1] = c->chunk_used; out[2] = c->use_struct ? c->n_items_f : (int)c->chunks.size();
 	out[3] = c->use_struct ? c->n_items_b : (int)c->chunks.size();
 	out[4] = c->last_fused; out[5] = c->last_ckpt; out[6] = c->timing_two_launches ? 2 : 1; out[7] = c->merge1_used;

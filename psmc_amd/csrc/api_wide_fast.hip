@@ -1,0 +1,192 @@
+// api_wide_fast.hip -- fast mode beyond 128 states: the factored statistics of psmc_hip_estep_factored[_device] at 129..256
+// states with the option "wide_fast" = 1 (kernels: estep_wide_fast.hip).  Everything else a context of that size does --
+// psmc_hip_estep, the batch, the table readers, decoding -- stays on the wide exact kernels, and this path does not touch their
+// tables: it keeps its own X table (8 S bytes per bin) and scale factors.
+//
+// One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
+// of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,
+// which launches one wave per HEAD of a failing run (a failing tile whose predecessor in the sweep direction passed).  With "learn"
+// (default) the wave walks on through the tiles after its head for as long as their start vectors disagree with what it computes
+// -- the run is glued for this E-step and repaired in one round; with "learn" = 0 every round rewrites the heads only.  The plan
+// (tiles, warm-ups) is the same at every E-step, so the result depends only on the inputs of the call: bit-reproducible.
+#include "psmc_hip_ctx.h"
+#include "wide_fast.h"
+
+static constexpr int WF_PAR = 8; // e0 | e1 | a0 | P | R | qa | c | dd (wide_fast.h)
+static constexpr int WF_NACC = 7; // SL SU DG CL CU E0 E1 per tile
+
+void free_wide_fast(psmc_hip_ctx *c)
+{
+	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
+	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list};
+	for (void *q : p) if (q) (void)hipFree(q);
+	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
+	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
+	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
+	c->wf_cap = 0; c->wf_bins = 0;
+}
+
+// Tiles of T bins (option "chunk", else about WF_TILES tiles: four waves per SIMD of an MI355X -- the forward sweep fits four at
+// up to 110 VGPRs; the accumulate sweep, at 154 / 206 VGPRs, fits three (192 states) or two (256) and runs the tiles in two generations), every one speculating "warmup" bins in both directions -- by default WF_WARMUP, not the 3072 of
+// the paths up to 128 states.  On the 30 M-bin benchmark genome at 200 and 256 states a warm-up of 3072 or 6144 bins leaves a few
+// tiles whose start vector is wrong outright (mismatch ~1), and the repair that follows walks on for a whole segment: 2.4-2.9 s
+// per E-step; 8192: 0.2-0.5 s; 12288 or 16384: 0.16 s (profiles/wide_fast_timing.txt).  The extra warm-up costs a few ms.
+static int plan_wide(psmc_hip_ctx *c)
+{
+	constexpr int64_t WF_TILES = 4096;
+	constexpr int WF_WARMUP = 16384;
+	int64_t bins = 0;
+	for (int32_t s : c->work) bins += c->L[s];
+	int T = c->chunk;
+	if (T <= 0) T = (int)std::max<int64_t>(256, ((bins + WF_TILES - 1) / WF_TILES + 63) & ~(int64_t)63);
+	const int W = c->warmup_set ? c->warmup : WF_WARMUP;
+	c->wf_chunks.clear();
+	for (size_t w = 0; w < c->work.size(); ++w) {
+		const int32_t s = c->work[w];
+		for (int32_t lo = 1; lo <= c->L[s]; lo += T) {
+			Chunk ch;
+			ch.off = c->off[s]; ch.L = c->L[s]; ch.lo = lo; ch.hi = std::min(c->L[s], lo + T - 1); ch.mult = c->mult[w];
+			ch.flags = 0; ch.wf = ch.wb = W;
+			if (ch.lo - W <= 1) ch.flags |= CHUNK_ANCHOR_F;
+			if ((int64_t)ch.hi + W + 1 >= ch.L) ch.flags |= CHUNK_ANCHOR_B;
+			if (ch.hi == ch.L) ch.flags |= CHUNK_LAST;
+			c->wf_chunks.push_back(ch);
+		}
+	}
+	const int nc = (int)c->wf_chunks.size(), S = c->ns;
+	int rc;
+	if (nc > c->wf_cap) {
+		if ((rc = dev_alloc(c, &c->d_wf_chunks, (size_t)nc))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wf_entry, (size_t)nc * S))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wf_bentry, (size_t)nc * S))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wf_bexit, (size_t)(nc + 1) * S))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wf_part, (size_t)nc * WF_NACC * S))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wf_ll, (size_t)nc))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wf_dirty, (size_t)nc))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wf_list, (size_t)nc))) return rc;
+		c->wf_cap = nc;
+	}
+	HIPCHK(c, hipMemcpy(c->d_wf_chunks, c->wf_chunks.data(), sizeof(Chunk) * nc, hipMemcpyHostToDevice));
+	c->wf_T = T; c->wf_W = W;
+	c->plan_dirty = false;
+	return 0;
+}
+
+// verify / repair rounds of one direction; returns 0, or PSMC_HIP_ECONVERGE after max_rounds repair rounds
+static int wide_rounds(psmc_hip_ctx *c, WideLaunch &w, bool bwd, int &rounds, int &tiles)
+{
+	const int nc = w.n_tiles;
+	std::vector<int> dirty(nc), heads;
+	rounds = tiles = 0;
+	for (;;) {
+		HIPCHK(c, hipMemsetAsync(w.cnt + (bwd ? 1 : 0), 0, sizeof(int), w.stream));
+		HIPCHK(c, hipMemsetAsync(w.warm + (bwd ? 1 : 0), 0, sizeof(unsigned long long), w.stream));
+		if (launch_wide_fast(w, bwd ? WF_VERIFY_B : WF_VERIFY_F)) return fail(c, PSMC_HIP_EDEVICE, "k_wf_verify", hipGetLastError());
+		int bad = 0;
+		HIPCHK(c, hipMemcpyAsync(&bad, w.cnt + (bwd ? 1 : 0), sizeof(int), hipMemcpyDeviceToHost, w.stream));
+		HIPCHK(c, hipMemcpyAsync(dirty.data(), w.dirty, sizeof(int) * nc, hipMemcpyDeviceToHost, w.stream));
+		HIPCHK(c, hipStreamSynchronize(w.stream));
+		if (bad == 0) return 0;
+		if (rounds >= c->max_rounds) return PSMC_HIP_ECONVERGE;
+		heads.clear();
+		for (int b = 0; b < nc; ++b) {
+			if (!dirty[b]) continue;
+			const int nb = bwd ? b + 1 : b - 1; // the neighbour it starts from
+			const bool follows = nb >= 0 && nb < nc && c->wf_chunks[nb].off == c->wf_chunks[b].off && dirty[nb];
+			if (!follows) heads.push_back(b);
+		}
+		HIPCHK(c, hipMemcpyAsync(c->d_wf_list, heads.data(), sizeof(int) * heads.size(), hipMemcpyHostToDevice, w.stream));
+		w.list = c->d_wf_list;
+		if (launch_wide_fast(w, bwd ? WF_ACC_REPAIR : WF_FWD_REPAIR, (int)heads.size()))
+			return fail(c, PSMC_HIP_EDEVICE, "wide repair", hipGetLastError());
+		HIPCHK(c, hipStreamSynchronize(w.stream)); // (heads lives on the host)
+		++rounds; tiles += (int)heads.size();
+	}
+}
+
+int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t ust)
+{
+	char msg[320];
+	if (c->ns > 256) {
+		snprintf(msg, sizeof msg, "estep_factored: the wide fast path (\"wide_fast\") covers 129..256 states; %d states run on the exact kernels only (psmc_hip_estep)", c->n);
+		return fail(c, PSMC_HIP_ENOTSUP, msg);
+	}
+	if (c->n_seg < 1) return fail(c, PSMC_HIP_ESTATE, "estep_factored: no segments loaded");
+	HIPCHK(c, hipSetDevice(c->device));
+	const int n = c->n, S = c->ns;
+	std::vector<double> sp((size_t)5 * n);
+	if (!c->struct_opt) // as up to 128 states: the factored statistics come from the structured sweeps only
+		return fail(c, PSMC_HIP_ENOTSUP, "estep_factored: the factored statistics need the structured sweeps (option \"structured\" is 0)");
+	if (!factor_structure(n, n, a, sp.data()))
+		return fail(c, PSMC_HIP_ENOTSUP, "estep_factored: the wide fast path needs a transition matrix of the PSMC form (two rank-1 triangles, core.c:112-122)");
+	int rc;
+	if ((rc = ensure_fast_buffers(c))) return rc;
+	if (!c->h_wf_par && hipHostMalloc((void **)&c->h_wf_par, sizeof(double) * WF_PAR * S, hipHostMallocDefault) != hipSuccess) {
+		c->h_wf_par = nullptr;
+		return fail(c, PSMC_HIP_ENOMEM, "hipHostMalloc");
+	}
+	if (!c->d_wf_par && (rc = dev_alloc(c, &c->d_wf_par, (size_t)WF_PAR * S))) return rc;
+	if ((c->plan_dirty || c->wf_chunks.empty()) && (rc = plan_wide(c))) return rc;
+	const int64_t bins = c->total + 128;
+	if (c->wf_bins < bins) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins)
+		if ((rc = dev_alloc(c, &c->d_wf_X, (size_t)bins * S))) { c->wf_bins = 0; return rc; }
+		if ((rc = dev_alloc(c, &c->d_wf_inv, (size_t)bins))) { c->wf_bins = 0; return rc; }
+		c->wf_bins = bins;
+	}
+	HIPCHK(c, hipStreamSynchronize(c->stream)); // the previous upload out of the pinned staging block
+	double *hp = c->h_wf_par;
+	memset(hp, 0, sizeof(double) * WF_PAR * S); // padded states: zero emission and matrix entries
+	for (int k = 0; k < n; ++k) { hp[k] = e[k]; hp[S + k] = e[n + k]; hp[2 * S + k] = a0[k]; }
+	for (int v = 0; v < 5; ++v)
+		for (int k = 0; k < n; ++k) hp[(size_t)(3 + v) * S + k] = sp[(size_t)v * n + k];
+	hipStream_t st = c->stream;
+	if (ust && ust != st) { HIPCHK(c, hipEventRecord(c->evx[0], ust)); HIPCHK(c, hipStreamWaitEvent(st, c->evx[0], 0)); }
+	HIPCHK(c, hipEventRecord(c->ev[0], st));
+	HIPCHK(c, hipMemcpyAsync(c->d_wf_par, hp, sizeof(double) * WF_PAR * S, hipMemcpyHostToDevice, st));
+	WideLaunch w;
+	memset(&w, 0, sizeof(w));
+	w.stream = st; w.ns = S; w.n_states = n; w.n_tiles = (int)c->wf_chunks.size(); w.chain = c->learn ? 1 : 0;
+	w.tol = c->warm_tol; w.tiny_total = (double)c->sel.size() * HMM_TINY_H;
+	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks; w.list = c->d_wf_list; w.dirty = c->d_wf_dirty;
+	w.cnt = c->d_cnt; w.warm = c->d_warm;
+	w.X = c->d_wf_X; w.inv = c->d_wf_inv; w.entry = c->d_wf_entry; w.bentry = c->d_wf_bentry; w.bexit = c->d_wf_bexit;
+	w.part = c->d_wf_part; w.LLpart = c->d_wf_ll; w.stage = c->d_stage; w.out = d_out;
+	c->report = FastReport{0, 0, 0, 0, 0, 0, 2};
+	c->wf_ran = true; c->last_fused = 3;
+	if (launch_wide_fast(w, WF_FWD) || launch_wide_fast(w, WF_BWARM)) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
+	int r = 0, t = 0;
+	rc = wide_rounds(c, w, false, r, t);
+	c->report.fwd_rounds = r; c->report.fwd_tiles = t;
+	if (rc == PSMC_HIP_ECONVERGE) return fail(c, rc, "fast mode (wide_fast): forward tile boundaries did not converge within max_rounds");
+	if (rc) return rc;
+	if (launch_wide_fast(w, WF_ACC)) return fail(c, PSMC_HIP_EDEVICE, "k_wf_acc", hipGetLastError());
+	rc = wide_rounds(c, w, true, r, t);
+	c->report.bwd_rounds = r; c->report.bwd_tiles = t;
+	if (rc == PSMC_HIP_ECONVERGE) return fail(c, rc, "fast mode (wide_fast): backward tile boundaries did not converge within max_rounds");
+	if (rc) return rc;
+	if (launch_wide_fast(w, WF_FINISH)) return fail(c, PSMC_HIP_EDEVICE, "k_wf_ll / k_wf_reduce", hipGetLastError());
+	HIPCHK(c, hipEventRecord(c->ev[4], st));
+	if (ust && ust != st) { HIPCHK(c, hipEventRecord(c->evx[1], st)); HIPCHK(c, hipStreamWaitEvent(ust, c->evx[1], 0)); }
+	c->report.converged = 1;
+	return 0;
+}
+
+int estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *sums, double *E, double *LL)
+{
+	int rc = ensure_fast_buffers(c);
+	if (rc) return rc;
+	if ((rc = estep_wide_fast(c, a, e, a0, c->d_stats, c->stream))) return rc;
+	const int n = c->n;
+	std::vector<double> h((size_t)7 * n + 1);
+	HIPCHK(c, hipMemcpyAsync(h.data(), c->d_stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	float ms = 0.0f;
+	c->timing_valid = hipEventElapsedTime(&ms, c->ev[0], c->ev[4]) == hipSuccess;
+	if (!c->timing_valid) (void)hipGetLastError();
+	for (double &v : c->last_ms) v = 0.0;
+	c->last_ms[0] = ms;
+	if (sums) memcpy(sums, h.data(), sizeof(double) * 5 * n);
+	if (E) memcpy(E, h.data() + (size_t)5 * n, sizeof(double) * 2 * n);
+	if (LL) *LL = h[(size_t)7 * n];
+	return PSMC_HIP_OK;
+}

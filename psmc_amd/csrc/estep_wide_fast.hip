@@ -1,0 +1,485 @@
+// estep_wide_fast.hip -- FAST mode, factored statistics, 129..256 states (option "wide_fast"; api_wide_fast.hip drives it).
+//
+// The algebra is the one of estep_struct.hip (forward / backward step in O(N): two scans) and estep_factored.hip (the five
+// triangular sums of A, E and LL straight from the backward sweep).  Only the layout differs: a state vector of S = 192 or 256
+// padded states is ONE tile per wave, 64 lanes x NPL adjacent states (NPL = 3 or 4, lane j holds k = NPL j + i), so the
+// cross-lane part of a scan is a whole-wave scan (wave_shr / wave_shl by one lane, then the row scans of struct_prims.h) instead
+// of a 16-lane row scan.  Nothing goes through LDS: the five structure vectors and the two emission rows stay in registers.
+// Padded states have zero matrix entries and zero emissions, so they stay zero.
+//
+// One wave per tile and direction:
+//   k_wf_fwd    speculative forward sweep (warm-up from a0, the stationary vector, `wf` bins before the tile; a segment's first tile
+//               from X_1 = a0 e[o_1]); stores X (one row of 8 S bytes per position), 1/d_p at p % 4 == 0 (a power of two: pow2_rcp)
+//               and the start vector `entry`.  REPAIR: from the neighbour's X_{lo-1}; with `chain` the wave walks on into the next
+//               tile while that tile's start vector disagrees with the new exit vector (a glued run: one round instead of one per tile).
+//   k_wf_bwarm  speculative backward warm-up: bentry = bt_{top+1} of every tile, from bt_q = e[o_q] `wb` bins above it.
+//   k_wf_acc    the tile's backward sweep from bentry, reading X: the seven per-lane sums of estep_factored.hip, bexit = bt_lo,
+//               the tile's partials (a repaired tile OVERWRITES them: nothing is counted twice).  REPAIR: from the exit vector of the
+//               tile above, chaining downwards like the forward repair.
+//   k_wf_verify every tile's start vector against its neighbour's exit vector (the test of estep_fast.hip k_verify).
+//   k_wf_ll, k_wf_reduce1/2: the log-likelihood of a tile (as estep_fast.hip k_ll) and the fixed-order sum of the partials.
+// A chain never enters a tile that is itself the head of a repair in the same launch, nor the neighbour whose boundary vector such a
+// head starts from: no wave of a repair launch reads or writes what another wave of it writes, so the result does not depend on
+// scheduling.  A tile a chain stops in front of is flagged again by the next verify round.
+#include <hip/hip_runtime.h>
+#include "wave_prims.h"
+#include "struct_prims.h"
+#include "psmc_hip_internal.h"
+#include "wide_fast.h"
+
+namespace psmc {
+namespace wide {
+
+constexpr int WACC = 7; // SL SU DG CL CU E0 E1
+// parameter block of the wide fast path, S doubles each: e0 | e1 | a0 | P | R | qa | c | dd
+constexpr int WP_E0 = 0, WP_E1 = 1, WP_A0 = 2, WP_SP = 3;
+
+// sums over lanes m' < m / m' > m of the whole wave (0 in lane 0 / 63): shift by one lane, then the inclusive scans
+__device__ __forceinline__ double wave_excl_prefix(double t) { return wave_prefix_incl_bc(dpp_z<0x138>(t)); } // wave_shr:1
+__device__ __forceinline__ double wave_excl_suffix(double t, const WaveScanMasks &m) { return wave_suffix_incl(dpp_z<0x130>(t), m); } // wave_shl:1
+// sum over the wave, the same bits in every lane (row sums, then the four rows in a fixed order)
+__device__ __forceinline__ double wave_total(double t) {
+	t = row_sum16(t);
+	return (readlane_f64(t, 0) + readlane_f64(t, 16)) + (readlane_f64(t, 32) + readlane_f64(t, 48));
+}
+__device__ __forceinline__ double wave_maxv(double v) {
+#pragma unroll
+	for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
+	return v;
+}
+template <int NPL> __device__ __forceinline__ double lsum(const double (&x)[NPL]) {
+	double t = x[0];
+#pragma unroll
+	for (int i = 1; i < NPL; ++i) t += x[i];
+	return t;
+}
+template <int NPL> __device__ __forceinline__ void ld(const double *p, double (&v)[NPL]) {
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) v[i] = p[i];
+}
+template <int NPL> __device__ __forceinline__ void st(double *p, const double (&v)[NPL]) {
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) p[i] = v[i];
+}
+// the five vectors in the roles load_struct_par (estep_struct.hip) gives them: forward mS = P, wS = qa, mP = R, wP = c;
+// backward mS = c, wS = R, mP = qa, wP = P
+template <int NPL> __device__ __forceinline__ void load_par(const double *__restrict__ par, int k0, bool fwd, StructParN<NPL> &c) {
+	constexpr int S = 64 * NPL;
+	const double *sp = par + WP_SP * S + k0; // P | R | qa | c | dd
+	ld<NPL>(sp + (fwd ? 0 : 3 * S), c.mS); ld<NPL>(sp + (fwd ? 2 * S : S), c.wS);
+	ld<NPL>(sp + (fwd ? S : 2 * S), c.mP); ld<NPL>(sp + (fwd ? 3 * S : 0), c.wP); ld<NPL>(sp + 4 * S, c.dd);
+}
+template <int NPL> __device__ __forceinline__ void emis(int sym, const double (&e0)[NPL], const double (&e1)[NPL], double (&ev)[NPL]) {
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) ev[i] = sym == 0 ? e0[i] : (sym == 1 ? e1[i] : 1.0);
+}
+// x <- M x: wS.SUF(x.mS) + wP.PRE(x.mP) + dd.x (inclusive scans over the S states)
+template <int NPL> __device__ __forceinline__ void wstep(const StructParN<NPL> &c, double (&x)[NPL], const WaveScanMasks &wm) {
+	double su[NPL], pv[NPL];
+	su[NPL - 1] = x[NPL - 1] * c.mS[NPL - 1];
+#pragma unroll
+	for (int i = NPL - 2; i >= 0; --i) su[i] = __builtin_fma(x[i], c.mS[i], su[i + 1]);
+	pv[0] = x[0] * c.mP[0];
+#pragma unroll
+	for (int i = 1; i < NPL; ++i) pv[i] = __builtin_fma(x[i], c.mP[i], pv[i - 1]);
+	const double ES = wave_excl_suffix(su[0], wm), EP = wave_excl_prefix(pv[NPL - 1]);
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) {
+		const double t = __builtin_fma(c.wS[i], su[i], __builtin_fma(c.wP[i], pv[i], c.dd[i] * x[i]));
+		x[i] = __builtin_fma(c.wS[i], ES, __builtin_fma(c.wP[i], EP, t));
+	}
+}
+// max_k |u/|u| - v/|v|| / max_k v/|v| (u: the vector a tile built on, v: what its neighbour computed); NaN anywhere: +inf
+template <int NPL> __device__ __forceinline__ double wmismatch(const double (&u)[NPL], const double (&v)[NPL]) {
+	const double iu = 1.0 / wave_total(lsum<NPL>(u)), iv = 1.0 / wave_total(lsum<NPL>(v));
+	double num = 0.0, den = 0.0;
+	bool bad = iu != iu || iv != iv;
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) {
+		num = fmax(num, fabs(u[i] * iu - v[i] * iv)); den = fmax(den, fabs(v[i] * iv));
+		bad = bad || u[i] != u[i] || v[i] != v[i];
+	}
+	num = wave_maxv(num); den = wave_maxv(den);
+	return __any(bad) ? __builtin_inf() : num / den;
+}
+__device__ __forceinline__ bool same_seg(const Chunk *__restrict__ ch, int a, int b) { return ch[a].off == ch[b].off; }
+// a tile that a repair launch of this round starts a wave on (dirty, and its predecessor in the sweep direction is not)
+__device__ __forceinline__ bool head_f(const Chunk *__restrict__ ch, const int *__restrict__ dirty, int b) {
+	return dirty[b] && !(b > 0 && same_seg(ch, b - 1, b) && dirty[b - 1]);
+}
+__device__ __forceinline__ bool head_b(const Chunk *__restrict__ ch, const int *__restrict__ dirty, int n, int b) {
+	return dirty[b] && !(b + 1 < n && same_seg(ch, b, b + 1) && dirty[b + 1]);
+}
+
+// ------------------------------------------------------------------ forward
+template <int NPL, bool REPAIR>
+__global__ __launch_bounds__(64) void k_wf_fwd(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                 const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
+                                                 const int *__restrict__ dirty, int chain, double tol, double *__restrict__ X,
+                                                 double *__restrict__ inv, double *__restrict__ entry)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane;
+	const WaveScanMasks wm = wave_scan_masks(lane);
+	StructParN<NPL> sc;
+	load_par<NPL>(par, k0, true, sc);
+	double e0[NPL], e1[NPL];
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+	if (REPAIR) __builtin_amdgcn_s_setprio(3);
+	int b = REPAIR ? list[blockIdx.x] : (int)blockIdx.x;
+	Chunk c = chunks[b];
+	double x[NPL];
+	int p0;
+	if (REPAIR) { // from the neighbour's X_{lo-1} (a repaired tile is never a segment's first)
+		ld<NPL>(X + (c.off + c.lo - 2) * S + k0, x);
+		p0 = c.lo;
+	} else {
+		const int ws = max(1, c.lo - c.wf);
+		ld<NPL>(par + WP_A0 * S + k0, x);
+		if (ws == 1) { // true start: X_1 = a0 e[o_1]
+			double ev[NPL];
+			emis<NPL>((int)obs[c.off] & 3, e0, e1, ev);
+#pragma unroll
+			for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
+			if (c.lo == 1) st<NPL>(X + c.off * S + k0, x);
+			p0 = 2;
+		} else p0 = ws;
+	}
+	for (;;) {
+		const uint8_t *o = obs + c.off;
+		double *fo = X + c.off * S + k0, *io = inv + c.off;
+		const int lo = c.lo, hi = c.hi;
+		if (p0 == lo) st<NPL>(entry + (int64_t)b * S + k0, x); // the X_{lo-1} this tile builds on
+		for (int g = (p0 - 1) >> 2; 4 * g < hi; ++g) { // positions 4g+1 .. 4g+4 (indices 4g .. 4g+3)
+			const unsigned w = *reinterpret_cast<const unsigned *>(o + 4 * (int64_t)g);
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				const int p = 4 * g + j + 1;
+				if (p < p0 || p > hi) continue;
+				if (p == lo && p != p0) st<NPL>(entry + (int64_t)b * S + k0, x);
+				double ev[NPL];
+				emis<NPL>((int)((w >> (8 * j)) & 3u), e0, e1, ev);
+				if (j == 3) { // p % 4 == 0: 1/d_p, a power of two (struct_prims.h pow2_rcp)
+					const double iv = pow2_rcp(wave_total(lsum<NPL>(x)));
+#pragma unroll
+					for (int i = 0; i < NPL; ++i) ev[i] *= iv;
+					if (p >= lo && lane == 0) io[p - 1] = iv;
+				}
+				wstep<NPL>(sc, x, wm);
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
+				if (p >= lo) st<NPL>(fo + (int64_t)(p - 1) * S, x);
+			}
+		}
+		if (!REPAIR || !chain) break;
+		// glued run: go on into the next tile while its start vector disagrees with this exit vector -- but not into a head of this
+		// launch, nor into the tile before one (that head reads the tile's last X row as its start vector)
+		const int nb = b + 1;
+		if (nb >= n || !same_seg(chunks, b, nb) || (chunks[nb].flags & CHUNK_ANCHOR_F) || head_f(chunks, dirty, nb)) break;
+		if (nb + 1 < n && same_seg(chunks, nb, nb + 1) && head_f(chunks, dirty, nb + 1)) break;
+		double u[NPL];
+		ld<NPL>(entry + (int64_t)nb * S + k0, u);
+		if (wmismatch<NPL>(u, x) <= tol) break;
+		b = nb; c = chunks[b]; p0 = c.lo;
+	}
+}
+
+// ------------------------------------------------------------------ backward
+// one backward step at position p: x = bt_{p+1} -> bt_p (own scaling at p % 4 == 0: 1/sum(bt_{p+1}))
+template <int NPL, bool NORM>
+__device__ __forceinline__ void bstep(const StructParN<NPL> &sc, const WaveScanMasks &wm, int sym, const double (&e0)[NPL],
+                                      const double (&e1)[NPL], double (&x)[NPL])
+{
+	double ev[NPL];
+	emis<NPL>(sym, e0, e1, ev);
+	if (NORM) {
+		const double sb = rcp_newton(wave_total(lsum<NPL>(x)));
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) ev[i] *= sb;
+	}
+	wstep<NPL>(sc, x, wm);
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
+}
+template <int NPL>
+__global__ __launch_bounds__(64) void k_wf_bwarm(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                   const Chunk *__restrict__ chunks, double *__restrict__ bentry)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane, b = blockIdx.x;
+	const WaveScanMasks wm = wave_scan_masks(lane);
+	const Chunk c = chunks[b];
+	const int top = min(c.hi, c.L - 1);
+	if (top < c.lo) return; // a tile holding only position L owns no transition
+	StructParN<NPL> sc;
+	load_par<NPL>(par, k0, false, sc);
+	double e0[NPL], e1[NPL];
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+	const uint8_t *o = obs + c.off;
+	const int q = min(c.hi + c.wb + 1, c.L); // B_q := 1: bt_q = e[o_q]
+	double x[NPL];
+	emis<NPL>((int)o[q - 1] & 3, e0, e1, x);
+	for (int g = (q - 2) >> 2; g >= 0 && 4 * g + 4 > top; --g) { // positions q-1 .. top+1, highest first (group g holds 4g+1 .. 4g+4)
+		const unsigned w = *reinterpret_cast<const unsigned *>(o + 4 * (int64_t)g);
+#pragma unroll
+		for (int j = 3; j >= 0; --j) {
+			const int p = 4 * g + j + 1;
+			if (p > q - 1 || p <= top) continue;
+			const int sym = (int)((w >> (8 * j)) & 3u);
+			if (j == 3) bstep<NPL, true>(sc, wm, sym, e0, e1, x); else bstep<NPL, false>(sc, wm, sym, e0, e1, x);
+		}
+	}
+	st<NPL>(bentry + (int64_t)b * S + k0, x);
+}
+
+// One position p of the accumulate sweep (estep_factored.hip acc_step with whole-wave scans): x = bt_{p+1} on entry, bt_p on exit;
+// X = X_p; inv = the forward scale factor at p (NORM: p % 4 == 0).  The partial sums are kept in units of the current I.
+template <int NPL, bool NORM>
+__device__ __forceinline__ void astep(const StructParN<NPL> &sc, const WaveScanMasks &wm, int sym, const double (&e0)[NPL],
+                                      const double (&e1)[NPL], const double (&X)[NPL], double (&x)[NPL], double inv,
+                                      double (&acc)[WACC][NPL], double &I_lane)
+{
+	double ev[NPL];
+	emis<NPL>(sym, e0, e1, ev);
+	const double m0 = sym == 0 ? 1.0 : 0.0, m1 = sym == 1 ? 1.0 : 0.0;
+	double f = 1.0;
+	if (NORM) {
+		const double sb = rcp_newton(wave_total(lsum<NPL>(x)));
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) ev[i] *= sb;
+		f = sb * pow2_rcp(inv);
+	}
+	double su[NPL + 1], pv[NPL + 1], sx[NPL + 1], px[NPL + 1];
+	su[NPL] = 0.0; sx[NPL] = 0.0; pv[0] = 0.0; px[0] = 0.0; // pv / px shifted by one: pv[i+1] = inclusive at i
+#pragma unroll
+	for (int i = NPL - 1; i >= 0; --i) { su[i] = __builtin_fma(x[i], sc.mS[i], su[i + 1]); sx[i] = __builtin_fma(X[i], sc.wP[i], sx[i + 1]); }
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) { pv[i + 1] = __builtin_fma(x[i], sc.mP[i], pv[i]); px[i + 1] = __builtin_fma(X[i], sc.wS[i], px[i]); }
+	const double ES = wave_excl_suffix(su[0], wm), EP = wave_excl_prefix(pv[NPL]);
+	const double EX = wave_excl_suffix(sx[0], wm), PX = wave_excl_prefix(px[NPL]);
+	double Il = 0.0;
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) {
+		const double t = __builtin_fma(sc.wS[i], su[i], __builtin_fma(sc.wP[i], pv[i + 1], sc.dd[i] * x[i]));
+		const double y = __builtin_fma(sc.wS[i], ES, __builtin_fma(sc.wP[i], EP, t)); // (a bt_{p+1})[k]
+		const double gk = X[i] * y;                                                    // I * posterior of state k at p
+		acc[0][i] = __builtin_fma(X[i], EP + pv[i], acc[0][i]);     // SL: strictly below k
+		acc[1][i] = __builtin_fma(X[i], ES + su[i + 1], acc[1][i]); // SU: strictly above k
+		acc[2][i] = __builtin_fma(X[i], x[i], acc[2][i]);           // DG
+		acc[3][i] = __builtin_fma(x[i], EX + sx[i + 1], acc[3][i]); // CL: rows k > l
+		acc[4][i] = __builtin_fma(x[i], PX + px[i], acc[4][i]);     // CU: rows k < l
+		acc[5][i] = __builtin_fma(gk, m0, acc[5][i]);
+		acc[6][i] = __builtin_fma(gk, m1, acc[6][i]);
+		Il += gk;
+		x[i] = y * ev[i];
+	}
+	I_lane = Il;
+	if (NORM) { // ... now in units of I_{p-1}
+#pragma unroll
+		for (int q = 0; q < WACC; ++q)
+#pragma unroll
+			for (int i = 0; i < NPL; ++i) acc[q][i] *= f;
+		I_lane *= f;
+	}
+}
+template <int NPL, bool REPAIR>
+__global__ __launch_bounds__(64) void k_wf_acc(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                 const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
+                                                 const int *__restrict__ dirty, int chain, double tol, const double *__restrict__ X,
+                                                 const double *__restrict__ inv, double *__restrict__ bentry,
+                                                 double *__restrict__ bexit, double *__restrict__ part)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane;
+	const WaveScanMasks wm = wave_scan_masks(lane);
+	StructParN<NPL> sc;
+	load_par<NPL>(par, k0, false, sc);
+	double e0[NPL], e1[NPL];
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+	if (REPAIR) __builtin_amdgcn_s_setprio(3);
+	int b = REPAIR ? list[blockIdx.x] : (int)blockIdx.x;
+	double x[NPL];
+	if (REPAIR) { ld<NPL>(bexit + (int64_t)(b + 1) * S + k0, x); st<NPL>(bentry + (int64_t)b * S + k0, x); }
+	else ld<NPL>(bentry + (int64_t)b * S + k0, x);
+	for (;;) {
+		const Chunk c = chunks[b];
+		const int lo = c.lo, top = min(c.hi, c.L - 1);
+		const uint8_t *o = obs + c.off;
+		const double *fo = X + c.off * S + k0, *io = inv + c.off;
+		double acc[WACC][NPL], accI = 1.0;
+#pragma unroll
+		for (int q = 0; q < WACC; ++q)
+#pragma unroll
+			for (int i = 0; i < NPL; ++i) acc[q][i] = 0.0;
+		if (top >= lo) {
+			double Xc[NPL], Xn[NPL];
+			ld<NPL>(fo + (int64_t)(top - 1) * S, Xc);
+			for (int g = (top - 1) >> 2; g >= 0 && 4 * g + 4 >= lo; --g) {
+				const unsigned w = *reinterpret_cast<const unsigned *>(o + 4 * (int64_t)g);
+				const double ivg = io[4 * g + 3]; // the forward scale factor of position 4g+4 (read only where that lies inside the tile)
+#pragma unroll
+				for (int j = 3; j >= 0; --j) {
+					const int p = 4 * g + j + 1;
+					if (p > top || p < lo) continue;
+					if (p > lo) ld<NPL>(fo + (int64_t)(p - 2) * S, Xn); // X_{p-1}, for the next step
+					const int sym = (int)((w >> (8 * j)) & 3u);
+					if (j == 3) astep<NPL, true>(sc, wm, sym, e0, e1, Xc, x, ivg, acc, accI);
+					else astep<NPL, false>(sc, wm, sym, e0, e1, Xc, x, 1.0, acc, accI);
+#pragma unroll
+					for (int i = 0; i < NPL; ++i) Xc[i] = Xn[i];
+				}
+			}
+			st<NPL>(bexit + (int64_t)b * S + k0, x); // bt_lo
+		}
+		const double iI = top >= lo ? rcp_newton(wave_total(accI)) : 1.0;
+		const double mult = (double)c.mult * iI;
+		double *out = part + (int64_t)b * (WACC * S) + k0;
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) {
+			const double akk = sc.dd[i] + sc.wP[i] * sc.mP[i] + sc.wS[i] * sc.mS[i]; // a[k][k]
+			acc[0][i] *= sc.wP[i] * mult; acc[1][i] *= sc.wS[i] * mult; acc[2][i] *= akk * mult;
+			acc[3][i] *= sc.mP[i] * mult; acc[4][i] *= sc.mS[i] * mult; acc[5][i] *= mult; acc[6][i] *= mult;
+		}
+#pragma unroll
+		for (int q = 0; q < WACC; ++q) st<NPL>(out + q * S, acc[q]);
+		if (!REPAIR || !chain || top < lo) break;
+		// glued run: go on into the tile below while its start vector disagrees with this exit vector -- but not into a head of this
+		// launch, nor into the tile above one (that head reads the tile's bexit as its start vector)
+		const int nb = b - 1;
+		if (nb < 0 || !same_seg(chunks, nb, b) || (chunks[nb].flags & CHUNK_ANCHOR_B) || head_b(chunks, dirty, n, nb)) break;
+		if (nb - 1 >= 0 && same_seg(chunks, nb - 1, nb) && head_b(chunks, dirty, n, nb - 1)) break;
+		double u[NPL];
+		ld<NPL>(bentry + (int64_t)nb * S + k0, u);
+		if (wmismatch<NPL>(u, x) <= tol) break;
+		b = nb;
+		st<NPL>(bentry + (int64_t)b * S + k0, x);
+	}
+}
+
+// ------------------------------------------------------------------ verify, LL, reduce
+template <int NPL, bool BWD>
+__global__ __launch_bounds__(64) void k_wf_verify(const Chunk *__restrict__ chunks, int n, double tol, const double *__restrict__ X,
+                                                    const double *__restrict__ mine, const double *__restrict__ bexit,
+                                                    int *__restrict__ dirty, int *__restrict__ cnt, unsigned long long *__restrict__ warm)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane, b = blockIdx.x;
+	const Chunk c = chunks[b];
+	bool check;
+	if (!BWD) check = c.lo > 1 && !(c.flags & CHUNK_ANCHOR_F);
+	else check = !(c.flags & (CHUNK_ANCHOR_B | CHUNK_LAST)) && min(c.hi, c.L - 1) >= c.lo && b + 1 < n && chunks[b + 1].off == c.off;
+	double m = 0.0;
+	if (check) {
+		double u[NPL], v[NPL];
+		ld<NPL>(mine + (int64_t)b * S + k0, u);
+		ld<NPL>(BWD ? bexit + (int64_t)(b + 1) * S + k0 : X + (c.off + c.lo - 2) * S + k0, v);
+		m = wmismatch<NPL>(u, v);
+	}
+	if (lane == 0) {
+		const int bad = check && !(m <= tol);
+		dirty[b] = bad;
+		if (bad) atomicAdd(cnt, 1);
+		if (check) atomicMax(warm, (unsigned long long)__double_as_longlong(m));
+	}
+}
+
+template <int NPL>
+__global__ __launch_bounds__(64) void k_wf_ll(const Chunk *__restrict__ chunks, const double *__restrict__ X, const double *__restrict__ inv,
+                                                const double *__restrict__ entry, double *__restrict__ LLpart)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane, b = blockIdx.x;
+	const Chunk c = chunks[b];
+	const double *io = inv + c.off;
+	double prod = 1.0, ll = 0.0;
+	const int first = (max(c.lo, 2) + NORM_EVERY - 1) & ~(NORM_EVERY - 1);
+	for (int p = first + NORM_EVERY * lane; p <= c.hi; p += NORM_EVERY * 64) {
+		prod *= io[p - 1];
+		if (prod > 1e280 || prod < 1e-280) { ll -= log(prod); prod = 1.0; }
+	}
+	ll -= log(prod);
+	ll = wave_total(ll);
+	double u[NPL];
+	if (c.lo > 1) { // the tile was computed from entry = X_{lo-1} up to a factor: put the telescoping sum back in step
+		double v[NPL];
+		ld<NPL>(X + (c.off + c.lo - 2) * S + k0, u); ld<NPL>(entry + (int64_t)b * S + k0, v);
+		ll += log(wave_total(lsum<NPL>(u))) - log(wave_total(lsum<NPL>(v)));
+	}
+	if (c.hi == c.L) {
+		ld<NPL>(X + (c.off + c.L - 1) * S + k0, u);
+		ll += log(wave_total(lsum<NPL>(u)));
+	}
+	if (lane == 0) LLpart[b] = ll * (double)c.mult;
+}
+
+// fixed-order two-stage sum over the tiles (estep_factored.hip k_reduce_factored1/2 at S = 192 / 256)
+template <int S>
+__global__ __launch_bounds__(S) void k_wf_reduce1(const double *__restrict__ part, int n_tiles, const double *__restrict__ LLpart,
+                                                    double *__restrict__ stage)
+{
+	constexpr int FSL = WACC * S + 1;
+	const int k = threadIdx.x, q = blockIdx.x, y = blockIdx.y;
+	if (q < WACC) {
+		double s = 0.0;
+		for (int j = y; j < n_tiles; j += RED_ROWS) s += part[(int64_t)j * (WACC * S) + q * S + k];
+		stage[(int64_t)y * FSL + q * S + k] = s;
+	} else if (k == 0) {
+		double s = 0.0;
+		for (int j = y; j < n_tiles; j += RED_ROWS) s += LLpart[j];
+		stage[(int64_t)y * FSL + WACC * S] = s;
+	}
+}
+template <int S>
+__global__ __launch_bounds__(S) void k_wf_reduce2(const double *__restrict__ stage, double tiny_total, int n, double *__restrict__ out)
+{
+	constexpr int FSL = WACC * S + 1;
+	const int k = threadIdx.x, q = blockIdx.x;
+	if (q == WACC) {
+		if (k == 0) {
+			double s = 0.0;
+			for (int y = 0; y < RED_ROWS; ++y) s += stage[(int64_t)y * FSL + WACC * S];
+			out[WACC * n] = s;
+		}
+		return;
+	}
+	double s = 0.0;
+	for (int y = 0; y < RED_ROWS; ++y) s += stage[(int64_t)y * FSL + q * S + k];
+	if (k < n) { // the HMM_TINY seeds of khmm.c:305-308, per cell
+		const double cells = q == 0 ? k : (q == 1 ? n - 1 - k : (q == 2 ? 1 : (q == 3 ? n - 1 - k : (q == 4 ? k : 1))));
+		out[q * n + k] = s + cells * tiny_total;
+	}
+}
+
+template <int NPL> static int launch_all(const WideLaunch &w, int what, int n_list)
+{
+	constexpr int S = 64 * NPL;
+	const int nc = w.n_tiles;
+	hipStream_t st = w.stream;
+	switch (what) {
+	case WF_FWD: hipLaunchKernelGGL((k_wf_fwd<NPL, false>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry); break;
+	case WF_FWD_REPAIR: hipLaunchKernelGGL((k_wf_fwd<NPL, true>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry); break;
+	case WF_BWARM: hipLaunchKernelGGL(k_wf_bwarm<NPL>, dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, w.bentry); break;
+	case WF_ACC: hipLaunchKernelGGL((k_wf_acc<NPL, false>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.bentry, w.bexit, w.part); break;
+	case WF_ACC_REPAIR: hipLaunchKernelGGL((k_wf_acc<NPL, true>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.bentry, w.bexit, w.part); break;
+	case WF_VERIFY_F: hipLaunchKernelGGL((k_wf_verify<NPL, false>), dim3(nc), dim3(64), 0, st, w.chunks, nc, w.tol, w.X, w.entry, w.bexit, w.dirty, w.cnt, w.warm); break;
+	case WF_VERIFY_B: hipLaunchKernelGGL((k_wf_verify<NPL, true>), dim3(nc), dim3(64), 0, st, w.chunks, nc, w.tol, w.X, w.bentry, w.bexit, w.dirty, w.cnt + 1, w.warm + 1); break;
+	case WF_FINISH:
+		hipLaunchKernelGGL(k_wf_ll<NPL>, dim3(nc), dim3(64), 0, st, w.chunks, w.X, w.inv, w.entry, w.LLpart);
+		hipLaunchKernelGGL(k_wf_reduce1<S>, dim3(WACC + 1, RED_ROWS), dim3(S), 0, st, w.part, nc, w.LLpart, w.stage);
+		hipLaunchKernelGGL(k_wf_reduce2<S>, dim3(WACC + 1), dim3(S), 0, st, w.stage, w.tiny_total, w.n_states, w.out);
+		break;
+	default: return -1;
+	}
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+} // namespace wide
+
+int launch_wide_fast(const WideLaunch &w, int what, int n_list)
+{
+	if (w.ns == 192) return wide::launch_all<3>(w, what, n_list);
+	if (w.ns == 256) return wide::launch_all<4>(w, what, n_list);
+	return -1;
+}
+
+} // namespace psmc

@@ -209,6 +209,18 @@ struct psmc_hip_ctx {
 	// report -- [0] replicate context creation, [1] select, [2] plan_fast (tiling + per-plan allocations), [3] build_items,
 	// [4] launch_fast (kernels + verify / repair rounds, synchronous), [5] result read-back; and [6] repair rounds, [7] repaired tiles
 	double dbg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	// fast mode beyond 128 states (api_wide_fast.hip): "wide_fast" = 1 runs psmc_hip_estep_factored[_device] of a fast context with 129..256
+	// states on the kernels of estep_wide_fast.hip, in tables of its own (the exact tables stay what the last exact E-step left)
+	int wide_fast = 0;
+	bool wf_ran = false;                 // the last fast E-step of this context was one of the wide path (fast_info, fast_diag)
+	std::vector<Chunk> wf_chunks;        // its plan; rebuilt when plan_dirty
+	Chunk *d_wf_chunks = nullptr;
+	int wf_cap = 0, wf_T = 0, wf_W = 0;  // tiles allocated; tile length and warm-up of the plan
+	bool warmup_set = false;             // "warmup" was set: the wide path takes it instead of its own default (api_wide_fast.hip)
+	double *d_wf_X = nullptr, *d_wf_inv = nullptr; int64_t wf_bins = 0; // X [bins][ns], 1/d_p [bins]
+	double *d_wf_par = nullptr, *h_wf_par = nullptr;                     // e0 | e1 | a0 | P | R | qa | c | dd
+	double *d_wf_entry = nullptr, *d_wf_bentry = nullptr, *d_wf_bexit = nullptr, *d_wf_part = nullptr, *d_wf_ll = nullptr;
+	int *d_wf_dirty = nullptr, *d_wf_list = nullptr;
 };
 inline double dbg_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline psmc_hip_ctx *dbg_root(psmc_hip_ctx *c) { return c->parent ? c->parent : c; }
@@ -262,4 +274,8 @@ int  ensure_fast_buffers(psmc_hip_ctx *c);                                      
 int  auto_tile_len(const psmc_hip_ctx *c, int64_t bins, size_t n_work, bool structured);                    // api_fast.hip
 int  enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t st); // api_fast.hip
 int  read_warm(psmc_hip_ctx *c, hipStream_t st);                                                            // api_fast.hip
+bool factor_structure(int n, int S, const double *a, double *sp);                                         // api.hip
+void free_wide_fast(psmc_hip_ctx *c);                                                                       // api_wide_fast.hip
+int  estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t st); // api_wide_fast.hip
+int  estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *sums, double *E, double *LL); // api_wide_fast.hip
 int  estep_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *A, double *E, double *A0, double *LL, double *chk); // api_fast.hip

@@ -1,0 +1,25 @@
+// wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "psmc_hip_internal.h"
+
+namespace psmc {
+
+enum { WF_FWD, WF_FWD_REPAIR, WF_BWARM, WF_ACC, WF_ACC_REPAIR, WF_VERIFY_F, WF_VERIFY_B, WF_FINISH };
+
+struct WideLaunch {
+	hipStream_t stream;
+	int ns, n_states, n_tiles, chain; // ns: padded states, 192 or 256; chain: repairs walk on through glued runs
+	double tol, tiny_total;
+	const double *par;                // e0 | e1 | a0 | P | R | qa | c | dd, ns doubles each
+	const uint8_t *obs;
+	const Chunk *chunks;
+	const int *list;                  // repair launches: the head tiles
+	int *dirty, *cnt;                 // [n_tiles] verify flags; [2] failing tiles, forward | backward
+	unsigned long long *warm;         // [2] largest mismatch of the last verify, forward | backward (bits of a double)
+	double *X, *inv, *entry, *bentry, *bexit, *part, *LLpart, *stage, *out;
+};
+
+int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip
+
+} // namespace psmc

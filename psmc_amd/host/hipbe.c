@@ -210,4 +210,10 @@ int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_fa
 	return 0;
 }
 
+int psmc_hipbe_set_option(psmc_estep_backend *be, const char *key, double value)
+{
+	hip_be *h = (hip_be *)be->self;
+	return h->grp ? psmc_hip_group_set_option(h->grp, key, value) : psmc_hip_set_option(h->ctx, key, value);
+}
+
 psmc_hip_ctx *psmc_hipbe_ctx(psmc_estep_backend *be) { return be && be->self ? ((hip_be *)be->self)->ctx : 0; }

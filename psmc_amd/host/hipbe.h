@@ -10,6 +10,8 @@
  * devices (psmc_hip_group_*).  use_factored: hand psmc_run the factored E-step (fast mode + O(N) objective).
  * Returns 0 or a PSMC_HIP_E* code; be->destroy releases everything. */
 int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_factored, const char *devices, int device);
+/* psmc_hip_set_option / psmc_hip_group_set_option on the backend's context or group */
+int psmc_hipbe_set_option(psmc_estep_backend *be, const char *key, double value);
 /* the single context behind the backend (NULL for a sharded one): psmc_hip_set_cu_range, psmc_hip_reserve_tables */
 psmc_hip_ctx *psmc_hipbe_ctx(psmc_estep_backend *be);
 #endif

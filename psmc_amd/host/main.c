@@ -4,6 +4,8 @@
  *   PSMC_HIP_MODE=exact (default: .psmc byte-identical to the reference) | fast
  *   PSMC_HIP_DECODE=fast             with PSMC_HIP_MODE=fast and -d/-D/-c/-s: stay in fast mode and decode from the fast
  *                                    tables (without it such a run is an exact run throughout)
+ *   PSMC_HIP_WIDE=fast               with PSMC_HIP_MODE=fast and 129..256 states: factored fast E-steps on the wide fast path
+ *                                    (option "wide_fast"); without it, or with -d/-D/-c/-s, such a run is an exact run throughout
  *   PSMC_HIP_DEVICE=<index>          one GPU
  *   PSMC_HIP_DEVICES=<i>,<j>,...     the segments of every E-step sharded over these GPUs (psmc_hip_group_*: LPT
  *                                    partition, one RCCL all-reduce of the statistics per EM iteration in fast mode,
@@ -42,8 +44,10 @@ int main(int argc, char *argv[])
 		psmc_options_free(&o);
 		return 2;
 	}
-	if (n_states > 128 && mode_is_fast())
-		fprintf(stderr, "psmc: %d hidden states: the fast kernels stop at 128, every E-step of this run uses the exact ones\n", n_states);
+	/* PSMC_HIP_WIDE=fast: the factored E-step of 129..256 states on the fast kernels (not with decoding: that needs the exact tables) */
+	const char *wide_s = getenv("PSMC_HIP_WIDE");
+	const int wide_fast = wide_s && strcmp(wide_s, "fast") == 0 && mode_is_fast() && n_states > 128 && n_states <= 256 &&
+	                      !(o.decode || o.print_prob || o.cnt_file);
 	const char *mode_s = getenv("PSMC_HIP_MODE"), *dev_s = getenv("PSMC_HIP_DEVICE");
 	int mode = (mode_s && strcmp(mode_s, "fast") == 0) ? PSMC_HIP_MODE_FAST : PSMC_HIP_MODE_EXACT;
 	if ((o.decode || o.print_prob || o.cnt_file) && mode == PSMC_HIP_MODE_FAST) {
@@ -61,7 +65,12 @@ int main(int argc, char *argv[])
 	}
 	/* the factored E-step goes with the O(N) objective: fast mode (PSMC_FACTORED=0 keeps the full counts) */
 	const char *fs = getenv("PSMC_FACTORED"), *devs = getenv("PSMC_HIP_DEVICES");
-	const int use_factored = o.fast_mstep && mode == PSMC_HIP_MODE_FAST && n_states <= 128 && !(fs && atoi(fs) == 0);
+	const int use_factored = o.fast_mstep && mode == PSMC_HIP_MODE_FAST && (n_states <= 128 || wide_fast) && !(fs && atoi(fs) == 0);
+	/* (PSMC_FACTORED=0 or PSMC_FAST_MSTEP=0 ask for full counts, which beyond 128 states only the exact kernels compute) */
+	if (wide_fast && use_factored)
+		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=fast: factored E-steps on the wide fast kernels (full counts and decoding stay exact)\n", n_states);
+	else if (n_states > 128 && mode_is_fast())
+		fprintf(stderr, "psmc: %d hidden states: the fast kernels stop at 128, every E-step of this run uses the exact ones\n", n_states);
 	/* The input is read on a thread of its own while the device comes up: 0.35 s for a 30 M-bin genome beside 0.4 s of HIP start-up, of a
 	 * program that takes 1.0 s in all in fast mode (profiles/r06_fast_after_exact.txt).  psmc_run_begin takes the result over. */
 	pthread_t rd_tid;
@@ -69,7 +78,8 @@ int main(int argc, char *argv[])
 	/* (not from stdin: a device that does not come up must say so at once, not after the pipe has closed) */
 	const int rd_started = pj.in && o.in_file && strcmp(o.in_file, "-") != 0 && pthread_create(&rd_tid, 0, prefetch_input, &pj) == 0;
 	psmc_estep_backend be;
-	const int rc = psmc_hipbe_create(&be, n_states, mode, use_factored, devs, dev_s ? atoi(dev_s) : 0);
+	int rc = psmc_hipbe_create(&be, n_states, mode, use_factored, devs, dev_s ? atoi(dev_s) : 0);
+	if (rc == 0 && wide_fast && use_factored) rc = psmc_hipbe_set_option(&be, "wide_fast", 1);
 	if (rd_started) { pthread_join(rd_tid, 0); o.prefetched = pj.in; o.prefetch_rc = pj.rc; }
 	else free(pj.in);
 	if (rc) {

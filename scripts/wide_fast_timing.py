@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""What the factored E-step of the wide fast path ("wide_fast", estep_wide_fast.hip) costs against the wide exact kernels, on the
+30 M-bin genome bench.py builds (psmc_amd/sim.py), at 149, 200 and 256 states (patterns "1+74*2", "100*2", "128*2"):
+
+  (a) ms per factored E-step on the wide fast path, parameters moving every step (the host model of psmc_amd.hostlib with
+      lambdas scaled by a few per cent per step): the first E-step of a context and the mean of the later ones, with the
+      verify / repair rounds and repaired head tiles of every step
+  (b) ms per E-step of the wide exact kernels (psmc_hip_estep) on the same input and the first parameters (one step after a
+      warm-up of the allocations)
+  (c) with --cli: wall clock of `psmc -N5 -p "100*2"` on the genome in exact mode and with PSMC_HIP_MODE=fast PSMC_HIP_WIDE=fast
+
+Library calls are synchronous.  Writes one JSON object to stdout (progress on stderr).
+
+    python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PATTERNS = {149: ("1+74*2", 75), 200: ("100*2", 100), 256: ("128*2", 128)}
+
+
+def params_seq(n, steps, seed=11):
+    from psmc_amd import hostlib
+    pat, k = PATTERNS[n]
+    rng = np.random.default_rng(seed + n)
+    lam = np.exp(rng.normal(0.0, 0.5, size=k))
+    out = []
+    for _ in range(steps):
+        out.append(hostlib.hmm_params(pat, [0.0008, 0.0002, 15.0] + list(lam)))
+        lam = lam * np.exp(rng.normal(0.0, 0.03, size=k))   # an EM round moves the parameters a little
+    return out
+
+
+def library_part(hip, segs, n, steps, exact_steps):
+    ps = params_seq(n, steps)
+    r = {}
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=1)
+    es.load_segments(segs)
+    ms, rounds = [], []
+    for a, e, a0 in ps:
+        t = time.perf_counter(); es.estep_factored(a, e[:2], a0); ms.append((time.perf_counter() - t) * 1e3)
+        d = es.fast_diag()
+        rounds.append(dict(fwd_rounds=d["fwd_rounds"], bwd_rounds=d["bwd_rounds"], fwd_tiles=d["fwd_tiles"], bwd_tiles=d["bwd_tiles"]))
+    d = es.fast_diag()
+    r.update(tiles=d["n_chunks"], tile_len=d["tile_len"], warmup=d["warmup"], fast_ms=ms, fast_first_ms=ms[0],
+             fast_later_ms_mean=float(np.mean(ms[1:])), fast_later_ms_min=float(np.min(ms[1:])), repairs=rounds)
+    es.close()
+    print(json.dumps({"n%d" % n: r}), file=sys.stderr, flush=True)
+    if exact_steps > 0:
+        ex = hip.HipEStep(n, mode=hip.MODE_EXACT)
+        ex.load_segments(segs)
+        a, e, a0 = ps[0]
+        t = time.perf_counter(); ex.estep(a, e, a0); r["exact_first_ms"] = (time.perf_counter() - t) * 1e3
+        xs = []
+        for _ in range(exact_steps - 1):
+            t = time.perf_counter(); ex.estep(a, e, a0); xs.append((time.perf_counter() - t) * 1e3)
+        ex.close()
+        r["exact_ms"] = float(np.min(xs)) if xs else r["exact_first_ms"]
+        r["exact_over_fast"] = r["exact_ms"] / r["fast_later_ms_mean"]
+        print(json.dumps({"n%d" % n: {k: r[k] for k in ("exact_first_ms", "exact_ms", "exact_over_fast")}}), file=sys.stderr, flush=True)
+    return r
+
+
+def write_psmcfa(path, segs):
+    conv = np.frombuffer(b"TKN", dtype=np.uint8)
+    with open(path, "wb") as fh:
+        for i, s in enumerate(segs):
+            fh.write(b">%d\n" % (i + 1))
+            c = conv[s]
+            for j in range(0, len(c), 60):
+                fh.write(c[j:j + 60].tobytes() + b"\n")
+
+
+def cli_part(segs):
+    psmc = os.path.join(ROOT, "psmc_amd", "host", "psmc")
+    r = {}
+    with tempfile.TemporaryDirectory() as td:
+        fa = os.path.join(td, "genome.psmcfa")
+        write_psmcfa(fa, segs)
+        for name, env in (("fast_wide", dict(PSMC_HIP_MODE="fast", PSMC_HIP_WIDE="fast")), ("exact", dict())):
+            e = dict(os.environ); [e.pop(k, None) for k in ("PSMC_HIP_MODE", "PSMC_HIP_WIDE", "PSMC_HIP_DECODE", "PSMC_HIP_OPTIONS")]
+            e.update(env)
+            t = time.perf_counter()
+            p = subprocess.run([psmc, "-N5", "-t15", "-r5", "-p", "100*2", fa], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
+                               text=True, env=e, timeout=1100)
+            r[name + "_N5_s"] = time.perf_counter() - t
+            r[name + "_stderr"] = p.stderr.strip().splitlines()[:3]
+            if p.returncode != 0:
+                raise RuntimeError(p.stderr[-400:])
+            print(json.dumps({"cli": {name + "_N5_s": r[name + "_N5_s"]}}), file=sys.stderr, flush=True)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bins", type=int, default=30_000_000)
+    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--exact-steps", type=int, default=2)
+    ap.add_argument("--states", default="149,200,256")
+    ap.add_argument("--cli", action="store_true")
+    args = ap.parse_args()
+    from psmc_amd import hip, sim
+    g = np.load(os.path.join(ROOT, "tests", "golden", "hmm_params.npz"))
+    p64 = (g["n64_curve.a"], g["n64_curve.e"], g["n64_curve.a0"])
+    lens = sim.human_like_lengths(args.bins, n_seg=90)
+    t = time.perf_counter()
+    segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
+    out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
+    for n in [int(x) for x in args.states.split(",") if x]:
+        out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps)
+    if args.cli:
+        out["cli"] = cli_part(segs)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
