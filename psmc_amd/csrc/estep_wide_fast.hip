@@ -53,6 +53,25 @@ template <int NPL> __device__ __forceinline__ double lsum(const double (&x)[NPL]
 	for (int i = 1; i < NPL; ++i) t += x[i];
 	return t;
 }
+// sum over the wave of NPL values per lane, carried as an unevaluated pair (Knuth's two-sum at every addition, the error terms
+// added up beside): the rounded result is the exact sum's nearest double but for ties, the same bits in every lane
+__device__ __forceinline__ void two_sum(double a, double b, double &s, double &err) {
+	s = a + b;
+	const double bb = s - a;
+	err = (a - (s - bb)) + (b - bb);
+}
+template <int NPL> __device__ __forceinline__ double wave_total_comp(const double (&x)[NPL]) {
+	double h = x[0], l = 0.0, t;
+#pragma unroll
+	for (int i = 1; i < NPL; ++i) { two_sum(h, x[i], h, t); l += t; }
+#pragma unroll
+	for (int m = 1; m <= 32; m <<= 1) {
+		const double oh = __shfl_xor(h, m, 64), ol = __shfl_xor(l, m, 64);
+		two_sum(h, oh, h, t);
+		l = (l + ol) + t;
+	}
+	return h + l;
+}
 template <int NPL> __device__ __forceinline__ void ld(const double *p, double (&v)[NPL]) {
 #pragma unroll
 	for (int i = 0; i < NPL; ++i) v[i] = p[i];
@@ -407,7 +426,10 @@ __global__ __launch_bounds__(64) void k_wf_ll(const Chunk *__restrict__ chunks, 
 	}
 	if (c.hi == c.L) {
 		ld<NPL>(X + (c.off + c.L - 1) * S + k0, u);
-		ll += log(wave_total(lsum<NPL>(u)));
+		// a segment of one bin: LL is this logarithm alone, log sum_k a0[k] e[o_1][k], and the rounding of the sum is all its
+		// error (log at 0.93 magnifies one unit in the last place 14 times) -- add it up without one.  Longer segments keep
+		// the plain sum: their LL adds hundreds of logarithms, and the last unit of this one is far below what those leave.
+		ll += log(c.L == 1 ? wave_total_comp<NPL>(u) : wave_total(lsum<NPL>(u)));
 	}
 	if (lane == 0) LLpart[b] = ll * (double)c.mult;
 }

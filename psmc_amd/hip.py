@@ -291,6 +291,13 @@ class HipEStep:
         self._chk(self.lib.psmc_hip_estep_factored(self.h, _p(a), _p(e), _p(a0), _p(sums), _p(E), C.byref(LL)), "estep_factored")
         return dict(sums=sums, E=E, LL=LL.value)
 
+    def estep_factored_device(self, a, e, a0, d_stats_ptr, stream_ptr=0):
+        """estep_factored, asynchronous: [SL | SU | DG | CL | CU | E | LL] (7n + 1 doubles) into device memory on `stream`."""
+        a, e, a0 = self._params(a, e, a0)
+        self.lib.psmc_hip_estep_factored_device.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.psmc_hip_estep_factored_device(self.h, _p(a), _p(e), _p(a0), C.c_void_p(int(d_stats_ptr)),
+                                                          C.c_void_p(int(stream_ptr))), "estep_factored_device")
+
     def fast_diag(self):
         wf = C.c_double(0); wb = C.c_double(0); nc = C.c_int(0); wu = C.c_int(0)
         self._chk(self.lib.psmc_hip_fast_diag(self.h, C.byref(wf), C.byref(wb), C.byref(nc), C.byref(wu)), "fast_diag")

@@ -71,3 +71,96 @@ def test_structured_factorisation(golden):
     assert fastmodel.factor_structure(a) is None
     b = rng.random((64, 64)); b /= b.sum(1, keepdims=True)
     assert fastmodel.factor_structure(b) is None
+
+
+# ---------------------------------------------------------------------------------------------
+# The CPU side of tests/test_gpu_wide_fast_edges.py (the wide fast E-step, 129 .. 256 states).
+def test_factorisation_criterion_on_the_extreme_models():
+    """api.hip factor_structure restated in numpy (fastmodel.factor_structure: every off-diagonal entry to 64 ulp, both corner
+    entries above 1e-280, dd >= 0) on the models of part B at the four sizes and at 200 states: it refuses exactly the models
+    the GPU test lists as REFUSED -- at most a quarter of the list -- and for the reason the list gives; the others must run
+    on the device.  The same answer at every size."""
+    import test_gpu_wide_fast_edges as edges
+    assert 4 * len(edges.REFUSED) <= len(edges.MODELS) and set(edges.REFUSED) <= set(edges.MODELS)
+    assert not set(edges.HARSH) & set(edges.REFUSED)
+    for name in edges.MODELS:
+        for n in list(edges.SIZES) + [200]:
+            a, e, a0 = edges.model(name, n)
+            f = fastmodel.factor_structure(a)
+            assert (f is None) == (name in edges.REFUSED), (name, n)
+            if f is not None:
+                assert np.isfinite(a).all() and np.isfinite(e).all() and (a >= 0).all() and (a0 >= 0).all()
+                x = np.linspace(0.1, 1.0, n) ** 3
+                assert relmax(fastmodel.struct_step_forward(f, x), a.T @ x) < 1e-13
+                assert relmax(fastmodel.struct_step_backward(f, x), a @ x) < 1e-13
+            elif "corner" in edges.REFUSED[name]:
+                assert a[0, n - 1] == 0.0 and not a[n - 1, 0] > 1e-280, (name, n)
+            else:   # the off-diagonal entries do factor; the remainder of the diagonal is negative
+                assert fastmodel.factor_structure(a, ulps=1e30) is None and a.min() < 0, (name, n)
+                P, qa, R, c = a[:, 0].copy(), a[n - 1] / a[n - 1, 0], a[:, n - 1].copy(), a[0] / a[0, n - 1]
+                P[0] = R[n - 1] = 0.0; qa[n - 1] = c[0] = 0.0
+                assert (np.diag(a) - P * qa - R * c).min() < 0, (name, n)
+
+
+def test_untiled_matches_oracle_per_cell_at_200_states(golden, oracle):
+    """Before the per-vector gates of the wide fast path (tests/test_gpu_wide_fast.py gate_factored, FAST_TOL_CELL = 1e-9) are
+    relied on: the algorithm itself -- this file's numpy model, untiled, in double -- agrees with the oracle on every gated cell
+    of each of the seven vectors at least ten times tighter, on the inputs the GPU tests use: the golden parameters at 200 states
+    on the ragged segments and on the sets of the call sequence, and every accepted extreme model (at 200 states) on the data
+    of part B.  Observed: <= 4.2e-13 (rho0 = 1e-6, DG); an input that missed this would not be fit for the gate."""
+    import os
+    from conftest import GOLD
+    from psmc_amd.parity import factored_error_metrics, tri_sums, FACTORED_NAMES
+    import test_gpu_wide_fast_edges as edges
+    from test_gpu_wide_fast import FAST_TOL_CELL
+    w = dict(np.load(os.path.join(GOLD, "estep_wide.npz")))
+    gold = (w["n200.a"], w["n200.e"], w["n200.a0"])
+    cases = [("golden n200, ragged", gold, edges.ragged_segs(golden)), ("golden n200, sequence", gold, golden.segs_small + golden.segs_mid[4:])]
+    cases += [(name, edges.model(name, 200), edges.extremes_segs(golden)) for name in edges.MODELS if name not in edges.REFUSED]
+    worst = 0.0
+    for what, (a, e, a0), segs in cases:
+        o = oracle.estep(a, e, a0, segs)
+        m = fastmodel.estep_fast_model(a, e, a0, segs, T=1 << 30, W=0)
+        x = factored_error_metrics(dict(sums=tri_sums(m["A"]), E=m["E"], LL=m["LL"]), dict(sums=tri_sums(o["A"]), E=o["E"], LL=o["LL"]), a, e)
+        cell = max(x[v + "_cell"] for v in FACTORED_NAMES)
+        worst = max(worst, cell)
+        assert cell <= FAST_TOL_CELL / 10, (what, x)
+        assert max(x[v + "_l1"] for v in FACTORED_NAMES) <= 1e-11 and x["QA"] <= 1e-11 and x["QE"] <= 1e-11 and x["LL"] <= 1e-13, (what, x)
+    print("fastmodel vs oracle, worst gated cell: %.2e" % worst)
+
+
+def test_per_vector_gate_refuses_what_the_block_gate_accepts():
+    """An error injected into the reference, not the kernel: one cell of weight 1e-5 of its vector's largest, off by 1e-6
+    relative.  The block gate of tests/test_gpu_wide_fast.py before the per-vector gates (max |x - ref| / max |ref| < 1e-10 over
+    the whole of SL | SU | DG | CL | CU) accepts it; gate_factored must not -- in whichever of the seven vectors it sits."""
+    import conftest
+    from test_gpu_wide_fast import check, gate_factored, relmax as block, FAST_TOL_STATS, WORST
+    seen, worst = len(conftest.FAST_METRICS), dict(WORST)
+    try:
+        _inject_and_gate(check, gate_factored, block, FAST_TOL_STATS)
+    finally:   # the injected errors are not measurements: keep them out of the session's summary
+        del conftest.FAST_METRICS[seen:]
+        WORST.clear(); WORST.update(worst)
+
+
+def _inject_and_gate(check, gate_factored, block, FAST_TOL_STATS):
+    rng = np.random.default_rng(5)
+    n = 193
+    sums = np.exp(rng.normal(0.0, 2.0, size=(5, n))) * 1e3
+    sums[2] *= 50.0                                  # the diagonal counts dominate the block
+    E = np.exp(rng.normal(0.0, 2.0, size=(2, n))) * 1e3
+    r = dict(sums=sums.copy(), E=E.copy(), LL=-12345.678)
+    gate_factored(r, sums, E, r["LL"], "unperturbed")
+    for v in range(7):
+        rs, rE = sums.copy(), E.copy()
+        vec = rs[v] if v < 5 else rE[v - 5]
+        k = (0, n - 1, n // 2, 63 * 3, 64 * 3, 1, n - 2)[v]   # first, last, lane 63's first state, the state after it ...
+        vec[k] = 1e-5 * np.delete(vec, k).max()
+        ref = dict(sums=rs.copy(), E=rE.copy())
+        vec[k] *= 1.0 + 1e-6
+        bad = dict(sums=rs, E=rE, LL=r["LL"])
+        assert block(bad["sums"], ref["sums"]) < FAST_TOL_STATS and block(bad["E"], ref["E"]) < FAST_TOL_STATS   # the old gate: passes
+        with pytest.raises(AssertionError):
+            gate_factored(bad, ref["sums"], ref["E"], r["LL"], "perturbed cell %d of vector %d" % (k, v))
+        with pytest.raises(AssertionError):
+            check(bad, ref["sums"], ref["E"], r["LL"], "perturbed cell %d of vector %d" % (k, v))
