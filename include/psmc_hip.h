@@ -17,7 +17,8 @@
  * _estep_segments, _estep_batch, the table readers and the decoding entry points; the device-resident and factored fast entry
  * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 a fast-mode context of 129..256 states runs
  * psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip (PSMC-form matrices; full
- * counts, batch, tables and decoding stay exact);
+ * counts, batch and psmc_hip_get_tables stay exact, and so does decoding unless "wide_decode" = 1 is set as well: see
+ * "Decoding on a FAST context");
  * row-major FP64; a[k*n+l]=P(k->l) (khmm.h:34); e[b*n+k], b=0 hom / 1 het
  * (khmm.h:34; the missing-data row e[2][*]=1 of khmm.c:21 is implied);
  * a0[k] (khmm.h:36); observations are bytes 0/1/2 exactly as psmc_read_seq
@@ -79,8 +80,14 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           "max_rounds" and "learn" (1: a repair walks on through the failing tiles after it in the same round;
  *                           0: one tile per wave and round); with "structured" = 0 it answers ENOTSUP, as the factored statistics
  *                           do up to 128 states.  It keeps an X table of its own: 8 x 192 or 8 x 256 bytes per bin
- *                           (46 / 61 GB at 30 M bins), beside the exact tables.  psmc_hip_estep, the batch, the table readers and the
- *                           decoding entry points stay on the exact kernels, bit for bit.  Exact mode and <= 128 states: no effect
+ *                           (46 / 61 GB at 30 M bins), beside the exact tables.  psmc_hip_estep, the batch, psmc_hip_get_tables and
+ *                           (without "wide_decode") the decoding entry points stay on the exact kernels, bit for bit.  Exact mode and
+ *                           <= 128 states: no effect
+ *  "wide_decode"   0        1, with "wide_fast" = 1 on a fast-mode context of 129..256 states: psmc_hip_decode, _posterior, _post_counts
+ *                           and _scales read what the LAST single E-step left -- after a wide fast factored E-step its X table and
+ *                           converged tile boundaries (estep_wide_post.hip, no backward table), after psmc_hip_estep the exact tables,
+ *                           bit for bit (see "Decoding on a FAST context").  0: the exact tables whatever E-step ran last, as before
+ *                           the option existed.  Anywhere else: no effect
  *  "merge"         0        1: a forward FIX pass between the forward sweep and the back half (64 states, fused back half): every tile's start
  *                           vector is checked there, and a tile that fails is rewritten from the true vector until its trajectory has the
  *                           direction of the stored one again (the factor between the two parts is kept for the counts and the likelihood) --
@@ -321,8 +328,8 @@ int psmc_hip_posterior(psmc_hip_ctx *ctx, int seg, double *post, double *recomb)
 int psmc_hip_post_counts(psmc_hip_ctx *ctx, int seg, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt);
 
 /* The reference's scaling factors s[u] of one segment (hmm_forward, khmm.c:170-186; the PR line of -s, aux.c:159-164), L doubles.
- * Exact mode (and more than 128 states, and the exact fallback below): a copy of the table, the doubles psmc_hip_get_tables
- * returns as s.  Fast mode: s_u = sum X_u / sum X_{u-1} / inv_u from the fast forward table, X_{u-1} being a tile's own start
+ * Exact mode (and more than 128 states unless the wide fast tables are decoded, and the exact fallback below): a copy of the
+ * table, the doubles psmc_hip_get_tables returns as s.  Fast mode: s_u = sum X_u / sum X_{u-1} / inv_u from the fast forward table, X_{u-1} being a tile's own start
  * vector at its first position and s_1 = sum_k a0_k e_k(o_1); within 1e-11 relative of the exact value. */
 int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
 
@@ -338,7 +345,22 @@ int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
  *     kernels, the reference's doubles;
  *   - PSMC_HIP_ESTATE after the fused or the factored back half (no bt: set "fuse" / "fuse128" to 0 first), after a batch,
  *     or before any single E-step; PSMC_HIP_ENOTSUP after an E-step whose forward fix pass ran ("merge" = 1).
- * A decoding call reads the tables only: it changes nothing a later E-step uses (plan, glue, warm-ups). */
+ * A decoding call reads the tables only: it changes nothing a later E-step uses (plan, glue, warm-ups).
+ *
+ * 129..256 states, "wide_fast" = 1 and "wide_decode" = 1: the same rule -- the last single E-step decides.
+ *   - a wide fast factored E-step (psmc_hip_estep_factored / _estep_factored_device) that returned 0: one more backward sweep per
+ *     tile (estep_wide_post.hip) from the tile's converged start vector bt_{top+1}, reading X; no backward table exists or is
+ *     written.  With y = a bt_{p+1}:  gamma_p(k) = X_p(k) y(k) / G_p,  G_p = sum_k X_p(k) y(k)  (the posterior the E-step's E adds
+ *     up; no division by an emission);  recomb_p = 1 - sum_l X_p(l) a_ll bt_{p+1}(l) / G_p;  at p = L: gamma_L = X_L / sum X_L,
+ *     recomb_L = 0;  the path takes the lowest state among equal maxima;  s_p = sum X_p / sum X_{p-1} / inv_p with a tile's own
+ *     start vector for X_{lo-1}, s_1 = sum_k a0_k e_k(o_1);  post_counts adds per-tile partials in tile order.  Tolerances: the
+ *     ones above (1e-9 absolute, scales 1e-11 relative, counts 1e-9 relative, path equal away from near-ties of 2e-9);
+ *   - psmc_hip_estep (the wide exact kernels): the exact tables, the reference's doubles, as without the option;
+ *   - PSMC_HIP_ESTATE before any single E-step, after a batch, after a wide fast E-step that returned an error (ECONVERGE: its
+ *     boundaries are not converged), after psmc_hip_select / a reload since that E-step, or for a segment that was not in its
+ *     selection.
+ * With "wide_decode" = 0 such a context decodes from the exact tables whatever ran last (ESTATE when there are none).
+ * psmc_hip_get_tables always reads the exact tables. */
 
 /* ---- one E-step sharded over several GPUs of the node (replaces em.c:36-55 + the serial
  * hmm_add_expect of khmm.c:346-359 by per-device E-steps and ONE exchange per EM iteration).  One process; devices[]

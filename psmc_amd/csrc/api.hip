@@ -228,6 +228,7 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "overlap") c->overlap = v != 0 ? 1 : 0;
 	else if (k == "warm_tol") c->warm_tol = v;
 	else if (k == "wide_fast") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_fast = (int)v; }
+	else if (k == "wide_decode") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_decode = (int)v; }
 	else if (k == "rep_impl") c->rep_impl = v < 0 ? -1 : (v != 0 ? 1 : 0);
 	else return PSMC_HIP_EINVAL;
 	return PSMC_HIP_OK;
@@ -311,6 +312,7 @@ extern "C" int psmc_hip_select(psmc_hip_ctx *c, int n_sel, const int32_t *idx)
 	if ((rc = dev_alloc(c, &c->d_work, c->work.size()))) return rc;
 	HIPCHK(c, hipMemcpy(c->d_work, c->work.data(), sizeof(int32_t) * c->work.size(), hipMemcpyHostToDevice));
 	c->plan_dirty = true;
+	++c->sel_serial;
 	return PSMC_HIP_OK;
 }
 
@@ -695,9 +697,11 @@ extern "C" int psmc_hip_get_tables(psmc_hip_ctx *c, int seg, double *f, double *
 
 // Which tables the decoding entry points of context c read (the exact ones: exact mode, more than 128 states, or the exact
 // fallback of a fast E-step), and for the fast tables the segment's first tile in the plan of the E-step that wrote them.
-// Returns DEC_EXACT, DEC_FAST, or a PSMC_HIP_E* code (message set).  Reads nothing but the context.
-static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_tile)
+// Returns DEC_EXACT, DEC_FAST, DEC_WIDE (129..256 states, "wide_fast" + "wide_decode", the last single E-step was a wide fast one:
+// n_tiles = the segment's tiles in its plan), or a PSMC_HIP_E* code (message set).  Reads nothing but the context.
+static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_tile, int *n_tiles)
 {
+	if (c->mode == PSMC_HIP_MODE_FAST && c->ns > 128) return wide_decode_source(c, seg, who, first_tile, n_tiles);
 	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return DEC_EXACT;
 	char msg[256];
 	if (!c->d_f || c->tables_batch || c->dec_kind == DEC_NONE || c->dec_serial != c->tab_serial) {
@@ -727,9 +731,10 @@ static const double *par_re(const psmc_hip_ctx *c) { return c->ns == 128 ? c->d_
 extern "C" int psmc_hip_decode(psmc_hip_ctx *c, int seg, int32_t *path, double *maxp)
 {
 	if (!c || seg < 0 || seg >= c->n_seg || !path) return fail(c, PSMC_HIP_EINVAL, "decode: bad argument");
-	int first = 0;
-	const int src = decode_source(c, seg, "decode", &first);
+	int first = 0, n_wide = 0;
+	const int src = decode_source(c, seg, "decode", &first, &n_wide);
 	if (src < 0) return src;
+	if (src == DEC_WIDE) return wide_decode(c, seg, first, n_wide, path, maxp);
 	if (src == DEC_FAST) {
 		HIPCHK(c, hipSetDevice(c->device));
 		const int L = c->L[seg];
@@ -763,9 +768,10 @@ extern "C" int psmc_hip_decode(psmc_hip_ctx *c, int seg, int32_t *path, double *
 extern "C" int psmc_hip_posterior(psmc_hip_ctx *c, int seg, double *post, double *recomb)
 {
 	if (!c || seg < 0 || seg >= c->n_seg || (!post && !recomb)) return fail(c, PSMC_HIP_EINVAL, "posterior: bad argument");
-	int first = 0;
-	const int src = decode_source(c, seg, "posterior", &first);
+	int first = 0, n_wide = 0;
+	const int src = decode_source(c, seg, "posterior", &first, &n_wide);
 	if (src < 0) return src;
+	if (src == DEC_WIDE) return wide_posterior(c, seg, first, n_wide, post, recomb);
 	if (src == DEC_FAST) {
 		HIPCHK(c, hipSetDevice(c->device));
 		const int L = c->L[seg], n = c->n;
@@ -802,9 +808,10 @@ extern "C" int psmc_hip_posterior(psmc_hip_ctx *c, int seg, double *post, double
 extern "C" int psmc_hip_post_counts(psmc_hip_ctx *c, int seg, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt)
 {
 	if (!c || seg < 0 || seg >= c->n_seg || !cnt || l < 0 || n_cnt < 1 || (l > 0 && !cnt1)) return fail(c, PSMC_HIP_EINVAL, "post_counts: bad argument");
-	int first = 0;
-	const int src = decode_source(c, seg, "post_counts", &first);
+	int first = 0, n_wide = 0;
+	const int src = decode_source(c, seg, "post_counts", &first, &n_wide);
 	if (src < 0) return src;
+	if (src == DEC_WIDE) return wide_post_counts(c, seg, first, n_wide, cnt1, l, n_cnt, cnt);
 	if (src == DEC_FAST) {
 		HIPCHK(c, hipSetDevice(c->device));
 		const int L = c->L[seg], n = c->n, min_l = L < l ? L : l;
@@ -844,9 +851,10 @@ extern "C" int psmc_hip_post_counts(psmc_hip_ctx *c, int seg, const int32_t *cnt
 extern "C" int psmc_hip_scales(psmc_hip_ctx *c, int seg, double *s)
 {
 	if (!c || seg < 0 || seg >= c->n_seg || !s) return fail(c, PSMC_HIP_EINVAL, "scales: bad argument");
-	int first = 0;
-	const int src = decode_source(c, seg, "scales", &first);
+	int first = 0, n_wide = 0;
+	const int src = decode_source(c, seg, "scales", &first, &n_wide);
 	if (src < 0) return src;
+	if (src == DEC_WIDE) return wide_scales(c, seg, first, n_wide, s);
 	if (!c->d_f || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "scales: no single E-step yet");
 	HIPCHK(c, hipSetDevice(c->device));
 	const int L = c->L[seg];

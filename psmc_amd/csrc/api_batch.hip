@@ -614,6 +614,7 @@ extern "C" int psmc_hip_estep_batch_cb(psmc_hip_ctx *c, int n_rep, const double 
 	if (c->parent) return fail(c, PSMC_HIP_EINVAL, "estep_batch: not on a replicate context");
 	if (c->n_seg < 1) return fail(c, PSMC_HIP_ESTATE, "estep_batch: no segments loaded");
 	HIPCHK(c, hipSetDevice(c->device));
+	c->wd_kind = WD_NONE; // (decoding after a batch needs a single E-step first, on the wide fast path as everywhere)
 	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return batch_exact(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user); // (beyond 128 states: the wide exact kernels whatever the mode)
 	return batch_fast(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user);
 }

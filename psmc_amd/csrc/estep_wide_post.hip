@@ -1,0 +1,200 @@
+// estep_wide_post.hip -- decoding on the wide fast path (129..256 states, options "wide_fast" + "wide_decode"; api_wide_fast.hip
+// drives it): psmc_hip_decode / _posterior / _post_counts / _scales from what the last wide fast E-step left, without a backward table.
+//
+// The E-step keeps the lag-normalised forward table X (and 1/d_p at p % 4 == 0), every tile's forward start vector `entry` and its
+// backward start vector bentry = bt_{top+1}, converged to "warm_tol" by the verify / repair rounds.  One more backward sweep per
+// tile from bentry -- the steps of k_wf_acc, so the bt of the E-step -- gives at every position p, with y = a bt_{p+1} (O(N)),
+//   g_p(k) = X_p(k) y(k),  G_p = sum_k g_p(k):  posterior gamma_p(k) = g_p(k) / G_p  (what E0 / E1 of the E-step add up; no division
+//            by an emission, so zero emissions and padded states are no special case),
+//   recomb_p = 1 - sum_l X_p(l) a_ll bt_{p+1}(l) / G_p  (aux.c:189-193),  and at p = L: gamma_L = X_L / sum X_L, recomb_L = 0.
+// One wave per tile, 64 lanes x NPL adjacent states as in estep_wide_fast.hip (wide_prims.h).  Nothing of 8 S bytes per bin is
+// written: only what was asked for (template flags) -- -d moves 12 bytes per bin.  Posterior rows have stride n; padded states
+// are never written, and a tile writes the positions lo .. hi it owns and nothing else.
+//   k_wp_dec     the sweep: posterior rows | recombination | argmax (lowest state wins a tie) and its value | per-tile partial
+//                posterior-weighted counts, CB count columns per sweep
+//   k_wp_cnt_add the tiles' partials added in tile order (deterministic)
+//   k_wp_scales  s_p = sum X_p / sum X_{p-1} / inv_p from X alone (X_{lo-1}: the tile's own `entry`), s_1 = sum_k a0_k e_k(o_1)
+#include <hip/hip_runtime.h>
+#include "wide_fast.h"
+#include "wide_prims.h"
+
+namespace psmc {
+namespace wide {
+
+constexpr int CB = 4; // count columns one sweep of k_wp_dec carries (CB x NPL accumulators per lane)
+
+// what one position hands out: g = unnormalised posterior of the lane's states, G = its sum over the wave, r = sum_l X a_ll bt_{p+1}
+// (last: position L, whose recombination probability is 0)
+template <int NPL, bool POST, bool REC, bool PATH, bool CNT>
+__device__ __forceinline__ void emit(int p, int lane, int n, const double (&g)[NPL], double G, double r, bool last, double *__restrict__ post,
+                                     double *__restrict__ recomb, int32_t *__restrict__ path, double *__restrict__ maxp,
+                                     const int32_t *__restrict__ cnt1, int n_cnt, int j0, int min_l, double (&acc)[CB][NPL])
+{
+	const int k0 = NPL * lane;
+	const double iG = rcp_newton(G);
+	if (POST) {
+		double *row = post + (int64_t)(p - 1) * n;
+#pragma unroll
+		for (int i = 0; i < NPL; ++i)
+			if (k0 + i < n) row[k0 + i] = g[i] * iG;
+	}
+	if (REC && lane == 0) recomb[p - 1] = last ? 0.0 : 1.0 - r * iG;
+	if (PATH) { // the first maximum: the lowest i of the lane, then the lowest lane that holds the wave's maximum
+		double best = g[0]; int arg = 0;
+#pragma unroll
+		for (int i = 1; i < NPL; ++i)
+			if (g[i] > best) { best = g[i]; arg = i; }
+		const double top = wave_maxv(best);
+		const unsigned long long who = __ballot(best == top);
+		const int src = who ? __ffsll((long long)who) - 1 : 0;
+		const int k = __shfl(k0 + arg, src, 64);
+		if (lane == 0) { path[p - 1] = k; maxp[p - 1] = top * iG; }
+	}
+	if (CNT && p <= min_l) {
+		const int32_t *c1 = cnt1 + (int64_t)(p - 1) * n_cnt + j0;
+#pragma unroll
+		for (int j = 0; j < CB; ++j) {
+			const double w = j0 + j < n_cnt ? (double)c1[j] : 0.0;
+#pragma unroll
+			for (int i = 0; i < NPL; ++i) acc[j][i] = __builtin_fma(g[i] * iG, w, acc[j][i]);
+		}
+	}
+}
+
+// Tile t0 + blockIdx.x of the plan (the tiles of one segment are consecutive).  Output pointers are the SEGMENT's (position 1 first).
+// CNT: part[(blockIdx.x * n_cnt + j) * S + k] for the columns j0 .. j0 + CB - 1 that exist.
+template <int NPL, bool POST, bool REC, bool PATH, bool CNT>
+__global__ __launch_bounds__(64) void k_wp_dec(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                 const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
+                                                 const double *__restrict__ bentry, int n, double *__restrict__ post,
+                                                 double *__restrict__ recomb, int32_t *__restrict__ path, double *__restrict__ maxp,
+                                                 const int32_t *__restrict__ cnt1, int n_cnt, int j0, int min_l, double *__restrict__ part)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
+	const WaveScanMasks wm = wave_scan_masks(lane);
+	const Chunk c = chunks[b];
+	const int lo = c.lo, top = min(c.hi, c.L - 1);
+	StructParN<NPL> sc;
+	load_par<NPL>(par, k0, false, sc);
+	double e0[NPL], e1[NPL], akk[NPL], acc[CB][NPL];
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) akk[i] = sc.dd[i] + sc.wP[i] * sc.mP[i] + sc.wS[i] * sc.mS[i]; // a[k][k]
+#pragma unroll
+	for (int j = 0; j < CB; ++j)
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) acc[j][i] = 0.0;
+	const uint8_t *o = obs + c.off;
+	const double *fo = X + c.off * S + k0;
+	if (c.hi == c.L) { // position L: beta_L = 1
+		double g[NPL];
+		ld<NPL>(fo + (int64_t)(c.L - 1) * S, g);
+		emit<NPL, POST, REC, PATH, CNT>(c.L, lane, n, g, wave_total(lsum<NPL>(g)), 0.0, true, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc);
+	}
+	if (top >= lo) {
+		double x[NPL], Xc[NPL], Xn[NPL];
+		ld<NPL>(bentry + (int64_t)b * S + k0, x);
+		ld<NPL>(fo + (int64_t)(top - 1) * S, Xc);
+		for (int g4 = (top - 1) >> 2; g4 >= 0 && 4 * g4 + 4 >= lo; --g4) {
+			const unsigned w = *reinterpret_cast<const unsigned *>(o + 4 * (int64_t)g4);
+#pragma unroll
+			for (int j = 3; j >= 0; --j) {
+				const int p = 4 * g4 + j + 1;
+				if (p > top || p < lo) continue;
+				if (p > lo) ld<NPL>(fo + (int64_t)(p - 2) * S, Xn); // X_{p-1}, for the next step
+				double ev[NPL], y[NPL], g[NPL];
+				emis<NPL>((int)((w >> (8 * j)) & 3u), e0, e1, ev);
+				if (j == 3) { // p % 4 == 0: the backward sweep's own scaling, as bstep
+					const double sb = rcp_newton(wave_total(lsum<NPL>(x)));
+#pragma unroll
+					for (int i = 0; i < NPL; ++i) ev[i] *= sb;
+				}
+				double r = 0.0;
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) {
+					y[i] = x[i];
+					if (REC) r = __builtin_fma(Xc[i] * akk[i], x[i], r);
+				}
+				wstep<NPL>(sc, y, wm); // (a bt_{p+1})
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) { g[i] = Xc[i] * y[i]; x[i] = y[i] * ev[i]; }
+				if (REC) r = wave_total(r);
+				emit<NPL, POST, REC, PATH, CNT>(p, lane, n, g, wave_total(lsum<NPL>(g)), r, false, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc);
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) Xc[i] = Xn[i];
+			}
+		}
+	}
+	if (CNT) {
+#pragma unroll
+		for (int j = 0; j < CB; ++j)
+			if (j0 + j < n_cnt) st<NPL>(part + ((int64_t)blockIdx.x * n_cnt + j0 + j) * S + k0, acc[j]);
+	}
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_wp_cnt_add(const double *__restrict__ part, int n_tiles, int n_cnt, int n, double *__restrict__ cnt)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n * n_cnt) return;
+	const int k = i / n_cnt, j = i % n_cnt;
+	double t = 0.0;
+	for (int q = 0; q < n_tiles; ++q) t += part[((int64_t)q * n_cnt + j) * S + k];
+	cnt[i] += t;
+}
+
+template <int NPL>
+__global__ __launch_bounds__(64) void k_wp_scales(const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
+                                                    const double *__restrict__ inv, const double *__restrict__ entry, double *__restrict__ s)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
+	const Chunk c = chunks[b];
+	const double *fo = X + c.off * S + k0, *io = inv + c.off;
+	double u[NPL], prev = 1.0;
+	if (c.lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, u); prev = wave_total(lsum<NPL>(u)); }
+	for (int p = c.lo; p <= c.hi; ++p) {
+		ld<NPL>(fo + (int64_t)(p - 1) * S, u);
+		const double cur = wave_total(lsum<NPL>(u));
+		double v = p == 1 ? cur : cur / prev; // X_1 = a0 e[o_1] as it stands
+		if (p > 1 && (p & (NORM_EVERY - 1)) == 0) v /= io[p - 1];
+		if (lane == 0) s[p - 1] = v;
+		prev = cur;
+	}
+}
+
+template <int NPL> static int launch_post(const WidePost &w)
+{
+	constexpr int S = 64 * NPL;
+	const dim3 grid(w.n_tiles), blk(64);
+	hipStream_t st = w.stream;
+#define WP_DEC(POST, REC, PATH, CNT, j0) \
+	hipLaunchKernelGGL((k_wp_dec<NPL, POST, REC, PATH, CNT>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.bentry, w.n_states, \
+	                   w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part)
+	switch (w.what) {
+	case WP_PATH: WP_DEC(false, false, true, false, 0); break;
+	case WP_POST: WP_DEC(true, false, false, false, 0); break;
+	case WP_REC: WP_DEC(false, true, false, false, 0); break;
+	case WP_POST_REC: WP_DEC(true, true, false, false, 0); break;
+	case WP_COUNTS:
+		for (int j0 = 0; j0 < w.n_cnt; j0 += CB) WP_DEC(false, false, false, true, j0);
+		hipLaunchKernelGGL(k_wp_cnt_add<S>, dim3((w.n_states * w.n_cnt + 255) / 256), dim3(256), 0, st, w.part, w.n_tiles, w.n_cnt, w.n_states, w.cnt);
+		break;
+	case WP_SCALES: hipLaunchKernelGGL(k_wp_scales<NPL>, grid, blk, 0, st, w.chunks, w.t0, w.X, w.inv, w.entry, w.s); break;
+	default: return -1;
+	}
+#undef WP_DEC
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+} // namespace wide
+
+int launch_wide_post(const WidePost &w)
+{
+	if (w.ns == 192) return wide::launch_post<3>(w);
+	if (w.ns == 256) return wide::launch_post<4>(w);
+	return -1;
+}
+
+} // namespace psmc

@@ -29,6 +29,11 @@ constexpr int DEC_FAST = 1;   // the fast tables X and bt (dense sweeps, or the 
 constexpr int DEC_EXACT = 2;  // the exact tables (65..128 states, a matrix without the PSMC form: fast mode ran the exact kernels)
 constexpr int DEC_NO_BT = 3;  // the fused or factored back half: no backward table
 constexpr int DEC_MERGED = 4; // the forward fix pass ("merge"): its X carries per-tile factors
+constexpr int DEC_WIDE = 5;   // decode_source only: the tables of the wide fast path (129..256 states, "wide_decode"): estep_wide_post.hip
+// psmc_hip_ctx::wd_kind: what the last wide fast E-step of the context left (api_wide_fast.hip)
+constexpr int WD_NONE = 0;    // there was none, or a batch came after it
+constexpr int WD_OK = 1;      // X, 1/d, entry and a converged bentry of every tile of its plan
+constexpr int WD_FAILED = 2;  // it returned an error: bentry is not converged
 
 struct psmc_hip_ctx {
 	int n = 0, ns = 64, device = 0, mode = PSMC_HIP_MODE_EXACT; // ns: states padded to 64 or 128
@@ -221,6 +226,11 @@ struct psmc_hip_ctx {
 	double *d_wf_par = nullptr, *h_wf_par = nullptr;                     // e0 | e1 | a0 | P | R | qa | c | dd
 	double *d_wf_entry = nullptr, *d_wf_bentry = nullptr, *d_wf_bexit = nullptr, *d_wf_part = nullptr, *d_wf_ll = nullptr;
 	int *d_wf_dirty = nullptr, *d_wf_list = nullptr;
+	// "wide_decode" = 1 (with "wide_fast"): the decoding entry points of such a context read the tables of the wide path when the last
+	// single E-step was one of its own.  wd_serial: the table serial at that E-step -- an exact E-step or a batch moves tab_serial on,
+	// and the exact tables are the newer ones; wd_sel: the selection serial it ran with (psmc_hip_select moves sel_serial on)
+	int wide_decode = 0;
+	int wd_kind = 0; unsigned long long wd_serial = 0, wd_sel = 0, sel_serial = 0;
 };
 inline double dbg_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline psmc_hip_ctx *dbg_root(psmc_hip_ctx *c) { return c->parent ? c->parent : c; }
@@ -278,4 +288,9 @@ bool factor_structure(int n, int S, const double *a, double *sp);               
 void free_wide_fast(psmc_hip_ctx *c);                                                                       // api_wide_fast.hip
 int  estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t st); // api_wide_fast.hip
 int  estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *sums, double *E, double *LL); // api_wide_fast.hip
+int  wide_decode_source(psmc_hip_ctx *c, int seg, const char *who, int *t0, int *n_tiles);                  // api_wide_fast.hip: DEC_WIDE, DEC_EXACT or an error
+int  wide_decode(psmc_hip_ctx *c, int seg, int t0, int nt, int32_t *path, double *maxp);                   // api_wide_fast.hip
+int  wide_posterior(psmc_hip_ctx *c, int seg, int t0, int nt, double *post, double *recomb);               // api_wide_fast.hip
+int  wide_post_counts(psmc_hip_ctx *c, int seg, int t0, int nt, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt); // api_wide_fast.hip
+int  wide_scales(psmc_hip_ctx *c, int seg, int t0, int nt, double *s);                                     // api_wide_fast.hip
 int  estep_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *A, double *E, double *A0, double *LL, double *chk); // api_fast.hip

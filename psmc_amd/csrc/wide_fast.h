@@ -1,4 +1,5 @@
-// wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states).
+// wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states)
+// and of estep_wide_post.hip (decoding from the tables that E-step left).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "psmc_hip_internal.h"
@@ -21,5 +22,24 @@ struct WideLaunch {
 };
 
 int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip
+
+// decoding of ONE segment: its tiles are t0 .. t0 + n_tiles - 1 of the plan; every output pointer is the segment's own buffer
+enum { WP_PATH, WP_POST, WP_REC, WP_POST_REC, WP_COUNTS, WP_SCALES };
+
+struct WidePost {
+	hipStream_t stream;
+	int what, ns, n_states, t0, n_tiles;
+	const double *par;                // as WideLaunch
+	const uint8_t *obs;
+	const Chunk *chunks;
+	const double *X, *inv, *entry, *bentry;
+	double *post, *recomb, *maxp, *s; // [L][n_states] | [L] | [L] | [L]
+	int32_t *path;                    // [L]
+	const int32_t *cnt1;              // WP_COUNTS: [min_l][n_cnt]
+	int n_cnt, min_l;
+	double *part, *cnt;               // [n_tiles][n_cnt][ns] per-tile partials; [n_states][n_cnt] running totals (in / out)
+};
+
+int launch_wide_post(const WidePost &w); // estep_wide_post.hip
 
 } // namespace psmc

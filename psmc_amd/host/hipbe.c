@@ -14,6 +14,8 @@ typedef struct {
 	psmc_hip_ctx *x_ctx; psmc_hip_group *x_grp; int n_fallbacks;
 	/* decoding (prepare_decode): the parameters of the last E-step, and whether the exact twin holds its tables */
 	int decoding, on_twin; double *pa, *pe, *pa0;
+	/* the wide fast path is on ("wide_fast" went through psmc_hipbe_set_option) / its tables are what the decoding reads ("wide_decode") */
+	int wide, wide_decode;
 } hip_be;
 
 /* the per-segment readers go to the context that holds the segment's tables: the exact twin's after a fallback */
@@ -98,7 +100,22 @@ static int hb_estep(void *self, const double *a, const double *e, const double *
 		memcpy(h->pa, a, sizeof(double) * n * n); memcpy(h->pe, e, sizeof(double) * 2 * n); memcpy(h->pa0, a0, sizeof(double) * n);
 	}
 	h->on_twin = 0;
-	int rc = h->grp ? psmc_hip_group_estep(h->grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->ctx, a, e, a0, A, E, 0, LL, h->chk);
+	int rc;
+	if (h->decoding && h->wide_decode) {
+		/* the decoding E-step of the wide fast path: psmc_hip_estep would run the exact full-counts kernels beyond 128 states, and the
+		 * decoding reads what the last single E-step left -- so the FACTORED wide E-step runs; decode_all reads neither A nor E */
+		const size_t n = (size_t)h->n_states;
+		double *sums = (double *)malloc(sizeof(double) * 5 * n);
+		if (!sums) return PSMC_HIP_ENOMEM;
+		memset(A, 0, sizeof(double) * n * n);
+		rc = h->grp ? psmc_hip_group_estep_factored(h->grp, a, e, a0, sums, E, LL) : psmc_hip_estep_factored(h->ctx, a, e, a0, sums, E, LL);
+		free(sums);
+		for (int i = 0; i < h->n_seg; ++i) h->chk[i] = 1.0; /* (fast mode has no underflow self-check) */
+		if (rc == PSMC_HIP_ENOTSUP) { /* "structured" = 0, a matrix without the PSMC form (-C): nothing of the wide path to decode */
+			fprintf(stderr, "psmc: the wide fast E-step cannot run (%s); repeating the decoding E-step with the exact kernels\n", hb_error(h));
+			rc = exact_once(h, a, e, a0, A, E, LL, 1);
+		}
+	} else rc = h->grp ? psmc_hip_group_estep(h->grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->ctx, a, e, a0, A, E, 0, LL, h->chk);
 	if (rc == PSMC_HIP_ECONVERGE && h->mode == PSMC_HIP_MODE_FAST) rc = exact_once(h, a, e, a0, A, E, LL, 0);
 	if (rc) return rc;
 	for (int i = 0; i < h->n_seg; ++i) { /* the diagnostic of khmm.c:239-240 */
@@ -128,12 +145,18 @@ static int hb_tables(void *self, int seg, double *f, double *b, double *s)
 	psmc_hip_ctx *c; int l; int rc = route((hip_be *)self, seg, &c, &l);
 	return rc ? rc : psmc_hip_get_tables(c, l, f, b, s);
 }
-/* PSMC_HIP_DECODE=fast: the decoding E-step keeps the backward table (the fused and factored back halves never store it) */
+/* PSMC_HIP_DECODE=fast: the decoding E-step keeps the backward table (the fused and factored back halves never store it); on the
+ * wide fast path (129..256 states) it is a factored wide E-step (hb_estep) and the decoding reads its tables ("wide_decode") */
 static int hb_prepare_decode(void *self)
 {
 	hip_be *h = (hip_be *)self;
 	if (h->mode != PSMC_HIP_MODE_FAST) return 0;
 	h->decoding = 1;
+	if (h->wide) {
+		const int rc = h->grp ? psmc_hip_group_set_option(h->grp, "wide_decode", 1) : psmc_hip_set_option(h->ctx, "wide_decode", 1);
+		if (rc) return rc;
+		h->wide_decode = 1;
+	}
 	int rc = h->grp ? psmc_hip_group_set_option(h->grp, "fuse", 0) : psmc_hip_set_option(h->ctx, "fuse", 0);
 	if (rc == 0) rc = h->grp ? psmc_hip_group_set_option(h->grp, "fuse128", 0) : psmc_hip_set_option(h->ctx, "fuse128", 0);
 	return rc;
@@ -213,6 +236,7 @@ int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_fa
 int psmc_hipbe_set_option(psmc_estep_backend *be, const char *key, double value)
 {
 	hip_be *h = (hip_be *)be->self;
+	if (strcmp(key, "wide_fast") == 0) h->wide = value != 0;
 	return h->grp ? psmc_hip_group_set_option(h->grp, key, value) : psmc_hip_set_option(h->ctx, key, value);
 }
 

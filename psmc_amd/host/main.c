@@ -5,7 +5,9 @@
  *   PSMC_HIP_DECODE=fast             with PSMC_HIP_MODE=fast and -d/-D/-c/-s: stay in fast mode and decode from the fast
  *                                    tables (without it such a run is an exact run throughout)
  *   PSMC_HIP_WIDE=fast               with PSMC_HIP_MODE=fast and 129..256 states: factored fast E-steps on the wide fast path
- *                                    (option "wide_fast"); without it, or with -d/-D/-c/-s, such a run is an exact run throughout
+ *                                    (option "wide_fast"); without it such a run is an exact run throughout, and so it is with
+ *                                    -d/-D/-c/-s unless PSMC_HIP_DECODE=fast is set too: the EM rounds then stay on the wide fast
+ *                                    path and the decoding reads its tables (option "wide_decode")
  *   PSMC_HIP_DEVICE=<index>          one GPU
  *   PSMC_HIP_DEVICES=<i>,<j>,...     the segments of every E-step sharded over these GPUs (psmc_hip_group_*: LPT
  *                                    partition, one RCCL all-reduce of the statistics per EM iteration in fast mode,
@@ -44,15 +46,18 @@ int main(int argc, char *argv[])
 		psmc_options_free(&o);
 		return 2;
 	}
-	/* PSMC_HIP_WIDE=fast: the factored E-step of 129..256 states on the fast kernels (not with decoding: that needs the exact tables) */
-	const char *wide_s = getenv("PSMC_HIP_WIDE");
-	const int wide_fast = wide_s && strcmp(wide_s, "fast") == 0 && mode_is_fast() && n_states > 128 && n_states <= 256 &&
-	                      !(o.decode || o.print_prob || o.cnt_file);
+	/* PSMC_HIP_WIDE=fast: the factored E-step of 129..256 states on the fast kernels (with decoding: only when PSMC_HIP_DECODE=fast
+	 * lets the decoding read that path's tables; otherwise it needs the exact ones) */
+	const char *wide_s = getenv("PSMC_HIP_WIDE"), *dec_s = getenv("PSMC_HIP_DECODE");
+	const int decoding = o.decode || o.print_prob || o.cnt_file;
+	const int plan = psmc_mode_plan(mode_is_fast(), wide_s && strcmp(wide_s, "fast") == 0, dec_s && strcmp(dec_s, "fast") == 0, n_states, decoding);
+	const int wide_fast = (plan & PSMC_PLAN_WIDE) != 0;
 	const char *mode_s = getenv("PSMC_HIP_MODE"), *dev_s = getenv("PSMC_HIP_DEVICE");
 	int mode = (mode_s && strcmp(mode_s, "fast") == 0) ? PSMC_HIP_MODE_FAST : PSMC_HIP_MODE_EXACT;
-	if ((o.decode || o.print_prob || o.cnt_file) && mode == PSMC_HIP_MODE_FAST) {
-		const char *dec_s = getenv("PSMC_HIP_DECODE");
-		if (dec_s && strcmp(dec_s, "fast") == 0) /* opt-in: decode from the fast E-step's tables (include/psmc_hip.h: tolerances) */
+	if (decoding && mode == PSMC_HIP_MODE_FAST) {
+		if (plan & PSMC_PLAN_WIDE_DECODE) /* (said below, once it is known that the factored E-step runs) */
+			;
+		else if (plan & PSMC_PLAN_FAST) /* opt-in: decode from the fast E-step's tables (include/psmc_hip.h: tolerances) */
 			fprintf(stderr, "psmc: PSMC_HIP_DECODE=fast: fast E-steps throughout; the decoding reads the fast forward/backward tables\n");
 		else {
 			fprintf(stderr, "psmc: decoding needs the exact forward/backward tables; using PSMC_HIP_MODE=exact\n");
@@ -67,7 +72,9 @@ int main(int argc, char *argv[])
 	const char *fs = getenv("PSMC_FACTORED"), *devs = getenv("PSMC_HIP_DEVICES");
 	const int use_factored = o.fast_mstep && mode == PSMC_HIP_MODE_FAST && (n_states <= 128 || wide_fast) && !(fs && atoi(fs) == 0);
 	/* (PSMC_FACTORED=0 or PSMC_FAST_MSTEP=0 ask for full counts, which beyond 128 states only the exact kernels compute) */
-	if (wide_fast && use_factored)
+	if (wide_fast && use_factored && (plan & PSMC_PLAN_WIDE_DECODE))
+		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=fast PSMC_HIP_DECODE=fast: factored E-steps on the wide fast kernels; the decoding reads the wide fast tables\n", n_states);
+	else if (wide_fast && use_factored)
 		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=fast: factored E-steps on the wide fast kernels (full counts and decoding stay exact)\n", n_states);
 	else if (n_states > 128 && mode_is_fast())
 		fprintf(stderr, "psmc: %d hidden states: the fast kernels stop at 128, every E-step of this run uses the exact ones\n", n_states);

@@ -8,6 +8,11 @@
   (b) ms per E-step of the wide exact kernels (psmc_hip_estep) on the same input and the first parameters (one step after a
       warm-up of the allocations)
   (c) with --cli: wall clock of `psmc -N5 -p "100*2"` on the genome in exact mode and with PSMC_HIP_MODE=fast PSMC_HIP_WIDE=fast
+  (d) with --decode: decoding from the wide fast tables ("wide_decode", estep_wide_post.hip) -- after a warm-up pass, --repeats
+      passes of each decoding call over ALL segments (decode = -d, recombination only and posterior rows + recombination = -D,
+      post_counts with three columns = -c, scales = -s; the posterior rows of the longest segment only unless --full-post: all
+      of them are 8 n bytes per bin to the host), min | median | max in ms; and what the same request costs without the option:
+      one exact E-step (full counts) + the same calls on the exact tables, once
 
 Library calls are synchronous.  Writes one JSON object to stdout (progress on stderr).
 
@@ -71,6 +76,54 @@ def library_part(hip, segs, n, steps, exact_steps):
     return r
 
 
+def _spread(xs):
+    return dict(min=float(np.min(xs)), median=float(np.median(xs)), max=float(np.max(xs)))
+
+
+def decode_calls(es, segs, n, full_post):
+    """one pass of every decoding call over all segments: seconds per kind"""
+    longest = int(np.argmax([len(s) for s in segs]))
+    c1 = [np.ones((len(s), 3), np.int32) for s in segs]
+    cnt = np.zeros((n, 3))
+    out = {}
+    for name, f in (("decode", lambda i: es.decode(i)), ("recomb", lambda i: es.posterior(i, want_post=False)),
+                    ("scales", lambda i: es.scales(i)), ("post_counts", lambda i: es.post_counts(i, c1[i], cnt))):
+        t = time.perf_counter()
+        for i in range(len(segs)):
+            f(i)
+        out[name] = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter()
+    for i in (range(len(segs)) if full_post else [longest]):
+        es.posterior(i)
+    out["posterior_all" if full_post else "posterior_longest"] = (time.perf_counter() - t) * 1e3
+    return out
+
+
+def decode_part(hip, segs, n, repeats, full_post, exact):
+    a, e, a0 = params_seq(n, 1)[0]
+    r = {"longest_segment_bins": int(max(len(s) for s in segs))}
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=1, wide_decode=1)
+    es.load_segments(segs)
+    es.estep_factored(a, e[:2], a0)
+    ms = []
+    for _ in range(3):
+        t = time.perf_counter(); es.estep_factored(a, e[:2], a0); ms.append((time.perf_counter() - t) * 1e3)
+    r["wide_estep_ms"] = _spread(ms)
+    decode_calls(es, segs, n, full_post)   # warm-up
+    passes = [decode_calls(es, segs, n, full_post) for _ in range(repeats)]
+    r["wide_decode_ms"] = {k: _spread([p[k] for p in passes]) for k in passes[0]}
+    es.close()
+    print(json.dumps({"n%d" % n: r}), file=sys.stderr, flush=True)
+    if exact:
+        ex = hip.HipEStep(n, mode=hip.MODE_EXACT)
+        ex.load_segments(segs)
+        t = time.perf_counter(); ex.estep(a, e, a0); r["exact_estep_ms"] = (time.perf_counter() - t) * 1e3
+        r["exact_decode_ms"] = decode_calls(ex, segs, n, full_post)
+        ex.close()
+        print(json.dumps({"n%d" % n: {k: r[k] for k in ("exact_estep_ms", "exact_decode_ms")}}), file=sys.stderr, flush=True)
+    return r
+
+
 def write_psmcfa(path, segs):
     conv = np.frombuffer(b"TKN", dtype=np.uint8)
     with open(path, "wb") as fh:
@@ -108,6 +161,9 @@ def main():
     ap.add_argument("--exact-steps", type=int, default=2)
     ap.add_argument("--states", default="149,200,256")
     ap.add_argument("--cli", action="store_true")
+    ap.add_argument("--decode", action="store_true", help="time the decoding calls on the wide fast tables (and on the exact ones) instead of (a), (b)")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--full-post", action="store_true")
     args = ap.parse_args()
     from psmc_amd import hip, sim
     g = np.load(os.path.join(ROOT, "tests", "golden", "hmm_params.npz"))
@@ -117,7 +173,10 @@ def main():
     segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
     out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
     for n in [int(x) for x in args.states.split(",") if x]:
-        out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps)
+        if args.decode:
+            out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0)
+        else:
+            out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps)
     if args.cli:
         out["cli"] = cli_part(segs)
     print(json.dumps(out))
