@@ -1,7 +1,7 @@
 // api.hip -- C-ABI of libpsmc_hip.so (see include/psmc_hip.h): context, options, segment upload, parameter staging, the
-// tables, the exact mode with its host-side ordered reductions, the table readers and the decoding entry points.  The fast
-// mode's planner and launcher are in api_fast.hip, the bootstrap batch in api_batch.hip, the diagnostics in api_probes.hip;
-// psmc_hip_ctx.h holds the context they share.
+// tables, the exact mode with its host-side ordered reductions and the table reader.  The fast mode's planner and launcher
+// are in api_fast.hip, the decoding entry points in api_decode.hip, the bootstrap batch in api_batch.hip, the diagnostics in
+// api_probes.hip; psmc_hip_ctx.h holds the context they share.
 #include "psmc_hip_ctx.h"
 
 static void destroy_kids(psmc_hip_ctx *c);
@@ -692,182 +692,5 @@ extern "C" int psmc_hip_get_tables(psmc_hip_ctx *c, int seg, double *f, double *
 		for (int u = 0; u < L; ++u) memcpy(dst + (size_t)u * n, &tmp[(size_t)u * S], sizeof(double) * n);
 	}
 	if (s) HIPCHK(c, hipMemcpy(s, c->d_s + off, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost));
-	return PSMC_HIP_OK;
-}
-
-// Which tables the decoding entry points of context c read (the exact ones: exact mode, more than 128 states, or the exact
-// fallback of a fast E-step), and for the fast tables the segment's first tile in the plan of the E-step that wrote them.
-// Returns DEC_EXACT, DEC_FAST, DEC_WIDE (129..256 states, "wide_fast" + "wide_decode", the last single E-step was a wide fast one:
-// n_tiles = the segment's tiles in its plan), or a PSMC_HIP_E* code (message set).  Reads nothing but the context.
-static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_tile, int *n_tiles)
-{
-	if (c->mode == PSMC_HIP_MODE_FAST && c->ns > 128) return wide_decode_source(c, seg, who, first_tile, n_tiles);
-	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return DEC_EXACT;
-	char msg[256];
-	if (!c->d_f || c->tables_batch || c->dec_kind == DEC_NONE || c->dec_serial != c->tab_serial) {
-		snprintf(msg, sizeof msg, "%s: no single E-step yet", who);
-		return fail(c, PSMC_HIP_ESTATE, msg);
-	}
-	if (c->dec_kind == DEC_EXACT) return DEC_EXACT;
-	if (c->dec_kind == DEC_MERGED) {
-		snprintf(msg, sizeof msg, "%s: not after an E-step with the forward fix pass (merge=1: its forward table carries per-tile factors)", who);
-		return fail(c, PSMC_HIP_ENOTSUP, msg);
-	}
-	if (c->dec_kind != DEC_FAST || !c->have_b) {
-		snprintf(msg, sizeof msg, "%s: the last fast E-step kept no backward table (fused or factored back half); run it with fuse=0 (<= 64 states) / fuse128=0 (65..128)", who);
-		return fail(c, PSMC_HIP_ESTATE, msg);
-	}
-	for (size_t t = 0; t < c->chunks.size(); ++t)
-		if (c->chunk_seg[t] == seg) { *first_tile = (int)t; return DEC_FAST; }
-	snprintf(msg, sizeof msg, "%s: segment %d was not in the selection of the last E-step", who, seg);
-	return fail(c, PSMC_HIP_ESTATE, msg);
-}
-
-// the parameter block's pieces the fast decoding kernels read (fill_params / fill_common)
-static const double *par_e(const psmc_hip_ctx *c) { return c->ns == 128 ? c->d_par + 32768 : c->d_par + 4 * 4096; }
-static const double *par_a0(const psmc_hip_ctx *c) { return par_e(c) + 3 * c->ns; }
-static const double *par_re(const psmc_hip_ctx *c) { return c->ns == 128 ? c->d_par + psmc_hip_ctx::RE128_OFF : c->d_par + 4 * 4096 + 192 + 64; }
-
-extern "C" int psmc_hip_decode(psmc_hip_ctx *c, int seg, int32_t *path, double *maxp)
-{
-	if (!c || seg < 0 || seg >= c->n_seg || !path) return fail(c, PSMC_HIP_EINVAL, "decode: bad argument");
-	int first = 0, n_wide = 0;
-	const int src = decode_source(c, seg, "decode", &first, &n_wide);
-	if (src < 0) return src;
-	if (src == DEC_WIDE) return wide_decode(c, seg, first, n_wide, path, maxp);
-	if (src == DEC_FAST) {
-		HIPCHK(c, hipSetDevice(c->device));
-		const int L = c->L[seg];
-		int32_t *dp = nullptr; double *dm = nullptr;
-		if (hipMalloc((void **)&dp, sizeof(int32_t) * (size_t)L) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-		if (hipMalloc((void **)&dm, sizeof(double) * (size_t)L) != hipSuccess) { (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-		int rc = launch_post_fast(c->stream, c->d_f, c->d_b, c->d_sb, par_re(c), c->d_par, c->d_obs, c->off[seg], L, c->n, c->ns, nullptr, nullptr, dp, dm);
-		hipError_t e1 = hipMemcpyAsync(path, dp, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, c->stream);
-		hipError_t e2 = maxp ? hipMemcpyAsync(maxp, dm, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-		hipError_t e3 = hipStreamSynchronize(c->stream);
-		(void)hipFree(dp); (void)hipFree(dm);
-		if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "decode");
-		return PSMC_HIP_OK;
-	}
-	if (!c->d_f || !c->have_b || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "decode: no single E-step yet");
-	HIPCHK(c, hipSetDevice(c->device));
-	const int L = c->L[seg];
-	int32_t *dp = nullptr; double *dm = nullptr;
-	if (hipMalloc((void **)&dp, sizeof(int32_t) * (size_t)L) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	if (hipMalloc((void **)&dm, sizeof(double) * (size_t)L) != hipSuccess) { (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-	int rc = c->ns > 128 ? launch_post_decode_wide(c->stream, c->d_f, c->d_b, c->d_s, c->off[seg], L, c->n, c->ns, dp, dm)
-	                     : launch_post_decode(c->stream, c->d_f, c->d_b, c->d_s, c->off[seg], L, c->n, c->ns, dp, dm);
-	hipError_t e1 = hipMemcpyAsync(path, dp, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, c->stream);
-	hipError_t e2 = maxp ? hipMemcpyAsync(maxp, dm, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-	hipError_t e3 = hipStreamSynchronize(c->stream);
-	(void)hipFree(dp); (void)hipFree(dm);
-	if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "decode");
-	return PSMC_HIP_OK;
-}
-
-extern "C" int psmc_hip_posterior(psmc_hip_ctx *c, int seg, double *post, double *recomb)
-{
-	if (!c || seg < 0 || seg >= c->n_seg || (!post && !recomb)) return fail(c, PSMC_HIP_EINVAL, "posterior: bad argument");
-	int first = 0, n_wide = 0;
-	const int src = decode_source(c, seg, "posterior", &first, &n_wide);
-	if (src < 0) return src;
-	if (src == DEC_WIDE) return wide_posterior(c, seg, first, n_wide, post, recomb);
-	if (src == DEC_FAST) {
-		HIPCHK(c, hipSetDevice(c->device));
-		const int L = c->L[seg], n = c->n;
-		double *dp = nullptr, *dr = nullptr;
-		if (post && hipMalloc((void **)&dp, sizeof(double) * (size_t)L * n) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-		if (recomb && hipMalloc((void **)&dr, sizeof(double) * (size_t)L) != hipSuccess) { if (dp) (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-		int rc = launch_post_fast(c->stream, c->d_f, c->d_b, c->d_sb, par_re(c), c->d_par, c->d_obs, c->off[seg], L, n, c->ns, dp, dr, nullptr, nullptr);
-		hipError_t e1 = post ? hipMemcpyAsync(post, dp, sizeof(double) * (size_t)L * n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-		hipError_t e2 = recomb ? hipMemcpyAsync(recomb, dr, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-		hipError_t e3 = hipStreamSynchronize(c->stream);
-		if (dp) (void)hipFree(dp);
-		if (dr) (void)hipFree(dr);
-		if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "posterior");
-		return PSMC_HIP_OK;
-	}
-	if (!c->d_f || !c->have_b || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "posterior: no single E-step yet");
-	HIPCHK(c, hipSetDevice(c->device));
-	const int L = c->L[seg], n = c->n;
-	double *dp = nullptr, *dr = nullptr;
-	if (post && hipMalloc((void **)&dp, sizeof(double) * (size_t)L * n) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	if (recomb && hipMalloc((void **)&dr, sizeof(double) * (size_t)L) != hipSuccess) { if (dp) (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-	const double *d_e = c->ns > 128 ? c->d_par + 2 * (size_t)c->ns * c->ns : (c->ns == 128 ? c->d_par + 32768 : c->d_par + 4 * 4096);
-	int rc = c->ns > 128 ? launch_post_full_wide(c->stream, c->d_par, d_e, c->d_obs, c->d_f, c->d_b, c->d_s, c->off[seg], L, n, c->ns, dp, dr)
-	                     : launch_post_full(c->stream, c->d_par, d_e, c->d_obs, c->d_f, c->d_b, c->d_s, c->off[seg], L, n, c->ns, dp, dr);
-	hipError_t e1 = post ? hipMemcpyAsync(post, dp, sizeof(double) * (size_t)L * n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-	hipError_t e2 = recomb ? hipMemcpyAsync(recomb, dr, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-	hipError_t e3 = hipStreamSynchronize(c->stream);
-	if (dp) (void)hipFree(dp);
-	if (dr) (void)hipFree(dr);
-	if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "posterior");
-	return PSMC_HIP_OK;
-}
-
-extern "C" int psmc_hip_post_counts(psmc_hip_ctx *c, int seg, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt)
-{
-	if (!c || seg < 0 || seg >= c->n_seg || !cnt || l < 0 || n_cnt < 1 || (l > 0 && !cnt1)) return fail(c, PSMC_HIP_EINVAL, "post_counts: bad argument");
-	int first = 0, n_wide = 0;
-	const int src = decode_source(c, seg, "post_counts", &first, &n_wide);
-	if (src < 0) return src;
-	if (src == DEC_WIDE) return wide_post_counts(c, seg, first, n_wide, cnt1, l, n_cnt, cnt);
-	if (src == DEC_FAST) {
-		HIPCHK(c, hipSetDevice(c->device));
-		const int L = c->L[seg], n = c->n, min_l = L < l ? L : l;
-		if (min_l == 0) return PSMC_HIP_OK;
-		const size_t n_part = (size_t)post_counts_fast_blocks(min_l) * n_cnt * c->ns;
-		int32_t *d1 = nullptr; double *dc = nullptr, *dpart = nullptr;
-		if (hipMalloc((void **)&d1, sizeof(int32_t) * (size_t)min_l * n_cnt) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-		if (hipMalloc((void **)&dc, sizeof(double) * (size_t)n * n_cnt) != hipSuccess) { (void)hipFree(d1); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-		if (hipMalloc((void **)&dpart, sizeof(double) * n_part) != hipSuccess) { (void)hipFree(d1); (void)hipFree(dc); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-		hipError_t e0 = hipMemcpyAsync(d1, cnt1, sizeof(int32_t) * (size_t)min_l * n_cnt, hipMemcpyHostToDevice, c->stream);
-		hipError_t e1 = hipMemcpyAsync(dc, cnt, sizeof(double) * (size_t)n * n_cnt, hipMemcpyHostToDevice, c->stream);
-		int rc = launch_post_counts_fast(c->stream, c->d_f, c->d_b, par_re(c), c->d_obs, c->off[seg], L, min_l, d1, n_cnt, n, c->ns, dpart, dc);
-		hipError_t e2 = hipMemcpyAsync(cnt, dc, sizeof(double) * (size_t)n * n_cnt, hipMemcpyDeviceToHost, c->stream);
-		hipError_t e3 = hipStreamSynchronize(c->stream);
-		(void)hipFree(d1); (void)hipFree(dc); (void)hipFree(dpart);
-		if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "post_counts");
-		return PSMC_HIP_OK;
-	}
-	if (!c->d_f || !c->have_b || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "post_counts: no single E-step yet");
-	HIPCHK(c, hipSetDevice(c->device));
-	const int L = c->L[seg], n = c->n, min_l = L < l ? L : l;
-	if (min_l == 0) return PSMC_HIP_OK;
-	int32_t *d1 = nullptr; double *dc = nullptr;
-	if (hipMalloc((void **)&d1, sizeof(int32_t) * (size_t)min_l * n_cnt) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	if (hipMalloc((void **)&dc, sizeof(double) * (size_t)n * n_cnt) != hipSuccess) { (void)hipFree(d1); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-	hipError_t e0 = hipMemcpyAsync(d1, cnt1, sizeof(int32_t) * (size_t)min_l * n_cnt, hipMemcpyHostToDevice, c->stream);
-	hipError_t e1 = hipMemcpyAsync(dc, cnt, sizeof(double) * (size_t)n * n_cnt, hipMemcpyHostToDevice, c->stream);
-	int rc = c->ns > 128 ? launch_post_counts_wide(c->stream, c->d_f, c->d_b, c->d_s, c->off[seg], min_l, d1, n_cnt, n, c->ns, dc)
-	                     : launch_post_counts(c->stream, c->d_f, c->d_b, c->d_s, c->off[seg], min_l, d1, n_cnt, n, c->ns, dc);
-	hipError_t e2 = hipMemcpyAsync(cnt, dc, sizeof(double) * (size_t)n * n_cnt, hipMemcpyDeviceToHost, c->stream);
-	hipError_t e3 = hipStreamSynchronize(c->stream);
-	(void)hipFree(d1); (void)hipFree(dc);
-	if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "post_counts");
-	return PSMC_HIP_OK;
-}
-
-extern "C" int psmc_hip_scales(psmc_hip_ctx *c, int seg, double *s)
-{
-	if (!c || seg < 0 || seg >= c->n_seg || !s) return fail(c, PSMC_HIP_EINVAL, "scales: bad argument");
-	int first = 0, n_wide = 0;
-	const int src = decode_source(c, seg, "scales", &first, &n_wide);
-	if (src < 0) return src;
-	if (src == DEC_WIDE) return wide_scales(c, seg, first, n_wide, s);
-	if (!c->d_f || c->tables_batch) return fail(c, PSMC_HIP_ESTATE, "scales: no single E-step yet");
-	HIPCHK(c, hipSetDevice(c->device));
-	const int L = c->L[seg];
-	if (src == DEC_EXACT) { // the exact tables hold s itself (the same doubles psmc_hip_get_tables returns)
-		HIPCHK(c, hipMemcpy(s, c->d_s + c->off[seg], sizeof(double) * (size_t)L, hipMemcpyDeviceToHost));
-		return PSMC_HIP_OK;
-	}
-	double *ds = nullptr;
-	if (hipMalloc((void **)&ds, sizeof(double) * (size_t)L) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	int rc = launch_scales_fast(c->stream, c->d_f, c->d_s, c->d_entry, par_a0(c), par_e(c), c->d_obs, c->off[seg], L, c->chunk_used, first, c->ns, ds);
-	hipError_t e1 = hipMemcpyAsync(s, ds, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, c->stream);
-	hipError_t e2 = hipStreamSynchronize(c->stream);
-	(void)hipFree(ds);
-	if (rc || e1 != hipSuccess || e2 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "scales");
 	return PSMC_HIP_OK;
 }

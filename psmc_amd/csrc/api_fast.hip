@@ -705,6 +705,14 @@ extern "C" int psmc_hip_fast_repairs(psmc_hip_ctx *c, int out[6])
 	return PSMC_HIP_OK;
 }
 
+// the factored result h = [SL | SU | DG | CL | CU | E(2n) | LL] on the host, handed to the pointers the caller gave
+void unpack_factored(const double *h, int n, double *sums, double *E, double *LL)
+{
+	if (sums) memcpy(sums, h, sizeof(double) * 5 * n);
+	if (E) memcpy(E, h + (size_t)5 * n, sizeof(double) * 2 * n);
+	if (LL) *LL = h[(size_t)7 * n];
+}
+
 extern "C" int psmc_hip_estep_factored(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *sums,
                                        double *E, double *LL)
 {
@@ -723,9 +731,7 @@ extern "C" int psmc_hip_estep_factored(psmc_hip_ctx *c, const double *a, const d
 	const int n = c->n;
 	std::vector<double> h((size_t)7 * n + 1);
 	HIPCHK(c, hipMemcpy(h.data(), c->d_stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-	if (sums) memcpy(sums, h.data(), sizeof(double) * 5 * n);
-	if (E) memcpy(E, h.data() + (size_t)5 * n, sizeof(double) * 2 * n);
-	if (LL) *LL = h[(size_t)7 * n];
+	unpack_factored(h.data(), n, sums, E, LL);
 	return PSMC_HIP_OK;
 }
 

@@ -1,6 +1,6 @@
 // api_wide_fast.hip -- fast mode beyond 128 states: the factored statistics of psmc_hip_estep_factored[_device] at 129..256
-// states with the option "wide_fast" = 1 (kernels: estep_wide_fast.hip), and with "wide_decode" = 1 the decoding entry points
-// after such an E-step (kernels: estep_wide_post.hip; the end of this file).  Everything else a context of that size does --
+// states with the option "wide_fast" = 1 (kernels: estep_wide_fast.hip).  With "wide_decode" = 1 the decoding entry points read
+// what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip).  Everything else a context of that size does --
 // psmc_hip_estep, the batch, psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide
 // exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
 //
@@ -114,7 +114,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	}
 	if (c->n_seg < 1) return fail(c, PSMC_HIP_ESTATE, "estep_factored: no segments loaded");
 	HIPCHK(c, hipSetDevice(c->device));
-	// this is the context's last single E-step from now on; until it has succeeded there is nothing to decode (wide_decode_source)
+	// this is the context's last single E-step from now on; until it has succeeded there is nothing to decode (api_decode.hip decode_source)
 	c->wd_kind = WD_FAILED; c->wd_serial = c->tab_serial; c->wd_sel = c->sel_serial;
 	const int n = c->n, S = c->ns;
 	std::vector<double> sp((size_t)5 * n);
@@ -189,123 +189,6 @@ int estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const
 	if (!c->timing_valid) (void)hipGetLastError();
 	for (double &v : c->last_ms) v = 0.0;
 	c->last_ms[0] = ms;
-	if (sums) memcpy(sums, h.data(), sizeof(double) * 5 * n);
-	if (E) memcpy(E, h.data() + (size_t)5 * n, sizeof(double) * 2 * n);
-	if (LL) *LL = h[(size_t)7 * n];
-	return PSMC_HIP_OK;
-}
-
-// ---- decoding from the tables of the last wide fast E-step ("wide_decode"; kernels: estep_wide_post.hip).  Every call reads
-// X, 1/d, entry, bentry, the parameter block and the plan of that E-step and writes buffers of its own, freed before it returns.
-
-// DEC_WIDE with the segment's tiles t0 .. t0 + n_tiles - 1, DEC_EXACT (the exact tables are what the last single E-step left, or
-// the options are off: as without "wide_decode"), or PSMC_HIP_ESTATE
-int wide_decode_source(psmc_hip_ctx *c, int seg, const char *who, int *t0, int *n_tiles)
-{
-	if (!c->wide_fast || !c->wide_decode || c->ns > 256 || c->wd_kind == WD_NONE || c->wd_serial != c->tab_serial) return DEC_EXACT;
-	char msg[256];
-	if (c->wd_kind != WD_OK) {
-		snprintf(msg, sizeof msg, "%s: the last wide fast E-step returned an error (no converged tile boundaries to decode from)", who);
-		return fail(c, PSMC_HIP_ESTATE, msg);
-	}
-	if (c->wd_sel != c->sel_serial) {
-		snprintf(msg, sizeof msg, "%s: the selection changed since the last E-step", who);
-		return fail(c, PSMC_HIP_ESTATE, msg);
-	}
-	const int nc = (int)c->wf_chunks.size();
-	for (int t = 0; t < nc; ++t)
-		if (c->wf_chunks[t].off == c->off[seg]) { // (a segment selected several times is in the plan once, with its multiplicity)
-			int e = t;
-			while (e < nc && c->wf_chunks[e].off == c->off[seg]) ++e;
-			*t0 = t; *n_tiles = e - t;
-			return DEC_WIDE;
-		}
-	snprintf(msg, sizeof msg, "%s: segment %d was not in the selection of the last E-step", who, seg);
-	return fail(c, PSMC_HIP_ESTATE, msg);
-}
-
-static void wide_post_common(const psmc_hip_ctx *c, WidePost &w, int what, int t0, int nt)
-{
-	memset(&w, 0, sizeof(w));
-	w.stream = c->stream; w.what = what; w.ns = c->ns; w.n_states = c->n; w.t0 = t0; w.n_tiles = nt;
-	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks;
-	w.X = c->d_wf_X; w.inv = c->d_wf_inv; w.entry = c->d_wf_entry; w.bentry = c->d_wf_bentry;
-}
-
-int wide_decode(psmc_hip_ctx *c, int seg, int t0, int nt, int32_t *path, double *maxp)
-{
-	HIPCHK(c, hipSetDevice(c->device));
-	const size_t L = (size_t)c->L[seg];
-	int32_t *dp = nullptr; double *dm = nullptr;
-	if (hipMalloc((void **)&dp, sizeof(int32_t) * L) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	if (hipMalloc((void **)&dm, sizeof(double) * L) != hipSuccess) { (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-	WidePost w;
-	wide_post_common(c, w, WP_PATH, t0, nt);
-	w.path = dp; w.maxp = dm;
-	const int rc = launch_wide_post(w);
-	hipError_t e1 = hipMemcpyAsync(path, dp, sizeof(int32_t) * L, hipMemcpyDeviceToHost, c->stream);
-	hipError_t e2 = maxp ? hipMemcpyAsync(maxp, dm, sizeof(double) * L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-	hipError_t e3 = hipStreamSynchronize(c->stream);
-	(void)hipFree(dp); (void)hipFree(dm);
-	if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "decode (wide fast tables)");
-	return PSMC_HIP_OK;
-}
-
-int wide_posterior(psmc_hip_ctx *c, int seg, int t0, int nt, double *post, double *recomb)
-{
-	HIPCHK(c, hipSetDevice(c->device));
-	const size_t L = (size_t)c->L[seg], n = (size_t)c->n;
-	double *dp = nullptr, *dr = nullptr;
-	if (post && hipMalloc((void **)&dp, sizeof(double) * L * n) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	if (recomb && hipMalloc((void **)&dr, sizeof(double) * L) != hipSuccess) { if (dp) (void)hipFree(dp); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-	WidePost w;
-	wide_post_common(c, w, post ? (recomb ? WP_POST_REC : WP_POST) : WP_REC, t0, nt);
-	w.post = dp; w.recomb = dr;
-	const int rc = launch_wide_post(w);
-	hipError_t e1 = post ? hipMemcpyAsync(post, dp, sizeof(double) * L * n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-	hipError_t e2 = recomb ? hipMemcpyAsync(recomb, dr, sizeof(double) * L, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-	hipError_t e3 = hipStreamSynchronize(c->stream);
-	if (dp) (void)hipFree(dp);
-	if (dr) (void)hipFree(dr);
-	if (rc || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "posterior (wide fast tables)");
-	return PSMC_HIP_OK;
-}
-
-int wide_post_counts(psmc_hip_ctx *c, int seg, int t0, int nt, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt)
-{
-	HIPCHK(c, hipSetDevice(c->device));
-	const int L = c->L[seg], n = c->n, min_l = L < l ? L : l;
-	if (min_l == 0) return PSMC_HIP_OK;
-	int32_t *d1 = nullptr; double *dc = nullptr, *dpart = nullptr;
-	if (hipMalloc((void **)&d1, sizeof(int32_t) * (size_t)min_l * n_cnt) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	if (hipMalloc((void **)&dc, sizeof(double) * (size_t)n * n_cnt) != hipSuccess) { (void)hipFree(d1); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-	if (hipMalloc((void **)&dpart, sizeof(double) * (size_t)nt * n_cnt * c->ns) != hipSuccess) { (void)hipFree(d1); (void)hipFree(dc); return fail(c, PSMC_HIP_ENOMEM, "hipMalloc"); }
-	hipError_t e0 = hipMemcpyAsync(d1, cnt1, sizeof(int32_t) * (size_t)min_l * n_cnt, hipMemcpyHostToDevice, c->stream);
-	hipError_t e1 = hipMemcpyAsync(dc, cnt, sizeof(double) * (size_t)n * n_cnt, hipMemcpyHostToDevice, c->stream);
-	WidePost w;
-	wide_post_common(c, w, WP_COUNTS, t0, nt);
-	w.cnt1 = d1; w.n_cnt = n_cnt; w.min_l = min_l; w.part = dpart; w.cnt = dc;
-	const int rc = launch_wide_post(w);
-	hipError_t e2 = hipMemcpyAsync(cnt, dc, sizeof(double) * (size_t)n * n_cnt, hipMemcpyDeviceToHost, c->stream);
-	hipError_t e3 = hipStreamSynchronize(c->stream);
-	(void)hipFree(d1); (void)hipFree(dc); (void)hipFree(dpart);
-	if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "post_counts (wide fast tables)");
-	return PSMC_HIP_OK;
-}
-
-int wide_scales(psmc_hip_ctx *c, int seg, int t0, int nt, double *s)
-{
-	HIPCHK(c, hipSetDevice(c->device));
-	const size_t L = (size_t)c->L[seg];
-	double *ds = nullptr;
-	if (hipMalloc((void **)&ds, sizeof(double) * L) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
-	WidePost w;
-	wide_post_common(c, w, WP_SCALES, t0, nt);
-	w.s = ds;
-	const int rc = launch_wide_post(w);
-	hipError_t e1 = hipMemcpyAsync(s, ds, sizeof(double) * L, hipMemcpyDeviceToHost, c->stream);
-	hipError_t e2 = hipStreamSynchronize(c->stream);
-	(void)hipFree(ds);
-	if (rc || e1 != hipSuccess || e2 != hipSuccess) return fail(c, PSMC_HIP_EDEVICE, "scales (wide fast tables)");
+	unpack_factored(h.data(), n, sums, E, LL);
 	return PSMC_HIP_OK;
 }

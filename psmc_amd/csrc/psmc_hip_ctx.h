@@ -1,6 +1,8 @@
 // psmc_hip_ctx.h -- the context behind the C-ABI of include/psmc_hip.h and the helpers its translation units share:
-//   api.hip        context, options, segments, parameter staging, tables, exact mode, table readers / decoding
+//   api.hip        context, options, segments, parameter staging, tables, exact mode, the table reader
 //   api_fast.hip   fast mode: tile plan, sweep items, learning, the launch of one fast E-step and its entry points
+//   api_wide_fast.hip  fast mode at 129..256 states ("wide_fast"): plan, rounds and launch of the factored E-step
+//   api_decode.hip psmc_hip_decode / _posterior / _post_counts / _scales from the exact, the fast or the wide fast tables
 //   api_batch.hip  psmc_hip_estep_batch (bootstrap replicates): exact launch groups, fast per-replicate plans
 //   api_probes.hip device self-test, microbenchmarks and probes (diagnostics)
 // Everything is built with -ffp-contract=off: no host or device expression is ever fused.
@@ -23,14 +25,14 @@ using namespace psmc;
 
 #define HMM_TINY_H 1e-25
 
-// psmc_hip_ctx::dec_kind: the tables the decoding entry points of a fast context (<= 128 states) would read
+// psmc_hip_ctx::dec_kind: the tables the decoding entry points of a fast context (<= 128 states) would read (api_decode.hip)
 constexpr int DEC_NONE = 0;   // no single E-step since the tables were last used otherwise (or it failed)
 constexpr int DEC_FAST = 1;   // the fast tables X and bt (dense sweeps, or the structured ones with the unfused back half): estep_post_fast.hip
 constexpr int DEC_EXACT = 2;  // the exact tables (65..128 states, a matrix without the PSMC form: fast mode ran the exact kernels)
 constexpr int DEC_NO_BT = 3;  // the fused or factored back half: no backward table
 constexpr int DEC_MERGED = 4; // the forward fix pass ("merge"): its X carries per-tile factors
-constexpr int DEC_WIDE = 5;   // decode_source only: the tables of the wide fast path (129..256 states, "wide_decode"): estep_wide_post.hip
-// psmc_hip_ctx::wd_kind: what the last wide fast E-step of the context left (api_wide_fast.hip)
+constexpr int DEC_WIDE = 5;   // never stored, decode_source returns it: the tables of the wide fast path (129..256 states, "wide_decode"): estep_wide_post.hip
+// psmc_hip_ctx::wd_kind: what the last wide fast E-step of the context left (set in api_wide_fast.hip, read by api_decode.hip decode_source)
 constexpr int WD_NONE = 0;    // there was none, or a batch came after it
 constexpr int WD_OK = 1;      // X, 1/d, entry and a converged bentry of every tile of its plan
 constexpr int WD_FAILED = 2;  // it returned an error: bentry is not converged
@@ -46,7 +48,7 @@ struct psmc_hip_ctx {
 	int struct_tiles = 8192;   // "struct_tiles": tiles aimed at when the structured sweeps are used (4 per wave)
 	bool use_struct = false, planned_struct = false;
 	int last_fused = 0, last_ckpt = 0; // what the last fast E-step ran: EstepLaunch::fused / ckpt
-	// what the last single E-step of a fast context left for the decoding entry points (api.hip decode_source), and the table
+	// what the last single E-step of a fast context left for the decoding entry points (api_decode.hip decode_source), and the table
 	// serial it left it at: any later use of the tables (another E-step, a batch) makes it stale
 	int dec_kind = 0; unsigned long long dec_serial = 0;
 	bool want_factored = false; // this call asked for the factored statistics (psmc_hip_estep_factored)
@@ -284,13 +286,9 @@ int  ensure_fast_buffers(psmc_hip_ctx *c);                                      
 int  auto_tile_len(const psmc_hip_ctx *c, int64_t bins, size_t n_work, bool structured);                    // api_fast.hip
 int  enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t st); // api_fast.hip
 int  read_warm(psmc_hip_ctx *c, hipStream_t st);                                                            // api_fast.hip
+void unpack_factored(const double *h, int n, double *sums, double *E, double *LL);                          // api_fast.hip
 bool factor_structure(int n, int S, const double *a, double *sp);                                         // api.hip
 void free_wide_fast(psmc_hip_ctx *c);                                                                       // api_wide_fast.hip
 int  estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t st); // api_wide_fast.hip
 int  estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *sums, double *E, double *LL); // api_wide_fast.hip
-int  wide_decode_source(psmc_hip_ctx *c, int seg, const char *who, int *t0, int *n_tiles);                  // api_wide_fast.hip: DEC_WIDE, DEC_EXACT or an error
-int  wide_decode(psmc_hip_ctx *c, int seg, int t0, int nt, int32_t *path, double *maxp);                   // api_wide_fast.hip
-int  wide_posterior(psmc_hip_ctx *c, int seg, int t0, int nt, double *post, double *recomb);               // api_wide_fast.hip
-int  wide_post_counts(psmc_hip_ctx *c, int seg, int t0, int nt, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt); // api_wide_fast.hip
-int  wide_scales(psmc_hip_ctx *c, int seg, int t0, int nt, double *s);                                     // api_wide_fast.hip
 int  estep_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *A, double *E, double *A0, double *LL, double *chk); // api_fast.hip
