@@ -117,6 +117,11 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           grid of "phase1_waves" waves per SIMD pulls from; 0 = two launches, dealt out by the dispatcher.  Bit-identical.
  *                           auto: 1
  *  "phase1_waves"  2        waves per SIMD of that grid (1..4)
+ *  "tail"          1        fused back half (64 and 128 states), overlapped streams: 1 = the waves of the fused counts test the backward tile
+ *                           boundaries themselves, with the verify kernel's own arithmetic (the few pairs they cannot -- tiles of glued runs, an
+ *                           upper tile that owns no transition -- stay with that kernel), and the reductions follow the counts instead of the
+ *                           verify, list A's partial counts being summed while list B runs; 0 = verify, compaction and reductions as launches
+ *                           behind list B.  Bit-identical; ignored by the factored, the unfused and the dense back half and by batches.
  *  "coarse"        auto     a bulk sweep item spans up to this many consecutive tiles of a segment: ONE speculative warm-up per item
  *                           and direction (the forward sweep runs through its tiles, the backward pass of phase 1 walks the item and
  *                           leaves every tile's start vector), so the back half keeps its ~4096 tiles while phase 1 pays half the

@@ -129,7 +129,8 @@ static int plan_fast(psmc_hip_ctx *c)
 			return fail(c, PSMC_HIP_ENOMEM, "hipHostMalloc (mapped)");
 		if ((rc = dev_alloc(c, &c->d_LLpart, (size_t)nc))) return rc;
 		if ((rc = dev_alloc(c, &c->d_items, (size_t)32 * nc + 64))) return rc; // (+ 4 nc: matrix slot of every KcTile | the KcTile that computes a slot; + 2 nc: the fix pass's tiles)
-		if ((rc = dev_alloc(c, &c->d_ftiles, (size_t)2 * (nc + 16)))) return rc;
+		if ((rc = dev_alloc(c, &c->d_ftiles, (size_t)3 * (nc + 16)))) return rc; // lists A | B, then the cover table of the backward verify
+		c->vcover_off = (size_t)2 * (nc + 16);
 		if (c->h_ritems) { (void)hipHostFree(c->h_ritems); c->h_ritems = nullptr; }
 		if (hipHostMalloc((void **)&c->h_ritems, (size_t)4 * nc * sizeof(int), hipHostMallocMapped) != hipSuccess ||
 		    hipHostGetDevicePointer((void **)&c->m_ritems, c->h_ritems, 0) != hipSuccess)
@@ -292,6 +293,20 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 		while (lb.size() % c->count_group) lb.push_back(-1);
 		la.insert(la.end(), lb.begin(), lb.end());
 		if (!la.empty()) HIPCHK(c, hipMemcpy(c->d_ftiles, la.data(), sizeof(int) * la.size(), hipMemcpyHostToDevice));
+	}
+	{ // "tail" = 1: who tests the backward boundary between tile b and tile b + 1 (TailVerify::cover, psmc_hip_internal.h).  The wave of the fused
+	  // counts that computes tile b + 1 has its exit vector in registers and reads tile b's start vector from memory -- allowed only where that
+	  // vector is final before EITHER counts launch starts: a bulk tile, whose speculation ran in phase 1.  Not a member of a glued run (the
+	  // runs' path may still be writing it while list A runs), not a from-above tile (its start vector is the exit vector above, copied by
+	  // its own wave in list B: that wave tests the pair).  An upper tile that owns no transition leaves no exit vector in the counts.
+		std::vector<int> cov(nc, 0);
+		for (int b = 0; b < nc; ++b) {
+			if (from_above[b]) { cov[b] = 2; continue; }
+			if (b + 1 >= nc || c->chunks[b + 1].off != c->chunks[b].off || in_run[b]) continue;
+			const Chunk &up = c->chunks[b + 1];
+			if (std::min(up.hi, up.L - 1) >= up.lo) cov[b] = 1;
+		}
+		HIPCHK(c, hipMemcpy(c->d_ftiles + c->vcover_off, cov.data(), sizeof(int) * cov.size(), hipMemcpyHostToDevice));
 	}
 	c->items_two_phase = two_phase_bwd ? 2 : 0; c->items_coarse = coarse;
 	HIPCHK(c, hipMemcpy(c->d_items, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
@@ -604,6 +619,7 @@ int enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double
 	p.coarse = coarse; p.d_singles_b = c->d_items + 24 * (size_t)p.n_chunks; p.n_singles_b = c->n_singles_b;
 	p.n_B_b = c->n_B_b; p.runs_in_b = c->runs_in_b ? 1 : 0; p.n_list_a = c->n_list_a; p.n_list_b = c->n_list_b; p.d_ftiles = c->d_ftiles; p.count_group = c->count_group;
 	c->timing_two_launches = p.fused == 1 && p.n_list_b > 0;
+	p.tail = c->tail != 0 && c->use_struct && p.fused == 1 && c->overlap ? 1 : 0; p.d_vcover = c->d_ftiles + c->vcover_off;
 	p.d_items_f = c->d_items; p.d_items_b = c->d_items + 2 * p.n_chunks;
 	p.d_ritems_f = c->d_items + 4 * p.n_chunks; p.d_ritems_b = c->d_items + 6 * p.n_chunks;
 	p.n_items_f = c->n_items_f; p.n_items_b = c->n_items_b; p.tile_len = c->chunk_used; p.h_ritems = c->h_ritems; p.m_ritems = c->m_ritems; p.m_cnt = c->m_cnt;

@@ -60,16 +60,6 @@ __device__ __forceinline__ double fast_rcp(double x) {
 	return r;
 }
 
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-	return v;
-}
-__device__ __forceinline__ double wave_add(double v) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-	return v;
-}
 // max_k |x-y| / max_k |y|  (NaN-safe: a NaN anywhere yields +inf)
 __device__ __forceinline__ double rel_mismatch(double x, double y) {
 	const double num = wave_max(fabs(x - y)), den = wave_max(fabs(y));
@@ -216,37 +206,27 @@ __global__ __launch_bounds__(64) void k_bwd_fast(const double *__restrict__ aT, 
 // ------------------------------------------------------------------ verify
 // flags tiles whose boundary vector disagrees with the neighbour's converged
 // one; cnt[0] = number flagged, warm[which] = largest mismatch seen this round
-// max_k |x/|x| - y/|y|| / max_k (y/|y|) over S = 64 or 128 states (lane and lane + 64), |.| = sum: boundary
-// vectors are compared as DIRECTIONS (a vector from the transfer-matrix chain has an arbitrary scale; every
-// consumer -- per-position normaliser of the counts, k_ll -- is scale-free)
+// (the test itself, rel_mismatch_vals, is shared with the fused counts kernels: psmc_hip_internal.h)
 template <int S> __device__ __forceinline__ double rel_mismatch_vec(const double *x, const double *y, int lane, bool with_scale = false) {
 	double xv = x[lane], yv = y[lane], xw = 0.0, yw = 0.0;
 	if (S == 128) { xw = x[64 + lane]; yw = y[64 + lane]; }
-	const double sx = wave_add(xv + xw), sy = wave_add(yv + yw);
-	const double ix = 1.0 / sx, iy = 1.0 / sy;
-	double num = fabs(xv * ix - yv * iy), den = fabs(yv * iy);
-	if (with_scale) num = fmax(num, fabs(sx - sy) * iy * den); // the two vectors themselves, not only their directions
-	bool bad = (xv != xv) || (yv != yv) || (ix != ix) || (iy != iy);
-	if (S == 128) {
-		num = fmax(num, fabs(xw * ix - yw * iy)); den = fmax(den, fabs(yw * iy));
-		bad = bad || (xw != xw) || (yw != yw);
-	}
-	num = wave_max(num); den = wave_max(den);
-	return __any(bad) ? __builtin_inf() : num / den;
+	return rel_mismatch_vals<S>(xv, yv, xw, yw, with_scale);
 }
 template <bool BWD, int S>
 __global__ __launch_bounds__(64) void k_verify(const Chunk *__restrict__ chunks, int n_chunks, double tol,
                                                  const double *__restrict__ f, const double *__restrict__ mine,
                                                  const double *__restrict__ bexit, int *__restrict__ dirty,
                                                  int *__restrict__ cnt, unsigned long long *__restrict__ warm, int with_scale,
-                                                 double *__restrict__ mis)
+                                                 double *__restrict__ mis, const int *__restrict__ cover)
 {
 	// mis (first verify of an E-step; host-mapped memory): the mismatch itself, for the per-tile warm-ups
 	// with_scale (backward, bt table in use): row lo-1 of the table is written by the tile below as ITS start vector
 	// and read by this tile's counts next to its own bt[lo+1], so the two tiles must agree on the scale as well.  A
 	// warm-up of at least one normalising position leaves the natural scale; without one (warmup < 4) a start vector
 	// can have the right direction and the wrong length.
+	// cover (backward, "tail" = 1, first verify of an E-step): the pairs a wave of the fused counts has tested already (TailVerify)
 	const int lane = threadIdx.x, b = blockIdx.x;
+	if (cover != nullptr && cover[b] != 0) return;
 	const Chunk c = chunks[b];
 	double m = 0.0;
 	bool check;
@@ -254,16 +234,10 @@ __global__ __launch_bounds__(64) void k_verify(const Chunk *__restrict__ chunks,
 		check = c.lo > 1 && !(c.flags & CHUNK_ANCHOR_F);
 		if (check) m = rel_mismatch_vec<S>(mine + (int64_t)b * S, f + (c.off + c.lo - 2) * S, lane);
 	} else {
-		check = !(c.flags & (CHUNK_ANCHOR_B | CHUNK_LAST)) && min(c.hi, c.L - 1) >= c.lo && b + 1 < n_chunks;
+		check = verify_check_bwd(c, b, n_chunks);
 		if (check) m = rel_mismatch_vec<S>(mine + (int64_t)b * S, bexit + (int64_t)(b + 1) * S, lane, with_scale != 0);
 	}
-	if (lane == 0) {
-		const int bad = check && !(m <= tol);
-		dirty[b] = bad;
-		if (bad) atomicAdd(cnt, 1);
-		if (mis) mis[b] = check ? m : -1.0;
-		if (check) atomicMax(&warm[BWD ? 1 : 0], (unsigned long long)__double_as_longlong(m));
-	}
+	if (lane == 0) verify_commit(b, check, m, tol, dirty, cnt, &warm[BWD ? 1 : 0], mis);
 }
 
 // ------------------------------------------------------------------ expect
@@ -436,30 +410,47 @@ __global__ __launch_bounds__(64) void k_ll(const Chunk *__restrict__ chunks, con
 
 // ------------------------------------------------------------------ reduce
 // Fixed-order two-stage reduction of the per-wave partials (deterministic).
+// s + p[j * stride] + p[(j + RED_ROWS) * stride] + ... (j < n), added strictly in that order.  The loads do not depend on the running
+// sum, so they are issued NB at a time ahead of their additions: a stage row of the genome's E partials is 127 terms, and one load
+// latency per term (the plain loop) was the whole length of the launch.  Same additions, same order, same bits.
+template <int NB>
+__device__ __forceinline__ double sum_ahead(const double *__restrict__ p, int64_t stride, int &j, int n, double s)
+{
+	for (; j + (NB - 1) * RED_ROWS < n; j += NB * RED_ROWS) {
+		double v[NB];
+#pragma unroll
+		for (int u = 0; u < NB; ++u) v[u] = p[(int64_t)(j + u * RED_ROWS) * stride];
+#pragma unroll
+		for (int u = 0; u < NB; ++u) s += v[u];
+	}
+	return s;
+}
+__device__ __forceinline__ double sum_rows(const double *__restrict__ p, int64_t stride, int j, int n, double s)
+{
+	s = sum_ahead<16>(p, stride, j, n, s);
+	s = sum_ahead<4>(p, stride, j, n, s);
+	return sum_ahead<1>(p, stride, j, n, s);
+}
 template <int S>
 __global__ __launch_bounds__(256) void k_reduce1(const double *__restrict__ Cpart, const double *__restrict__ Spart,
                                                    int nC, int nS, const double *__restrict__ LLpart, int nchunks,
-                                                   double *__restrict__ stage)
+                                                   double *__restrict__ stage, int c0)
 {
+	// c0 > 0 ("tail" = 1, launch_fast): an earlier launch (grid.x = S * S / 256: the C blocks only) has left in every stage row the sum of its
+	// partials below c0; this one continues each row's running sum with the partials from c0 on -- the same additions in the same order
+	// as one launch over all of them, hence the same bits
 	constexpr int SL = S * S + 3 * S + 1; // C | S-counts | LL of one stage row
 	const int y = blockIdx.y, tid = threadIdx.x;
 	double *st = stage + (int64_t)y * SL;
 	if ((int)blockIdx.x < S * S / 256) {
 		const int i = blockIdx.x * 256 + tid;
 		double s = 0.0;
-		for (int j = y; j < nC; j += RED_ROWS) s += Cpart[(int64_t)j * (S * S) + i];
-		st[i] = s;
+		int j = y;
+		if (c0 > 0) { s = st[i]; if (j < c0) j += (c0 - j + RED_ROWS - 1) / RED_ROWS * RED_ROWS; }
+		st[i] = sum_rows(Cpart + i, S * S, j, nC, s);
 	} else {
-		for (int i = tid; i < 3 * S; i += 256) {
-			double s = 0.0;
-			for (int j = y; j < nS; j += RED_ROWS) s += Spart[(int64_t)j * (3 * S) + i];
-			st[S * S + i] = s;
-		}
-		if (tid == 255) {
-			double s = 0.0;
-			for (int j = y; j < nchunks; j += RED_ROWS) s += LLpart[j];
-			st[S * S + 3 * S] = s;
-		}
+		for (int i = tid; i < 3 * S; i += 256) st[S * S + i] = sum_rows(Spart + i, 3 * S, y, nS, 0.0);
+		if (tid == 255) st[S * S + 3 * S] = sum_rows(LLpart, 1, y, nchunks, 0.0);
 	}
 }
 // Writes the final statistics UNPADDED: out = [A n*n | E 2*n | LL].
@@ -547,7 +538,14 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 	hipStream_t sm = p.stream, sa = ov ? p.stream2 : p.stream, sx = ov ? p.stream3 : p.stream;
 	rep->fwd_rounds = rep->bwd_rounds = rep->fwd_tiles = rep->bwd_tiles = rep->merged = rep->recounted = 0;
 	rep->converged = 1;
+	static const bool recheck = getenv("PSMC_HIP_DEBUG_RECHECK") != nullptr; // the diagnostic at the end runs after the E-step: keep the ordinary tail
+	const bool optimistic = p.fused != 0 && ov && !recheck; // the OPTIMISTIC TAIL, further down
+	// "tail" = 1 (fused back half, optimistic tail): the counts waves test the backward boundaries of round 0 themselves (estep_fused.hip
+	// tail_verify) and the reductions follow the counts, not the verify.  The words that verify accumulates into are cleared here, with the
+	// rest, instead of by two fills behind list B.
+	const bool tl = p.tail != 0 && p.fused == 1 && optimistic && p.d_vcover != nullptr;
 	(void)hipMemsetAsync(p.d_warm, 0, 2 * sizeof(unsigned long long), sm);
+	if (tl) (void)hipMemsetAsync(p.d_cnt + 1, 0, sizeof(int), sm);
 	(void)hipMemsetAsync(p.d_touch_f, 0, 3 * sizeof(int) * (size_t)p.n_chunks, sm); // touch_f | touch_b | fmerge
 	if (p.d_gate) (void)hipMemsetAsync(p.d_gate, 0, 2 * sizeof(int), sm); // started-counters of the walks and of the bulk grid
 	if (p.q_grid > 0) (void)hipMemsetAsync(p.d_qhead, 0, sizeof(int), sm); // head of phase 1's work queue
@@ -648,13 +646,14 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 		if (p.ev[8]) (void)hipEventRecord(p.ev[8], sa);
 		if (p.fused == 2) { if (p.coarse > 1) launch_bwd_acc(p, sa, 6, 0, p.n_singles_b); else launch_bwd_acc(p, sa, 0, fb0, p.n_items_b - fb0); }
 		else {
-			launch_bwd_count(p, sa, 0, false);
+			launch_bwd_count(p, sa, 0, false, false, tl);
 			if (p.n_list_b > 0) { // its tiles start from the exit vectors list A left
 				if (lw && ov && sw != sa && late) (void)hipStreamWaitEvent(sa, p.evx[7], 0);
 				(void)hipEventRecord(p.evx[11], sa);
 				(void)hipEventRecord(p.evx[12], sa);
-				launch_bwd_count(p, sa, 1, false);
+				launch_bwd_count(p, sa, 1, false, false, tl);
 			}
+			if (tl) (void)hipEventRecord(p.evx[13], sa); // every partial of the counts is final (evx[12]: list A's)
 		}
 		if (p.ev[9]) (void)hipEventRecord(p.ev[9], sa);
 		if (p.ev[6]) (void)hipEventRecord(p.ev[6], sa);
@@ -679,15 +678,19 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 	struct Chain { hipStream_t st; hipEvent_t rb; int slot; bool bwd, done, pending; int round; };
 	Chain ch[2] = {{sm, p.evx[4], 0, false, false, false, 0}, {sa, p.evx[5], 1, true, false, false, 0}};
 	auto post_verify = [&](Chain &c) -> int {
-		(void)hipMemsetAsync(p.d_cnt + c.slot, 0, sizeof(int), c.st);
-		(void)hipMemsetAsync(p.d_warm + c.slot, 0, sizeof(unsigned long long), c.st);
+		const bool tv = tl && c.bwd && c.round == 0; // most pairs are tested, flagged and counted already: k_verify takes the rest (TailVerify::cover)
+		if (!tv) {
+			(void)hipMemsetAsync(p.d_cnt + c.slot, 0, sizeof(int), c.st);
+			(void)hipMemsetAsync(p.d_warm + c.slot, 0, sizeof(unsigned long long), c.st);
+		}
 #define PSMC_LV(BW, S, MINE, DIRTY, CNT) hipLaunchKernelGGL((k_verify<BW, S>), g, b, 0, c.st, p.d_chunks, p.n_chunks, p.tol, p.d_f, \
 			MINE, p.d_bexit, DIRTY, CNT, p.d_warm, (BW && !p.fused) ? 1 : 0, \
-			(p.m_mis && c.round == 0 && (BW || !p.merge)) ? p.m_mis + (BW ? p.n_chunks : 0) : nullptr) /* (forward, with the fix pass: it has recorded them) */
+			(p.m_mis && c.round == 0 && (BW || !p.merge)) ? p.m_mis + (BW ? p.n_chunks : 0) : nullptr, /* (forward, with the fix pass: it has recorded them) */ \
+			(BW && tv) ? p.d_vcover : nullptr)
 		if (!c.bwd) { if (p.ns == 128) PSMC_LV(false, 128, p.d_entry, p.d_dirty, p.d_cnt); else PSMC_LV(false, 64, p.d_entry, p.d_dirty, p.d_cnt); }
 		else { if (p.ns == 128) PSMC_LV(true, 128, p.d_bentry, p.d_dirty_b, p.d_cnt + 1); else PSMC_LV(true, 64, p.d_bentry, p.d_dirty_b, p.d_cnt + 1); }
 #undef PSMC_LV
-		launch_compact(p, c.st, c.bwd); // flagged tiles in ascending order + their number, straight into host-mapped memory
+		launch_compact(p, c.st, c.bwd, tv); // flagged tiles in ascending order + their number, straight into host-mapped memory
 		if (hipEventRecord(c.rb, c.st) != hipSuccess) return -1;
 		c.pending = true;
 		return 0;
@@ -699,18 +702,22 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 		else hipLaunchKernelGGL(k_ll<64>, g, b, 0, st, p.d_chunks, p.d_f, p.d_s, p.d_entry, p.d_LLpart, fm, p.d_finv);
 		PSMC_DBG("k_ll", p.n_chunks, 0, 0);
 	};
-	auto launch_reduce = [&](hipStream_t sm) { // (the parameter shadows the main stream on purpose: the optimistic tail reduces on another one)
+	// part: 0 = everything; 1 = list A's C partials only (the head of every stage row's sum), 2 = the rest, continuing from what 1 left
+	auto launch_reduce = [&](hipStream_t sm, int part = 0) { // (the parameter shadows the main stream on purpose: the optimistic tail reduces on another one)
+		const int ga = p.fused == 1 ? (p.n_list_a + p.count_group - 1) / p.count_group : 0, c0 = part == 2 ? ga : 0;
 		const int nS = p.n_chunks * p.n_sub, nC = p.fused == 1 ? (p.n_list_a + p.count_group - 1) / p.count_group + (p.n_list_b + p.count_group - 1) / p.count_group : nS; // fused: one C partial per group of four tiles
 		if (p.fused == 2) {
 			launch_reduce_factored(p, sm);
 		} else if (p.ns == 128) {
-			hipLaunchKernelGGL(k_reduce1<128>, dim3(128 * 128 / 256 + 1, RED_ROWS), dim3(256), 0, sm, p.d_Cpart, p.d_Epart, nC, nS, p.d_LLpart,
-			                   p.n_chunks, p.d_stage);
+			hipLaunchKernelGGL(k_reduce1<128>, dim3(128 * 128 / 256 + (part == 1 ? 0 : 1), RED_ROWS), dim3(256), 0, sm, p.d_Cpart, p.d_Epart, part == 1 ? ga : nC, nS, p.d_LLpart,
+			                   p.n_chunks, p.d_stage, c0);
+			if (part == 1) return;
 			hipLaunchKernelGGL(k_reduce2<128>, dim3((128 * 128 + 3 * 128 + 1 + 255) / 256), dim3(256), 0, sm, p.d_stage, p.d_a, p.d_e,
 			                   p.tiny_total, p.n_states, p.d_stats);
 		} else {
-			hipLaunchKernelGGL(k_reduce1<64>, dim3(17, RED_ROWS), dim3(256), 0, sm, p.d_Cpart, p.d_Epart, nC, nS, p.d_LLpart,
-			                   p.n_chunks, p.d_stage);
+			hipLaunchKernelGGL(k_reduce1<64>, dim3(part == 1 ? 16 : 17, RED_ROWS), dim3(256), 0, sm, p.d_Cpart, p.d_Epart, part == 1 ? ga : nC, nS, p.d_LLpart,
+			                   p.n_chunks, p.d_stage, c0);
+			if (part == 1) return;
 			hipLaunchKernelGGL(k_reduce2<64>, dim3((STATS_LEN + 255) / 256), dim3(256), 0, sm, p.d_stage, p.d_a, p.d_e,
 			                   p.tiny_total, p.n_states, p.d_stats);
 		}
@@ -725,16 +732,20 @@ int launch_fast(const EstepLaunch &p, FastReport *rep)
 	// unfused one takes its counts in a separate pass that has its own dependencies.)  The tail runs on the counts' stream
 	// of the unfused plan, which is idle here: on the main stream it would sit between the forward verify and a forward
 	// REPAIR round, and the repair would wait for the whole back half instead of running beside it.
-	static const bool recheck = getenv("PSMC_HIP_DEBUG_RECHECK") != nullptr; // the diagnostic below runs after the E-step: keep the ordinary tail
-	const bool optimistic = p.fused != 0 && ov && !recheck;
+	// "tail" = 1 (the fused back half): the reductions read the partials of the counts and k_ll, nothing the backward verify writes -- so
+	// they follow the counts (evx[13]), not the verify behind them, and the half of the C partials that list A left is summed while list B
+	// runs (evx[12] sits between the two launches).  A verify that flags tiles has the tail enqueued again, as before.
 	if (optimistic) {
 		(void)hipStreamWaitEvent(sx, p.evx[4], 0); // forward verify (and compaction) done: the forward tables are final unless it flagged tiles
 		launch_ll(sx);
-		(void)hipEventRecord(p.evx[2], sa); (void)hipStreamWaitEvent(sx, p.evx[2], 0); // back half + backward verify done
+		const bool early = tl && p.n_list_a > 0 && p.n_list_b > 0;
+		if (early) { (void)hipStreamWaitEvent(sx, p.evx[12], 0); launch_reduce(sx, 1); }
+		if (tl) (void)hipStreamWaitEvent(sx, p.evx[13], 0); // back half done
+		else { (void)hipEventRecord(p.evx[2], sa); (void)hipStreamWaitEvent(sx, p.evx[2], 0); } // back half + backward verify done
 		if (p.ev[1]) (void)hipEventRecord(p.ev[1], sx);
 		if (p.ev[2]) (void)hipEventRecord(p.ev[2], sx);
 		if (p.ev[3]) (void)hipEventRecord(p.ev[3], sx);
-		launch_reduce(sx);
+		launch_reduce(sx, early ? 2 : 0);
 		(void)hipEventRecord(p.evx[10], sx);
 	}
 	bool ll_stale = !optimistic;

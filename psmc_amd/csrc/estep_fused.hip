@@ -104,6 +104,57 @@ __device__ __forceinline__ void count4f_mfma(const double (&FA)[NPLF], const dou
 #pragma unroll
 		for (int j2 = 0; j2 < 4; ++j2) acc[j][j2] = __builtin_amdgcn_mfma_f64_16x16x4f64(FA[j], FB[j2], acc[j][j2], 0, 0, 0);
 }
+// ---- "tail" = 1: the backward verify of round 0 inside the counts (TailVerify, psmc_hip_internal.h; launch_fast's optimistic tail).
+// The wave that computes tile t holds bexit[t] in registers: each of its four rows still has x = bt_lo when the kernel ends (a row that is
+// done idles MASKED, which leaves x alone), so the pair (t - 1, t) is tested here, with k_verify's own arithmetic, instead of by a launch
+// behind list B.  bentry[t - 1] is read from memory: `cover` says 1 only where phase 1 wrote it (a bulk tile that speculated), which is
+// before either counts launch in stream order -- no flag, no wait.  A from-above tile (cover 2) tests its own pair: both sides are the
+// vector it started from.  Everything else (tiles of glued runs, an upper tile that owns no transition) is left to k_verify.
+// One pair at a time, the whole wave on it (lane = state), exactly like a block of k_verify.
+template <int NPL, int S>
+__device__ __forceinline__ void tail_verify(const TailVerify &tv, const Chunk *__restrict__ chunks, int tile, bool valid, bool work, bool from_above,
+                                            const double (&x)[NPL], const double *__restrict__ bentry, const double *__restrict__ bexit, int lane)
+{
+#pragma unroll
+	for (int r = 0; r < 4; ++r) {
+		const int t = __builtin_amdgcn_readlane(tile, 16 * r);
+		const bool v_r = __builtin_amdgcn_readlane((int)valid, 16 * r) != 0, w_r = __builtin_amdgcn_readlane((int)work, 16 * r) != 0;
+		const bool fa_r = __builtin_amdgcn_readlane((int)from_above, 16 * r) != 0;
+		if (v_r && fa_r && tv.cover[t] == 2) {
+			const Chunk cb = chunks[t];
+			const bool check = verify_check_bwd(cb, t, tv.n_chunks);
+			double m = 0.0;
+			if (check) {
+				const double *y = bexit + (int64_t)(t + 1) * S;
+				const double yv = y[lane], yw = S == 128 ? y[64 + lane] : 0.0;
+				m = rel_mismatch_vals<S>(yv, yv, yw, yw, false);
+			}
+			if (lane == 0) verify_commit(t, check, m, tv.tol, tv.dirty, tv.cnt, tv.warm, tv.mis);
+		}
+		if (w_r && t > 0 && tv.cover[t - 1] == 1) {
+			const Chunk cb = chunks[t - 1];
+			const bool check = verify_check_bwd(cb, t - 1, tv.n_chunks);
+			double m = 0.0;
+			if (check) {
+				// the row's vector in k_verify's layout: state k sits in register k % NPL of lane 16 r + k / NPL
+				double yv = 0.0, yw = 0.0;
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) {
+					const double lo_v = __shfl(x[i], 16 * r + lane / NPL, 64);
+					if (lane % NPL == i) yv = lo_v;
+					if (S == 128) {
+						const double hi_v = __shfl(x[i], 16 * r + (64 + lane) / NPL, 64);
+						if (lane % NPL == i) yw = hi_v;
+					}
+				}
+				const double *xm = bentry + (int64_t)(t - 1) * S;
+				const double xv = xm[lane], xw = S == 128 ? xm[64 + lane] : 0.0;
+				m = rel_mismatch_vals<S>(xv, yv, xw, yw, false);
+			}
+			if (lane == 0) verify_commit(t - 1, check, m, tv.tol, tv.dirty, tv.cnt, tv.warm, tv.mis);
+		}
+	}
+}
 #ifdef PSMC_TRACE_SWEEP
 __device__ unsigned long long g_trace_c[4 * 8192];
 #endif
@@ -114,7 +165,7 @@ __global__ __launch_bounds__(64, 1) void k_bwd_count4f_struct(const double *__re
                                                                 double *__restrict__ bentry, double *__restrict__ bexit,
                                                                 double *__restrict__ Cpart,
                                                                 double *__restrict__ Epart, const int *__restrict__ touch_f,
-                                                                const int *__restrict__ touch_b, const int *__restrict__ fmerge, const double *__restrict__ finv)
+                                                                const int *__restrict__ touch_b, const int *__restrict__ fmerge, const double *__restrict__ finv, const TailVerify tv)
 {
 	__shared__ double lds_e[4 * SF], lds_m[8]; // e rows: hom, het, 1, 1;  count masks per symbol
 	const int lane = threadIdx.x, row = lane >> 4, m = lane & 15, k0 = NPLF * m;
@@ -251,6 +302,7 @@ __global__ __launch_bounds__(64, 1) void k_bwd_count4f_struct(const double *__re
 		const double zero[NPLF] = {0.0, 0.0, 0.0, 0.0};
 		storeN<NPLF>(os, S[0]); storeN<NPLF>(os + SF, S[1]); storeN<NPLF>(os + 2 * SF, zero); // missing symbols are not counted (khmm.c:355)
 	}
+	if (tv.dirty != nullptr) tail_verify<NPLF, SF>(tv, chunks, tile, valid, work, from_above, x, bentry, bexit, lane);
 }
 
 constexpr int NPL8 = 8, S8 = 128;
@@ -339,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void k_bwd_count8x_struct(const double *__r
                                                                  double *__restrict__ bentry, double *__restrict__ bexit,
                                                                  double *__restrict__ Cpart,
                                                                  double *__restrict__ Epart, const int *__restrict__ touch_f,
-                                                                 const int *__restrict__ touch_b)
+                                                                 const int *__restrict__ touch_b, const TailVerify tv)
 {
 	__shared__ d2v_t lds_e[4 * 64];   // emission rows hom | het | 1 | 1 in the load8p layout
 	__shared__ double lds_m[8];
@@ -490,10 +542,11 @@ __global__ __launch_bounds__(256, 1) void k_bwd_count8x_struct(const double *__r
 		const double zero[NPL8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 		storeN<NPL8>(os, S[0]); storeN<NPL8>(os + S8, S[1]); storeN<NPL8>(os + 2 * S8, zero); // missing symbols are not counted (khmm.c:355)
 	}
+	if (tv.dirty != nullptr) tail_verify<NPL8, S8>(tv, chunks, tile, valid, work, from_above, x, bentry, bexit, lane); // (each wave: its own four tiles)
 }
 
 // list 0 / 1: tile list A / B of the plan (api_fast.hip build_items);  redo: only the groups a repair touched
-void launch_bwd_count(const EstepLaunch &p, hipStream_t st, int list, bool redo, bool all_from_bentry)
+void launch_bwd_count(const EstepLaunch &p, hipStream_t st, int list, bool redo, bool all_from_bentry, bool verify)
 {
 	const int G = p.count_group; // tiles per work-group / per C partial: 4, or 16 (k_bwd_count8x_struct)
 	const int ga = (p.n_list_a + G - 1) / G, gb = (p.n_list_b + G - 1) / G;
@@ -501,14 +554,16 @@ void launch_bwd_count(const EstepLaunch &p, hipStream_t st, int list, bool redo,
 	if (n_groups <= 0) return;
 	const int *tl = p.d_ftiles + (list == 0 ? 0 : G * ga);
 	const int g0 = list == 0 ? 0 : ga, md = all_from_bentry ? 3 : (redo ? 2 : 0); // 3 (diagnostic): every group, every tile from its bentry
+	TailVerify tv = {nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0};
+	if (verify && md == 0) tv = {p.d_vcover, p.d_dirty_b, p.d_cnt + 1, p.d_warm + 1, p.m_mis ? p.m_mis + p.n_chunks : nullptr, p.tol, p.n_chunks};
 	if (p.ns == 128) {
 		hipLaunchKernelGGL(k_bwd_count8x_struct, dim3(n_groups), dim3(256), 0, st, p.d_sp, p.d_e, p.d_s, p.d_obs, p.d_chunks, tl, g0, md,
-		                   p.d_f, p.d_bentry, p.d_bexit, p.d_Cpart, p.d_Epart, p.d_touch_f, p.d_touch_b);
+		                   p.d_f, p.d_bentry, p.d_bexit, p.d_Cpart, p.d_Epart, p.d_touch_f, p.d_touch_b, tv);
 		PSMC_DBG("launch_bwd_count (128 states)", list, redo, n_groups);
 		return;
 	}
 	hipLaunchKernelGGL(k_bwd_count4f_struct, dim3(n_groups), dim3(64), 0, st, p.d_sp, p.d_e, p.d_s, p.d_obs, p.d_chunks, tl, g0, md,
-	                   p.d_f, p.d_bentry, p.d_bexit, p.d_Cpart, p.d_Epart, p.d_touch_f, p.d_touch_b, p.merge ? p.d_fmerge : nullptr, p.d_finv);
+	                   p.d_f, p.d_bentry, p.d_bexit, p.d_Cpart, p.d_Epart, p.d_touch_f, p.d_touch_b, p.merge ? p.d_fmerge : nullptr, p.d_finv, tv);
 	PSMC_DBG("launch_bwd_count", list, redo, n_groups);
 }
 

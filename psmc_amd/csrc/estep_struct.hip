@@ -1057,9 +1057,16 @@ __global__ __launch_bounds__(64) void k_sweep_struct(const double *__restrict__ 
 // host_out / host_cnt are host-mapped pinned memory: the host learns the count (and the list) without a
 // copy command, which would be a blit kernel queued behind whatever is running
 __global__ __launch_bounds__(64) void k_compact(const int *__restrict__ dirty, int n, SweepItem *__restrict__ out,
-                                                  SweepItem *__restrict__ host_out, int *__restrict__ host_cnt)
+                                                  SweepItem *__restrict__ host_out, int *__restrict__ host_cnt, const int *__restrict__ counted)
 {
 	const int lane = threadIdx.x;
+	// counted ("tail" = 1, estep_fused.hip tail_verify): the flags' writers have counted them already; an all-clear round -- nearly every one --
+	// has no list to build and only hands that zero to the host
+	if (counted != nullptr && *counted == 0) {
+		if (lane == 0) *host_cnt = 0;
+		__threadfence_system();
+		return;
+	}
 	int base = 0;
 	for (int i0 = 0; i0 < n; i0 += 64) {
 		const int i = i0 + lane;
@@ -1144,11 +1151,11 @@ void launch_phase1_queue(const EstepLaunch &p, hipStream_t st, int ff, int nf, i
 #undef PSMC_LQ
 	PSMC_DBG("launch_phase1_queue", nf, nb, p.q_grid);
 }
-void launch_compact(const EstepLaunch &p, hipStream_t st, bool bwd)
+void launch_compact(const EstepLaunch &p, hipStream_t st, bool bwd, bool counted)
 {
 	hipLaunchKernelGGL(k_compact, dim3(1), dim3(64), 0, st, bwd ? p.d_dirty_b : p.d_dirty, p.n_chunks,
 	                   (SweepItem *)(bwd ? p.d_ritems_b : p.d_ritems_f),
-	                   (SweepItem *)(p.m_ritems ? p.m_ritems + (size_t)(bwd ? 1 : 0) * 2 * p.n_chunks : nullptr), p.m_cnt + (bwd ? 1 : 0));
+	                   (SweepItem *)(p.m_ritems ? p.m_ritems + (size_t)(bwd ? 1 : 0) * 2 * p.n_chunks : nullptr), p.m_cnt + (bwd ? 1 : 0), counted ? p.d_cnt + (bwd ? 1 : 0) : nullptr);
 	PSMC_DBG("verify + launch_compact", bwd, p.n_chunks, 0);
 }
 // bulk of both sweeps in one grid: forward items [ff, ff+nf) and backward items [fb, fb+nb); top_only: the backward

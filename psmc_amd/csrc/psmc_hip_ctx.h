@@ -166,7 +166,11 @@ struct psmc_hip_ctx {
 	int items_two_phase = -1;  // what the current item lists were built for
 	int runs_late = 1;         // "runs_late": two-phase plan, 1 = run tiles go to the second launch of the fused back half
 	bool runs_in_b = false;    // two-phase plan: every tile of a glued run is in the second list of the fused back half (build_items)
-	int *d_ftiles = nullptr;   // [2 * (n_tiles + 4)] tile lists A | B of the fused back half (bit 30: start from the tile above)
+	int *d_ftiles = nullptr;   // [2 * (chunk_cap + 16)] tile lists A | B of the fused back half (bit 30: start from the tile above), then [chunk_cap]
+	                           // who tests each backward boundary ("tail" = 1: TailVerify::cover, psmc_hip_internal.h)
+	size_t vcover_off = 0;     // ... where that table starts in d_ftiles (ints)
+	int tail = 1;              // "tail": fused back half, 1 = the counts waves verify the backward boundaries and the reductions follow the counts
+	                           // directly, list A's half beside list B (estep_fast.hip launch_fast); 0 = verify, compaction and reductions behind list B
 	FastReport report = {0, 0, 0, 0, 1, 0, 0};
 	double *d_stage = nullptr, *d_stats = nullptr;
 	unsigned long long *d_warm = nullptr;

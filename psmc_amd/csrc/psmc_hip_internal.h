@@ -29,6 +29,61 @@ constexpr int CHUNK_ANCHOR_F = 1; // forward speculation started at the true seg
 constexpr int CHUNK_ANCHOR_B = 2; // backward speculation started at the true segment end: exact
 constexpr int CHUNK_LAST = 4;     // last tile of its segment
 
+// ---- The boundary test of the verify step, shared by k_verify (estep_fast.hip) and by the epilogue of the fused counts kernels
+// (estep_fused.hip, "tail" = 1): one wave per pair, lane = state (S = 128: lane and lane + 64).  Both callers must produce the same bits,
+// so the arithmetic lives here and nowhere else.
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+	for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
+	return v;
+}
+__device__ __forceinline__ double wave_add(double v) {
+#pragma unroll
+	for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+	return v;
+}
+// max_k |x/|x| - y/|y|| / max_k (y/|y|) over S = 64 or 128 states, |.| = sum: boundary vectors are compared as DIRECTIONS (a vector from
+// the transfer-matrix chain has an arbitrary scale; every consumer -- per-position normaliser of the counts, k_ll -- is scale-free).
+// xv, yv: state `lane` of the two vectors; xw, yw: state lane + 64 (S = 128 only).  NaN-safe: a NaN anywhere yields +inf.
+template <int S> __device__ __forceinline__ double rel_mismatch_vals(double xv, double yv, double xw, double yw, bool with_scale) {
+	if (S != 128) { xw = 0.0; yw = 0.0; }
+	const double sx = wave_add(xv + xw), sy = wave_add(yv + yw);
+	const double ix = 1.0 / sx, iy = 1.0 / sy;
+	double num = fabs(xv * ix - yv * iy), den = fabs(yv * iy);
+	if (with_scale) num = fmax(num, fabs(sx - sy) * iy * den); // the two vectors themselves, not only their directions
+	bool bad = (xv != xv) || (yv != yv) || (ix != ix) || (iy != iy);
+	if (S == 128) {
+		num = fmax(num, fabs(xw * ix - yw * iy)); den = fmax(den, fabs(yw * iy));
+		bad = bad || (xw != xw) || (yw != yw);
+	}
+	num = wave_max(num); den = wave_max(den);
+	return __any(bad) ? __builtin_inf() : num / den;
+}
+// does the backward verify compare tile b's start vector (bentry[b]) with the exit vector of tile b + 1?
+__device__ __forceinline__ bool verify_check_bwd(const Chunk &c, int b, int n_chunks) {
+	return !(c.flags & (CHUNK_ANCHOR_B | CHUNK_LAST)) && min(c.hi, c.L - 1) >= c.lo && b + 1 < n_chunks;
+}
+// what ONE lane of the wave that tested tile b leaves: the flag, the flagged count, the mismatch itself (mis: host-mapped, first verify
+// of an E-step, may be null) and the largest mismatch of the round (warm: the direction's own word)
+__device__ __forceinline__ void verify_commit(int b, bool check, double m, double tol, int *__restrict__ dirty, int *__restrict__ cnt,
+                                              unsigned long long *__restrict__ warm, double *__restrict__ mis) {
+	const int bad = check && !(m <= tol);
+	dirty[b] = bad;
+	if (bad) atomicAdd(cnt, 1);
+	if (mis) mis[b] = check ? m : -1.0;
+	if (check) atomicMax(warm, (unsigned long long)__double_as_longlong(m));
+}
+// "tail" = 1: where the fused counts kernels leave the backward verify of round 0 (dirty == nullptr: they do not)
+struct TailVerify {
+	const int *cover; // [n_chunks] who tests the pair (b, b + 1): 0 = k_verify, 1 = the wave that computes tile b + 1, 2 = tile b's own wave
+	                  // (a from-above tile: it starts from the very vector it is compared with).  api_fast.hip build_items
+	int *dirty, *cnt; // d_dirty_b, d_cnt + 1
+	unsigned long long *warm; // d_warm + 1
+	double *mis;      // the backward half of m_mis, or null
+	double tol;
+	int n_chunks;
+};
+
 // Exact mode: the list of sweeps of one launch, one entry per (parameter set, segment).  A single E-step has one
 // parameter set and keeps every segment's tables at the segment's own offset (par == tab == nullptr); a batch
 // (psmc_hip_estep_batch) gives each entry its parameter-set index and its own table slot.
@@ -89,6 +144,9 @@ struct EstepLaunch {
 	const int *d_ftiles; int n_list_a, n_list_b; // fused back half: tile lists A | B (each padded to a multiple of 4 with -1)
 	int count_group;                  // ... tiles per work-group of the fused back half (one C partial each): 4; 16 = k_bwd_count8x_struct (128 states, "fuse128" = 2)
 	int runs_in_b;                    // ... and every tile of a glued run is in list B: only the second launch waits for the runs' path
+	int tail;                         // fused == 1, overlapped: 1 = the counts waves test the backward boundaries themselves and the reductions do not
+	                                  // wait for the verify (launch_fast, the optimistic tail); 0 = verify and reductions behind list B
+	const int *d_vcover;              // ... [n_chunks] who tests the pair (b, b + 1): TailVerify::cover
 	hipStream_t stream4, stream5;
 	// walks: heads of the chain runs (count 1) followed by the short runs; transfer-matrix chains of the long runs
 	const int *d_wl_f, *d_wl_b; int n_wl_f, n_wl_b;
@@ -160,7 +218,7 @@ int launch_post_counts_wide(hipStream_t st, const double *f, const double *b, co
 int launch_fast(const EstepLaunch &p, FastReport *rep);
 void launch_fwd_struct(const EstepLaunch &p, hipStream_t st, int which, int first, int n_items);
 void launch_bwd_struct(const EstepLaunch &p, hipStream_t st, int which, int first, int n_items);
-void launch_compact(const EstepLaunch &p, hipStream_t st, bool bwd);
+void launch_compact(const EstepLaunch &p, hipStream_t st, bool bwd, bool counted = false); // counted: d_cnt already holds the number of flags (an all-clear round writes only that)
 void launch_gather_prev(const EstepLaunch &p, hipStream_t st, int first, int n_items, double *prevx); // estep_struct.hip
 int launch_tile_allmiss(hipStream_t st, const uint8_t *d_obs, const Chunk *d_chunks, int n_chunks, int *d_flags); // estep_struct.hip
 void launch_walks(const EstepLaunch &p, hipStream_t st);
@@ -169,7 +227,7 @@ int walk_blocks(const EstepLaunch &p);
 void launch_kchain(const EstepLaunch &p, hipStream_t st_cols, hipStream_t st_chain, hipEvent_t ev_cols);
 void launch_sweeps(const EstepLaunch &p, hipStream_t st, int ff, int nf, int fb, int nb, bool top_only);
 void launch_phase1_queue(const EstepLaunch &p, hipStream_t st, int ff, int nf, int fb, int nb);
-void launch_bwd_count(const EstepLaunch &p, hipStream_t st, int list, bool redo, bool all_from_bentry = false);
+void launch_bwd_count(const EstepLaunch &p, hipStream_t st, int list, bool redo, bool all_from_bentry = false, bool verify = false); // verify: the waves test the backward boundaries (TailVerify; mode 0 only)
 void launch_bwd_acc(const EstepLaunch &p, hipStream_t st, int which, int first, int n);
 void launch_reduce_factored(const EstepLaunch &p, hipStream_t st);
 int launch_post_decode(hipStream_t st, const double *f, const double *b, const double *s, int64_t off, int L, int n,
