@@ -15,10 +15,11 @@
  * fast mode runs the structured sweeps for matrices of the PSMC form and psmc_hip_estep falls back to the exact kernels for
  * any other matrix; 129..1024 (`psmc -p "100*2"`): the wide exact kernels of estep_wide.hip whatever the mode -- psmc_hip_estep,
  * _estep_segments, _estep_batch, the table readers and the decoding entry points; the device-resident and factored fast entry
- * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 a fast-mode context of 129..256 states runs
- * psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip (PSMC-form matrices; full
- * counts, batch and psmc_hip_get_tables stay exact, and so does decoding unless "wide_decode" = 1 is set as well: see
- * "Decoding on a FAST context");
+ * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 or 2 a fast-mode context of 129..256 states
+ * runs psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip, and with "wide_fast" = 2 one
+ * of 257..1024 states runs them on the multi-wave kernels of estep_wide_fast_mw.hip (PSMC-form matrices; full
+ * counts, batch and psmc_hip_get_tables stay exact, and so does decoding unless, up to 256 states, "wide_decode" = 1 is set as
+ * well: see "Decoding on a FAST context");
  * row-major FP64; a[k*n+l]=P(k->l) (khmm.h:34); e[b*n+k], b=0 hom / 1 het
  * (khmm.h:34; the missing-data row e[2][*]=1 of khmm.c:21 is implied);
  * a0[k] (khmm.h:36); observations are bytes 0/1/2 exactly as psmc_read_seq
@@ -35,14 +36,15 @@ extern "C" {
 #define PSMC_HIP_MODE_FAST  1 /* tiled speculative sweeps, FMA/MFMA, tree reductions; stats within 1e-10 */
 
 #define PSMC_HIP_MAX_STATES 1024 /* exact mode; the fast kernels cover up to 128 states (beyond: a fast-mode context runs the exact ones),
-                                    and the factored statistics up to 256 with the option "wide_fast" */
+                                    and the factored statistics up to 256 with the option "wide_fast" = 1, up to 1024 with "wide_fast" = 2 */
 
 #define PSMC_HIP_OK        0
 #define PSMC_HIP_EINVAL   -1 /* bad argument (NULL, n out of range, empty segment ...) */
 #define PSMC_HIP_ENOMEM   -2 /* host or device allocation failed */
 #define PSMC_HIP_EDEVICE  -3 /* HIP runtime error; see psmc_hip_last_error() */
 #define PSMC_HIP_ENOTSUP  -4 /* not supported in this build (n > 1024; the device-resident / factored fast entry points with n > 128 -- the
-                                factored ones with n > 256 when "wide_fast" is set -- or with n > 64 and a matrix without the PSMC form) */
+                                factored ones with n > 256 when "wide_fast" is 1; "wide_fast" = 2 covers them all -- or with n > 64 and a
+                                matrix without the PSMC form) */
 #define PSMC_HIP_ESTATE   -5 /* call order violated (no segments loaded ...) */
 #define PSMC_HIP_ECONVERGE -6 /* fast mode: tile boundaries did not converge within max_rounds */
 
@@ -82,12 +84,19 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           do up to 128 states.  It keeps an X table of its own: 8 x 192 or 8 x 256 bytes per bin
  *                           (46 / 61 GB at 30 M bins), beside the exact tables.  psmc_hip_estep, the batch, psmc_hip_get_tables and
  *                           (without "wide_decode") the decoding entry points stay on the exact kernels, bit for bit.  Exact mode and
- *                           <= 128 states: no effect
+ *                           <= 128 states: no effect.
+ *                           2: the same at 129..256 states (the same kernels, the same bits as 1), and a fast-mode context of 257..1024
+ *                           states runs them on the kernels of estep_wide_fast_mw.hip: a tile is one work-group of 2, 3 or 4 waves
+ *                           (padded widths 512, 768, 1024: 64 lanes x 4 states per wave), the waves exchange their scan totals through
+ *                           LDS once per position.  Plan, options, ENOTSUP / ECONVERGE and diagnostics as for 1; the X table is 8 x 512,
+ *                           8 x 768 or 8 x 1024 bytes per bin (PSMC_HIP_ENOMEM, with the table's size in the message, when it does
+ *                           not fit).  Everything else such a context does, decoding included, stays on the exact kernels.
+ *                           Other values: PSMC_HIP_EINVAL
  *  "wide_decode"   0        1, with "wide_fast" = 1 on a fast-mode context of 129..256 states: psmc_hip_decode, _posterior, _post_counts
  *                           and _scales read what the LAST single E-step left -- after a wide fast factored E-step its X table and
  *                           converged tile boundaries (estep_wide_post.hip, no backward table), after psmc_hip_estep the exact tables,
  *                           bit for bit (see "Decoding on a FAST context").  0: the exact tables whatever E-step ran last, as before
- *                           the option existed.  Anywhere else: no effect
+ *                           the option existed.  Anywhere else, beyond 256 states included ("wide_fast" = 2): no effect
  *  "merge"         0        1: a forward FIX pass between the forward sweep and the back half (64 states, fused back half): every tile's start
  *                           vector is checked there, and a tile that fails is rewritten from the true vector until its trajectory has the
  *                           direction of the stored one again (the factor between the two parts is kept for the counts and the likelihood) --
@@ -279,7 +288,7 @@ int psmc_hip_fast_diag(psmc_hip_ctx *ctx, double *warm_err_fwd, double *warm_err
 /* How much repair the speculation needed: verify/repair rounds and the total
  * number of tile re-runs, forward and backward, out[0..3]; out[4] = tiles
  * the forward fix pass rewrote in part ("merge"),
- * out[5] = 1 when a second pass of the counts had to run, 2 when the E-step was one of the wide path ("wide_fast", 129..256
+ * out[5] = 1 when a second pass of the counts had to run, 2 when the E-step was one of the wide path ("wide_fast": 129..256, with the value 2 up to 1024
  * states: out[0..3] are then its verify / repair rounds and the head tiles the repairs started from, out[4] = 0). */
 int psmc_hip_fast_repairs(psmc_hip_ctx *ctx, int out[6]);
 /* Diagnostic: the plan the NEXT fast E-step of this context will run with: out = {tiles, tile length in bins, mean forward
@@ -291,7 +300,7 @@ int psmc_hip_fast_plan(psmc_hip_ctx *ctx, double out[8]);
  * N x N counts.  The EM objective needs of A only  SL_k = sum_{l<k} A[k][l],  SU_k = sum_{l>k} A[k][l],
  * DG_k = A[k][k],  CL_l = sum_{k>l} A[k][l],  CU_l = sum_{k<l} A[k][l]  (psmc_amd/host/mstep.c); they come out
  * of the backward sweep in O(N) per bin.  sums = SL | SU | DG | CL | CU (5n), E as in psmc_hip_estep (2n).
- * PSMC_HIP_ENOTSUP when the matrix does not have the form.  129..256 states: with the option "wide_fast" only (see there).
+ * PSMC_HIP_ENOTSUP when the matrix does not have the form.  129..256 states: with the option "wide_fast" only, 257..1024 states: with "wide_fast" = 2 only (see there).
  * Replaces em.c:33-55 + the reads of hmm_Q. */
 int psmc_hip_estep_factored(psmc_hip_ctx *ctx, const double *a, const double *e, const double *a0, double *sums,
                             double *E, double *LL);

@@ -735,7 +735,7 @@ extern "C" int psmc_hip_estep_factored(psmc_hip_ctx *c, const double *a, const d
 	if (!c || !a || !e || !a0) return fail(c, PSMC_HIP_EINVAL, "estep_factored: bad argument");
 	if (c->mode != PSMC_HIP_MODE_FAST) return fail(c, PSMC_HIP_ENOTSUP, "estep_factored: fast mode only");
 	HIPCHK(c, hipSetDevice(c->device));
-	if (c->ns > 128 && c->wide_fast) return estep_factored_wide(c, a, e, a0, sums, E, LL); // 129..256 states (api_wide_fast.hip)
+	if (c->ns > 128 && c->wide_fast) return estep_factored_wide(c, a, e, a0, sums, E, LL); // 129..256 states, 257..1024 with "wide_fast" = 2 (api_wide_fast.hip)
 	int rc;
 	if ((rc = ensure_fast_buffers(c))) return rc; // d_stats must exist before the first enqueue (the plan follows stage_params)
 	c->want_factored = true;
@@ -769,7 +769,7 @@ extern "C" int psmc_hip_estep_factored_device(psmc_hip_ctx *c, const double *a, 
 extern "C" int psmc_hip_fast_info(psmc_hip_ctx *c, int out[8])
 {
 	if (!c || !out) return PSMC_HIP_EINVAL;
-	if (c->wf_ran) { // the wide path (129..256 states): one tile per wave, no items
+	if (c->wf_ran) { // the wide path (129..256 states: one tile per wave; 257..1024: one per work-group): no items
 		const int nc = (int)c->wf_chunks.size();
 		out[0] = 1; out[1] = c->wf_T; out[2] = nc; out[3] = nc; out[4] = 3; out[5] = 0; out[6] = 1; out[7] = 0;
 		return PSMC_HIP_OK;

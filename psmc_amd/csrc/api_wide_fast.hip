@@ -1,6 +1,8 @@
 // api_wide_fast.hip -- fast mode beyond 128 states: the factored statistics of psmc_hip_estep_factored[_device] at 129..256
-// states with the option "wide_fast" = 1 (kernels: estep_wide_fast.hip).  With "wide_decode" = 1 the decoding entry points read
-// what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip).  Everything else a context of that size does --
+// states with the option "wide_fast" = 1 or 2 (kernels: estep_wide_fast.hip, one wave per tile) and at 257..1024 states with
+// "wide_fast" = 2 (kernels: estep_wide_fast_mw.hip, 2..4 waves per tile at the padded widths 512, 768 and 1024; plan, rounds and
+// options are the same, only WideLaunch knows the width and the waves).  With "wide_decode" = 1 the decoding entry points read
+// what such an E-step left at up to 256 states (api_decode.hip; kernels: estep_wide_post.hip).  Everything else a context of that size does --
 // psmc_hip_estep, the batch, psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide
 // exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
 //
@@ -15,6 +17,11 @@
 
 static constexpr int WF_PAR = 8; // e0 | e1 | a0 | P | R | qa | c | dd (wide_fast.h)
 static constexpr int WF_NACC = 7; // SL SU DG CL CU E0 E1 per tile
+
+// the padded width of the path's own tables: c->ns (192 or 256) up to 256 states, beyond them the next multiple of 256 -- one wave
+// of the tile per 256 states (c->ns stays what the wide exact kernels pad to, a multiple of 64)
+static int wf_width(const psmc_hip_ctx *c) { return c->n <= 256 ? c->ns : 256 * ((c->n + 255) / 256); }
+static int wf_waves(const psmc_hip_ctx *c) { return c->n <= 256 ? 1 : (c->n + 255) / 256; }
 
 void free_wide_fast(psmc_hip_ctx *c)
 {
@@ -54,7 +61,7 @@ static int plan_wide(psmc_hip_ctx *c)
 			c->wf_chunks.push_back(ch);
 		}
 	}
-	const int nc = (int)c->wf_chunks.size(), S = c->ns;
+	const int nc = (int)c->wf_chunks.size(), S = wf_width(c);
 	int rc;
 	if (nc > c->wf_cap) {
 		if ((rc = dev_alloc(c, &c->d_wf_chunks, (size_t)nc))) return rc;
@@ -108,7 +115,7 @@ static int wide_rounds(psmc_hip_ctx *c, WideLaunch &w, bool bwd, int &rounds, in
 int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t ust)
 {
 	char msg[320];
-	if (c->ns > 256) {
+	if (c->n > 256 && c->wide_fast < 2) {
 		snprintf(msg, sizeof msg, "estep_factored: the wide fast path (\"wide_fast\") covers 129..256 states; %d states run on the exact kernels only (psmc_hip_estep)", c->n);
 		return fail(c, PSMC_HIP_ENOTSUP, msg);
 	}
@@ -116,7 +123,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	HIPCHK(c, hipSetDevice(c->device));
 	// this is the context's last single E-step from now on; until it has succeeded there is nothing to decode (api_decode.hip decode_source)
 	c->wd_kind = WD_FAILED; c->wd_serial = c->tab_serial; c->wd_sel = c->sel_serial;
-	const int n = c->n, S = c->ns;
+	const int n = c->n, S = wf_width(c);
 	std::vector<double> sp((size_t)5 * n);
 	if (!c->struct_opt) // as up to 128 states: the factored statistics come from the structured sweeps only
 		return fail(c, PSMC_HIP_ENOTSUP, "estep_factored: the factored statistics need the structured sweeps (option \"structured\" is 0)");
@@ -131,8 +138,13 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	if (!c->d_wf_par && (rc = dev_alloc(c, &c->d_wf_par, (size_t)WF_PAR * S))) return rc;
 	if ((c->plan_dirty || c->wf_chunks.empty()) && (rc = plan_wide(c))) return rc;
 	const int64_t bins = c->total + 128;
-	if (c->wf_bins < bins) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins)
-		if ((rc = dev_alloc(c, &c->d_wf_X, (size_t)bins * S))) { c->wf_bins = 0; return rc; }
+	if (c->wf_bins < bins) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins; 8 KB per bin at S = 1024)
+		if ((rc = dev_alloc(c, &c->d_wf_X, (size_t)bins * S))) {
+			c->wf_bins = 0;
+			snprintf(msg, sizeof msg, "estep_factored: no device memory for the X table of the wide fast path: %lld bytes (%lld bins x %d padded states x 8)",
+			         (long long)bins * S * 8, (long long)bins, S);
+			return fail(c, PSMC_HIP_ENOMEM, msg);
+		}
 		if ((rc = dev_alloc(c, &c->d_wf_inv, (size_t)bins))) { c->wf_bins = 0; return rc; }
 		c->wf_bins = bins;
 	}
@@ -149,6 +161,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	WideLaunch w;
 	memset(&w, 0, sizeof(w));
 	w.stream = st; w.ns = S; w.n_states = n; w.n_tiles = (int)c->wf_chunks.size(); w.chain = c->learn ? 1 : 0;
+	w.waves = wf_waves(c);
 	w.tol = c->warm_tol; w.tiny_total = (double)c->sel.size() * HMM_TINY_H;
 	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks; w.list = c->d_wf_list; w.dirty = c->d_wf_dirty;
 	w.cnt = c->d_cnt; w.warm = c->d_warm;

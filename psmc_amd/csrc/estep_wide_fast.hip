@@ -386,6 +386,7 @@ template <int NPL> static int launch_all(const WideLaunch &w, int what, int n_li
 
 int launch_wide_fast(const WideLaunch &w, int what, int n_list)
 {
+	if (w.waves > 1) return launch_wide_fast_mw(w, what, n_list); // 257..1024 states: estep_wide_fast_mw.hip
 	if (w.ns == 192) return wide::launch_all<3>(w, what, n_list);
 	if (w.ns == 256) return wide::launch_all<4>(w, what, n_list);
 	return -1;

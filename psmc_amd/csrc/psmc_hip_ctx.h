@@ -1,7 +1,7 @@
 // psmc_hip_ctx.h -- the context behind the C-ABI of include/psmc_hip.h and the helpers its translation units share:
 //   api.hip        context, options, segments, parameter staging, tables, exact mode, the table reader
 //   api_fast.hip   fast mode: tile plan, sweep items, learning, the launch of one fast E-step and its entry points
-//   api_wide_fast.hip  fast mode at 129..256 states ("wide_fast"): plan, rounds and launch of the factored E-step
+//   api_wide_fast.hip  fast mode at 129..256 states ("wide_fast") and 257..1024 states ("wide_fast" = 2): plan, rounds and launch of the factored E-step
 //   api_decode.hip psmc_hip_decode / _posterior / _post_counts / _scales from the exact, the fast or the wide fast tables
 //   api_batch.hip  psmc_hip_estep_batch (bootstrap replicates): exact launch groups, fast per-replicate plans
 //   api_probes.hip device self-test, microbenchmarks and probes (diagnostics)
@@ -221,14 +221,15 @@ struct psmc_hip_ctx {
 	// [4] launch_fast (kernels + verify / repair rounds, synchronous), [5] result read-back; and [6] repair rounds, [7] repaired tiles
 	double dbg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	// fast mode beyond 128 states (api_wide_fast.hip): "wide_fast" = 1 runs psmc_hip_estep_factored[_device] of a fast context with 129..256
-	// states on the kernels of estep_wide_fast.hip, in tables of its own (the exact tables stay what the last exact E-step left)
+	// states on the kernels of estep_wide_fast.hip, in tables of its own (the exact tables stay what the last exact E-step left);
+	// "wide_fast" = 2: the same, and 257..1024 states on the multi-wave kernels of estep_wide_fast_mw.hip
 	int wide_fast = 0;
 	bool wf_ran = false;                 // the last fast E-step of this context was one of the wide path (fast_info, fast_diag)
 	std::vector<Chunk> wf_chunks;        // its plan; rebuilt when plan_dirty
 	Chunk *d_wf_chunks = nullptr;
 	int wf_cap = 0, wf_T = 0, wf_W = 0;  // tiles allocated; tile length and warm-up of the plan
 	bool warmup_set = false;             // "warmup" was set: the wide path takes it instead of its own default (api_wide_fast.hip)
-	double *d_wf_X = nullptr, *d_wf_inv = nullptr; int64_t wf_bins = 0; // X [bins][ns], 1/d_p [bins]
+	double *d_wf_X = nullptr, *d_wf_inv = nullptr; int64_t wf_bins = 0; // X [bins][padded width of the path: ns up to 256 states, 512 / 768 / 1024 beyond], 1/d_p [bins]
 	double *d_wf_par = nullptr, *h_wf_par = nullptr;                     // e0 | e1 | a0 | P | R | qa | c | dd
 	double *d_wf_entry = nullptr, *d_wf_bentry = nullptr, *d_wf_bexit = nullptr, *d_wf_part = nullptr, *d_wf_ll = nullptr;
 	int *d_wf_dirty = nullptr, *d_wf_list = nullptr;

@@ -1,5 +1,6 @@
-// wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states)
-// and of estep_wide_post.hip (decoding from the tables that E-step left).
+// wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states:
+// one wave per tile), of estep_wide_fast_mw.hip (257..1024 states: 2..4 waves per tile) and of estep_wide_post.hip (decoding from
+// the tables the one-wave E-step left).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "psmc_hip_internal.h"
@@ -10,7 +11,8 @@ enum { WF_FWD, WF_FWD_REPAIR, WF_BWARM, WF_ACC, WF_ACC_REPAIR, WF_VERIFY_F, WF_V
 
 struct WideLaunch {
 	hipStream_t stream;
-	int ns, n_states, n_tiles, chain; // ns: padded states, 192 or 256; chain: repairs walk on through glued runs
+	int ns, n_states, n_tiles, chain; // ns: padded states, 192 or 256 (one wave per tile), 512, 768 or 1024 (waves = 2, 3, 4); chain: repairs walk on through glued runs
+	int waves;                        // waves per tile: 1, or ns / 256 on the multi-wave path
 	double tol, tiny_total;
 	const double *par;                // e0 | e1 | a0 | P | R | qa | c | dd, ns doubles each
 	const uint8_t *obs;
@@ -21,7 +23,8 @@ struct WideLaunch {
 	double *X, *inv, *entry, *bentry, *bexit, *part, *LLpart, *stage, *out;
 };
 
-int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip
+int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip (waves > 1: hands on to the next)
+int launch_wide_fast_mw(const WideLaunch &w, int what, int n_list);  // estep_wide_fast_mw.hip
 
 // decoding of ONE segment: its tiles are t0 .. t0 + n_tiles - 1 of the plan; every output pointer is the segment's own buffer
 enum { WP_PATH, WP_POST, WP_REC, WP_POST_REC, WP_COUNTS, WP_SCALES };

@@ -8,6 +8,8 @@
  *                                    (option "wide_fast"); without it such a run is an exact run throughout, and so it is with
  *                                    -d/-D/-c/-s unless PSMC_HIP_DECODE=fast is set too: the EM rounds then stay on the wide fast
  *                                    path and the decoding reads its tables (option "wide_decode")
+ *   PSMC_HIP_WIDE=fast-all           the same, and at 257..1024 states the factored fast E-steps of the multi-wave wide fast path
+ *                                    ("wide_fast" = 2); a decoding run beyond 256 states stays on the exact kernels throughout
  *   PSMC_HIP_DEVICE=<index>          one GPU
  *   PSMC_HIP_DEVICES=<i>,<j>,...     the segments of every E-step sharded over these GPUs (psmc_hip_group_*: LPT
  *                                    partition, one RCCL all-reduce of the statistics per EM iteration in fast mode,
@@ -50,7 +52,8 @@ int main(int argc, char *argv[])
 	 * lets the decoding read that path's tables; otherwise it needs the exact ones) */
 	const char *wide_s = getenv("PSMC_HIP_WIDE"), *dec_s = getenv("PSMC_HIP_DECODE");
 	const int decoding = o.decode || o.print_prob || o.cnt_file;
-	const int plan = psmc_mode_plan(mode_is_fast(), wide_s && strcmp(wide_s, "fast") == 0, dec_s && strcmp(dec_s, "fast") == 0, n_states, decoding);
+	const int wide_level = !wide_s ? 0 : (strcmp(wide_s, "fast-all") == 0 ? 2 : (strcmp(wide_s, "fast") == 0 ? 1 : 0));
+	const int plan = psmc_mode_plan(mode_is_fast(), wide_level, dec_s && strcmp(dec_s, "fast") == 0, n_states, decoding);
 	const int wide_fast = (plan & PSMC_PLAN_WIDE) != 0;
 	const char *mode_s = getenv("PSMC_HIP_MODE"), *dev_s = getenv("PSMC_HIP_DEVICE");
 	int mode = (mode_s && strcmp(mode_s, "fast") == 0) ? PSMC_HIP_MODE_FAST : PSMC_HIP_MODE_EXACT;
@@ -73,9 +76,9 @@ int main(int argc, char *argv[])
 	const int use_factored = o.fast_mstep && mode == PSMC_HIP_MODE_FAST && (n_states <= 128 || wide_fast) && !(fs && atoi(fs) == 0);
 	/* (PSMC_FACTORED=0 or PSMC_FAST_MSTEP=0 ask for full counts, which beyond 128 states only the exact kernels compute) */
 	if (wide_fast && use_factored && (plan & PSMC_PLAN_WIDE_DECODE))
-		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=fast PSMC_HIP_DECODE=fast: factored E-steps on the wide fast kernels; the decoding reads the wide fast tables\n", n_states);
+		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s PSMC_HIP_DECODE=fast: factored E-steps on the wide fast kernels; the decoding reads the wide fast tables\n", n_states, wide_s);
 	else if (wide_fast && use_factored)
-		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=fast: factored E-steps on the wide fast kernels (full counts and decoding stay exact)\n", n_states);
+		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s: factored E-steps on the wide fast kernels (full counts and decoding stay exact)\n", n_states, wide_s);
 	else if (n_states > 128 && mode_is_fast())
 		fprintf(stderr, "psmc: %d hidden states: the fast kernels stop at 128, every E-step of this run uses the exact ones\n", n_states);
 	/* The input is read on a thread of its own while the device comes up: 0.35 s for a 30 M-bin genome beside 0.4 s of HIP start-up, of a
@@ -86,7 +89,7 @@ int main(int argc, char *argv[])
 	const int rd_started = pj.in && o.in_file && strcmp(o.in_file, "-") != 0 && pthread_create(&rd_tid, 0, prefetch_input, &pj) == 0;
 	psmc_estep_backend be;
 	int rc = psmc_hipbe_create(&be, n_states, mode, use_factored, devs, dev_s ? atoi(dev_s) : 0);
-	if (rc == 0 && wide_fast && use_factored) rc = psmc_hipbe_set_option(&be, "wide_fast", 1);
+	if (rc == 0 && wide_fast && use_factored) rc = psmc_hipbe_set_option(&be, "wide_fast", wide_level);
 	if (rd_started) { pthread_join(rd_tid, 0); o.prefetched = pj.in; o.prefetch_rc = pj.rc; }
 	else free(pj.in);
 	if (rc) {

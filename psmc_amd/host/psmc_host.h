@@ -141,7 +141,7 @@ int psmc_run(psmc_options *o, psmc_estep_backend *be);
 /* What PSMC_HIP_MODE / PSMC_HIP_WIDE / PSMC_HIP_DECODE (each 1 when set to "fast") mean for a run with n_states hidden states and
  * `decoding` != 0 when -d / -D / -s / -c was given: a set of PSMC_PLAN_* bits. */
 #define PSMC_PLAN_FAST        1 /* the run is a fast-mode run (else: exact throughout) */
-#define PSMC_PLAN_WIDE        2 /* 129..256 states: factored E-steps on the wide fast kernels (option "wide_fast") */
+#define PSMC_PLAN_WIDE        2 /* 129..256 states (wide_fast = 2: 129..1024): factored E-steps on the wide fast kernels (option "wide_fast") */
 #define PSMC_PLAN_WIDE_DECODE 4 /* ... and the decoding reads the wide fast tables (option "wide_decode") */
 int psmc_mode_plan(int mode_fast, int wide_fast, int decode_fast, int n_states, int decoding);
 /* ... in two halves: everything up to RD 0 -- all draws from the process-wide drand48 stream happen here -- and the EM rounds,

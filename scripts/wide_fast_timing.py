@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """What the factored E-step of the wide fast path ("wide_fast", estep_wide_fast.hip) costs against the wide exact kernels, on the
-30 M-bin genome bench.py builds (psmc_amd/sim.py), at 149, 200 and 256 states (patterns "1+74*2", "100*2", "128*2"):
+30 M-bin genome bench.py builds (psmc_amd/sim.py), at 149, 200 and 256 states (patterns "1+74*2", "100*2", "128*2"), and
+-- beyond 256 states with "wide_fast" = 2, the multi-wave kernels of estep_wide_fast_mw.hip -- at 300, 512, 768 and 1024 states
+("150*2", "128*4", "128*6", "128*8"); --stress takes the stress fixture (tests/golden/stress, 2.2 M bins) instead of the genome:
 
   (a) ms per factored E-step on the wide fast path, parameters moving every step (the host model of psmc_amd.hostlib with
       lambdas scaled by a few per cent per step): the first E-step of a context and the mean of the later ones, with the
@@ -17,6 +19,7 @@
 Library calls are synchronous.  Writes one JSON object to stdout (progress on stderr).
 
     python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
+    python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
 """
 import argparse
 import json
@@ -31,7 +34,23 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PATTERNS = {149: ("1+74*2", 75), 200: ("100*2", 100), 256: ("128*2", 128)}
+PATTERNS = {149: ("1+74*2", 75), 200: ("100*2", 100), 256: ("128*2", 128),
+            300: ("150*2", 150), 512: ("128*4", 128), 768: ("128*6", 128), 1024: ("128*8", 128)}
+
+
+def stress_segs():
+    """tests/golden/stress: 2e5-bin runs of N, a 5e4-bin run of homozygosity, an all-gap segment; 2.2 M bins in six segments"""
+    import gzip
+    lut = np.full(256, 2, np.uint8); lut[ord("T")] = 0; lut[ord("K")] = 1
+    segs, cur = [], []
+    for line in gzip.open(os.path.join(ROOT, "tests", "golden", "stress", "stress.psmcfa.gz"), "rb"):
+        if line.startswith(b">"):
+            if cur: segs.append(np.concatenate(cur))
+            cur = []
+        else:
+            cur.append(lut[np.frombuffer(line.rstrip(b"\n"), dtype=np.uint8)])
+    segs.append(np.concatenate(cur))
+    return segs
 
 
 def params_seq(n, steps, seed=11):
@@ -49,7 +68,7 @@ def params_seq(n, steps, seed=11):
 def library_part(hip, segs, n, steps, exact_steps):
     ps = params_seq(n, steps)
     r = {}
-    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=1)
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1)
     es.load_segments(segs)
     ms, rounds = [], []
     for a, e, a0 in ps:
@@ -164,14 +183,19 @@ def main():
     ap.add_argument("--decode", action="store_true", help="time the decoding calls on the wide fast tables (and on the exact ones) instead of (a), (b)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--full-post", action="store_true")
+    ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
     args = ap.parse_args()
     from psmc_amd import hip, sim
-    g = np.load(os.path.join(ROOT, "tests", "golden", "hmm_params.npz"))
-    p64 = (g["n64_curve.a"], g["n64_curve.e"], g["n64_curve.a0"])
-    lens = sim.human_like_lengths(args.bins, n_seg=90)
-    t = time.perf_counter()
-    segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
-    out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
+    if args.stress:
+        segs = stress_segs()
+        out = {"input": "tests/golden/stress", "bins": int(sum(len(s) for s in segs)), "segments": len(segs)}
+    else:
+        g = np.load(os.path.join(ROOT, "tests", "golden", "hmm_params.npz"))
+        p64 = (g["n64_curve.a"], g["n64_curve.e"], g["n64_curve.a0"])
+        lens = sim.human_like_lengths(args.bins, n_seg=90)
+        t = time.perf_counter()
+        segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
+        out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
     for n in [int(x) for x in args.states.split(",") if x]:
         if args.decode:
             out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0)
