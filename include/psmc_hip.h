@@ -18,8 +18,8 @@
  * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 or 2 a fast-mode context of 129..256 states
  * runs psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip, and with "wide_fast" = 2 one
  * of 257..1024 states runs them on the multi-wave kernels of estep_wide_fast_mw.hip (PSMC-form matrices; full
- * counts, batch and psmc_hip_get_tables stay exact, and so does decoding unless, up to 256 states, "wide_decode" = 1 is set as
- * well: see "Decoding on a FAST context");
+ * counts, batch and psmc_hip_get_tables stay exact, and so does decoding unless "wide_decode" = 1 is set as well -- beyond 256
+ * states together with "wide_fast" = 2: see "Decoding on a FAST context");
  * row-major FP64; a[k*n+l]=P(k->l) (khmm.h:34); e[b*n+k], b=0 hom / 1 het
  * (khmm.h:34; the missing-data row e[2][*]=1 of khmm.c:21 is implied);
  * a0[k] (khmm.h:36); observations are bytes 0/1/2 exactly as psmc_read_seq
@@ -36,7 +36,8 @@ extern "C" {
 #define PSMC_HIP_MODE_FAST  1 /* tiled speculative sweeps, FMA/MFMA, tree reductions; stats within 1e-10 */
 
 #define PSMC_HIP_MAX_STATES 1024 /* exact mode; the fast kernels cover up to 128 states (beyond: a fast-mode context runs the exact ones),
-                                    and the factored statistics up to 256 with the option "wide_fast" = 1, up to 1024 with "wide_fast" = 2 */
+                                    and the factored statistics up to 256 with the option "wide_fast" = 1, up to 1024 with "wide_fast" = 2;
+                                    with "wide_decode" = 1 the decoding entry points read such an E-step's tables at the same sizes */
 
 #define PSMC_HIP_OK        0
 #define PSMC_HIP_EINVAL   -1 /* bad argument (NULL, n out of range, empty segment ...) */
@@ -44,7 +45,8 @@ extern "C" {
 #define PSMC_HIP_EDEVICE  -3 /* HIP runtime error; see psmc_hip_last_error() */
 #define PSMC_HIP_ENOTSUP  -4 /* not supported in this build (n > 1024; the device-resident / factored fast entry points with n > 128 -- the
                                 factored ones with n > 256 when "wide_fast" is 1; "wide_fast" = 2 covers them all -- or with n > 64 and a
-                                matrix without the PSMC form) */
+                                matrix without the PSMC form).  The decoding entry points never answer it beyond 128 states: where they
+                                cannot read the wide fast tables ("wide_decode") they read the exact ones */
 #define PSMC_HIP_ESTATE   -5 /* call order violated (no segments loaded ...) */
 #define PSMC_HIP_ECONVERGE -6 /* fast mode: tile boundaries did not converge within max_rounds */
 
@@ -90,13 +92,18 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           (padded widths 512, 768, 1024: 64 lanes x 4 states per wave), the waves exchange their scan totals through
  *                           LDS once per position.  Plan, options, ENOTSUP / ECONVERGE and diagnostics as for 1; the X table is 8 x 512,
  *                           8 x 768 or 8 x 1024 bytes per bin (PSMC_HIP_ENOMEM, with the table's size in the message, when it does
- *                           not fit).  Everything else such a context does, decoding included, stays on the exact kernels.
+ *                           not fit).  Everything else such a context does stays on the exact kernels -- decoding too, unless
+ *                           "wide_decode" = 1 is set as well.
  *                           Other values: PSMC_HIP_EINVAL
- *  "wide_decode"   0        1, with "wide_fast" = 1 on a fast-mode context of 129..256 states: psmc_hip_decode, _posterior, _post_counts
- *                           and _scales read what the LAST single E-step left -- after a wide fast factored E-step its X table and
- *                           converged tile boundaries (estep_wide_post.hip, no backward table), after psmc_hip_estep the exact tables,
+ *  "wide_decode"   0        1, with "wide_fast" = 1 or 2 on a fast-mode context of 129..256 states, and with "wide_fast" = 2 on one of
+ *                           257..1024 states: psmc_hip_decode, _posterior, _post_counts and _scales read what the LAST single E-step
+ *                           left -- after a wide fast factored E-step its X table and converged tile boundaries (estep_wide_post.hip,
+ *                           beyond 256 states estep_wide_post_mw.hip; no backward table), after psmc_hip_estep the exact tables,
  *                           bit for bit (see "Decoding on a FAST context").  0: the exact tables whatever E-step ran last, as before
- *                           the option existed.  Anywhere else, beyond 256 states included ("wide_fast" = 2): no effect
+ *                           the option existed.  Anywhere else -- exact mode, up to 128 states, beyond 256 states with "wide_fast" = 1
+ *                           -- no effect.  (In the one release where "wide_fast" = 2 existed without this, the pair had no effect
+ *                           beyond 256 states: a decode after a wide fast E-step read the exact tables of an OLDER E-step, or
+ *                           answered ESTATE.)  Other values: PSMC_HIP_EINVAL
  *  "merge"         0        1: a forward FIX pass between the forward sweep and the back half (64 states, fused back half): every tile's start
  *                           vector is checked there, and a tile that fails is rewritten from the true vector until its trajectory has the
  *                           direction of the stored one again (the factor between the two parts is kept for the counts and the likelihood) --
@@ -342,7 +349,7 @@ int psmc_hip_posterior(psmc_hip_ctx *ctx, int seg, double *post, double *recomb)
 int psmc_hip_post_counts(psmc_hip_ctx *ctx, int seg, const int32_t *cnt1, int32_t l, int32_t n_cnt, double *cnt);
 
 /* The reference's scaling factors s[u] of one segment (hmm_forward, khmm.c:170-186; the PR line of -s, aux.c:159-164), L doubles.
- * Exact mode (and more than 128 states unless the wide fast tables are decoded, and the exact fallback below): a copy of the
+ * Exact mode (and more than 128 states unless the wide fast tables are decoded -- "wide_decode" --, and the exact fallback below): a copy of the
  * table, the doubles psmc_hip_get_tables returns as s.  Fast mode: s_u = sum X_u / sum X_{u-1} / inv_u from the fast forward table, X_{u-1} being a tile's own start
  * vector at its first position and s_1 = sum_k a0_k e_k(o_1); within 1e-11 relative of the exact value. */
 int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
@@ -361,10 +368,12 @@ int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
  *     or before any single E-step; PSMC_HIP_ENOTSUP after an E-step whose forward fix pass ran ("merge" = 1).
  * A decoding call reads the tables only: it changes nothing a later E-step uses (plan, glue, warm-ups).
  *
- * 129..256 states, "wide_fast" = 1 and "wide_decode" = 1: the same rule -- the last single E-step decides.
+ * 129..256 states with "wide_fast" = 1 or 2, 257..1024 states with "wide_fast" = 2, and "wide_decode" = 1: the same rule -- the
+ * last single E-step decides.
  *   - a wide fast factored E-step (psmc_hip_estep_factored / _estep_factored_device) that returned 0: one more backward sweep per
- *     tile (estep_wide_post.hip) from the tile's converged start vector bt_{top+1}, reading X; no backward table exists or is
- *     written.  With y = a bt_{p+1}:  gamma_p(k) = X_p(k) y(k) / G_p,  G_p = sum_k X_p(k) y(k)  (the posterior the E-step's E adds
+ *     tile (estep_wide_post.hip; beyond 256 states estep_wide_post_mw.hip, a tile being one work-group of 2..4 waves over X at
+ *     the padded width 512 / 768 / 1024) from the tile's converged start vector bt_{top+1}, reading X; no backward table exists
+ *     or is written.  With y = a bt_{p+1}:  gamma_p(k) = X_p(k) y(k) / G_p,  G_p = sum_k X_p(k) y(k)  (the posterior the E-step's E adds
  *     up; no division by an emission);  recomb_p = 1 - sum_l X_p(l) a_ll bt_{p+1}(l) / G_p;  at p = L: gamma_L = X_L / sum X_L,
  *     recomb_L = 0;  the path takes the lowest state among equal maxima;  s_p = sum X_p / sum X_{p-1} / inv_p with a tile's own
  *     start vector for X_{lo-1}, s_1 = sum_k a0_k e_k(o_1);  post_counts adds per-tile partials in tile order.  Tolerances: the
@@ -373,8 +382,12 @@ int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
  *   - PSMC_HIP_ESTATE before any single E-step, after a batch, after a wide fast E-step that returned an error (ECONVERGE: its
  *     boundaries are not converged), after psmc_hip_select / a reload since that E-step, or for a segment that was not in its
  *     selection.
- * With "wide_decode" = 0 such a context decodes from the exact tables whatever ran last (ESTATE when there are none).
- * psmc_hip_get_tables always reads the exact tables. */
+ * With "wide_decode" = 0 -- and beyond 256 states with "wide_fast" = 1 -- such a context decodes from the exact tables whatever
+ * ran last (ESTATE when there are none).  psmc_hip_get_tables always reads the exact tables.
+ * What it is worth beyond 256 states, on the 2.2 M-bin stress fixture (scripts/wide_fast_timing.py --decode --stress, one E-step plus
+ * every decoding call over all segments, profiles/wide_fast_timing.txt): 0.69 s at 300 states against 19.2 s on the exact kernels,
+ * 1.15 s at 1024 states against 193.8 s.  The E-step is the gain; of the calls themselves psmc_hip_scales (4 / 5 ms against a
+ * 0.6 ms copy of the exact table) and, at 300 states, psmc_hip_decode (34 ms against 5 ms) are slower than their exact twins. */
 
 /* ---- one E-step sharded over several GPUs of the node (replaces em.c:36-55 + the serial
  * hmm_add_expect of khmm.c:346-359 by per-device E-steps and ONE exchange per EM iteration).  One process; devices[]

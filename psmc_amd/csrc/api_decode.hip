@@ -2,7 +2,8 @@
 // E-step, from whichever tables that E-step left (decode_source):
 //   DEC_EXACT  f, b and s of the exact kernels (estep_exact.hip, estep_wide.hip beyond 128 states)
 //   DEC_FAST   X and bt of a fast E-step with the unfused back half, up to 128 states (estep_post_fast.hip)
-//   DEC_WIDE   X, 1/d, entry and bentry of a wide fast E-step, 129..256 states with "wide_decode" (estep_wide_post.hip)
+//   DEC_WIDE   X, 1/d, entry and bentry of a wide fast E-step with "wide_decode": 129..256 states (estep_wide_post.hip), and
+//              257..1024 states with "wide_fast" = 2 (estep_wide_post_mw.hip; the tables are 512, 768 or 1024 states wide)
 // Every entry point is written once: argument check, decode_source, device scratch of its own (freed before it returns), uploads, a
 // switch on the source that holds nothing but the launch, downloads, one synchronise, one error mapping.
 #include "psmc_hip_ctx.h"
@@ -10,15 +11,15 @@
 
 // Which tables the decoding entry points of context c read, and for the fast ones the segment's tiles in the plan of the E-step
 // that wrote them: first_tile, and n_tiles of them.  Returns DEC_EXACT (exact mode; the exact fallback of a fast E-step; beyond
-// 128 states unless "wide_fast" + "wide_decode" are on and the last single E-step was a wide fast one), DEC_FAST, DEC_WIDE, or a
-// PSMC_HIP_E* code (message set).  Reads nothing but the context.
+// 128 states unless "wide_fast" + "wide_decode" are on -- beyond 256 states "wide_fast" = 2 -- and the last single E-step was a
+// wide fast one), DEC_FAST, DEC_WIDE, or a PSMC_HIP_E* code (message set).  Reads nothing but the context.
 static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_tile, int *n_tiles)
 {
 	if (c->mode == PSMC_HIP_MODE_EXACT) return DEC_EXACT;
 	const bool wide = c->ns > 128;
 	char msg[256];
 	if (wide) {
-		if (!c->wide_fast || !c->wide_decode || c->ns > 256 || c->wd_kind == WD_NONE || c->wd_serial != c->tab_serial) return DEC_EXACT;
+		if (!c->wide_fast || !c->wide_decode || (c->n > 256 && c->wide_fast < 2) || c->wd_kind == WD_NONE || c->wd_serial != c->tab_serial) return DEC_EXACT;
 		if (c->wd_kind != WD_OK) {
 			snprintf(msg, sizeof msg, "%s: the last wide fast E-step returned an error (no converged tile boundaries to decode from)", who);
 			return fail(c, PSMC_HIP_ESTATE, msg);
@@ -82,7 +83,7 @@ static const double *par_re(const psmc_hip_ctx *c) { return c->ns == 128 ? c->d_
 static void wide_post_common(const psmc_hip_ctx *c, WidePost &w, int what, int t0, int nt)
 {
 	memset(&w, 0, sizeof(w));
-	w.stream = c->stream; w.what = what; w.ns = c->ns; w.n_states = c->n; w.t0 = t0; w.n_tiles = nt;
+	w.stream = c->stream; w.what = what; w.ns = wf_width(c); w.waves = wf_waves(c); w.n_states = c->n; w.t0 = t0; w.n_tiles = nt;
 	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks;
 	w.X = c->d_wf_X; w.inv = c->d_wf_inv; w.entry = c->d_wf_entry; w.bentry = c->d_wf_bentry;
 }
@@ -173,8 +174,8 @@ extern "C" int psmc_hip_post_counts(psmc_hip_ctx *c, int seg, const int32_t *cnt
 	HIPCHK(c, hipSetDevice(c->device));
 	const int L = c->L[seg], n = c->n, min_l = L < l ? L : l;
 	if (min_l == 0) return PSMC_HIP_OK;
-	// per-block (fast) or per-tile (wide) partial counts, n_cnt x ns doubles each; the exact kernels need none
-	const size_t n_part = (size_t)(src == DEC_FAST ? post_counts_fast_blocks(min_l) : nt) * n_cnt * c->ns;
+	// per-block (fast) or per-tile (wide) partial counts, n_cnt x the tables' padded width doubles each; the exact kernels need none
+	const size_t n_part = src == DEC_FAST ? (size_t)post_counts_fast_blocks(min_l) * n_cnt * c->ns : (size_t)nt * n_cnt * wf_width(c);
 	Scratch sc;
 	int32_t *d1 = sc.get<int32_t>((size_t)min_l * n_cnt);
 	double *dc = sc.get<double>((size_t)n * n_cnt);

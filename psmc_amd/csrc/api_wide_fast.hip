@@ -2,7 +2,7 @@
 // states with the option "wide_fast" = 1 or 2 (kernels: estep_wide_fast.hip, one wave per tile) and at 257..1024 states with
 // "wide_fast" = 2 (kernels: estep_wide_fast_mw.hip, 2..4 waves per tile at the padded widths 512, 768 and 1024; plan, rounds and
 // options are the same, only WideLaunch knows the width and the waves).  With "wide_decode" = 1 the decoding entry points read
-// what such an E-step left at up to 256 states (api_decode.hip; kernels: estep_wide_post.hip).  Everything else a context of that size does --
+// what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip up to 256 states, estep_wide_post_mw.hip beyond).  Everything else a context of that size does --
 // psmc_hip_estep, the batch, psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide
 // exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
 //
@@ -17,11 +17,6 @@
 
 static constexpr int WF_PAR = 8; // e0 | e1 | a0 | P | R | qa | c | dd (wide_fast.h)
 static constexpr int WF_NACC = 7; // SL SU DG CL CU E0 E1 per tile
-
-// the padded width of the path's own tables: c->ns (192 or 256) up to 256 states, beyond them the next multiple of 256 -- one wave
-// of the tile per 256 states (c->ns stays what the wide exact kernels pad to, a multiple of 64)
-static int wf_width(const psmc_hip_ctx *c) { return c->n <= 256 ? c->ns : 256 * ((c->n + 255) / 256); }
-static int wf_waves(const psmc_hip_ctx *c) { return c->n <= 256 ? 1 : (c->n + 255) / 256; }
 
 void free_wide_fast(psmc_hip_ctx *c)
 {

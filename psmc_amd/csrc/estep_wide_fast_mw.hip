@@ -6,7 +6,7 @@
 // continued over the work-group.  Padded states have zero matrix entries and zero emissions, so they stay zero.
 //
 // Every wave does its in-wave scans exactly as wstep / bstep / astep of the one-wave path, then the waves EXCHANGE one small
-// record per position through LDS (Xchg below): the wave totals of the scans (and the wave's sum of the state vector where the
+// record per position through LDS (Xchg, wide_mw_prims.h: shared with the decoding kernels of estep_wide_post_mw.hip): the wave totals of the scans (and the wave's sum of the state vector where the
 // position is scaled, p % 4 == 0), one barrier, and every wave adds the totals of the waves above it (suffix scans) or below it
 // (prefix scans), lowest wave index first.  Sums over the whole tile (the scale factors, I of a tile, the mismatch of a boundary,
 // the logarithms of k_mw_ll) go through the same exchange in the same fixed order, so every wave holds the same bits and the path
@@ -39,109 +39,13 @@
 #include "psmc_hip_internal.h"
 #include "wide_fast.h"
 #include "wide_prims.h"
+#include "wide_mw_prims.h"
 
 namespace psmc {
 namespace wide {
 
-constexpr int MW_NPL = 4;   // states per lane
 constexpr int MW_ACC = 7;   // SL SU DG CL CU E0 E1
-constexpr int MW_SLOTS = 6; // values one wave publishes per exchange, at most
 
-// The exchange between the W waves of a tile.  put(): lane 0 publishes a wave-uniform value; sync(): the one barrier; above() /
-// below() / sum() / vmax(): the other waves' values in a fixed order (the same bits in every wave); next(): the other buffer.
-// Every wave of the work-group must go through the same sequence of exchanges.
-template <int W> struct Xchg {
-	double *lds;
-	int wave, lane;
-	unsigned t;
-	__device__ __forceinline__ double *buf() const { return lds + (t & 1u) * (MW_SLOTS * W); }
-	__device__ __forceinline__ void put(int s, double v) const { if (lane == 0) buf()[s * W + wave] = v; }
-	__device__ __forceinline__ void sync() const { __syncthreads(); }
-	__device__ __forceinline__ void next() { ++t; }
-	__device__ __forceinline__ double get(int s, int w) const { return buf()[s * W + w]; }
-	__device__ __forceinline__ double above(int s) const { // waves w' > wave, lowest first
-		double r = 0.0;
-#pragma unroll
-		for (int w = 1; w < W; ++w) r += w > wave ? get(s, w) : 0.0;
-		return r;
-	}
-	__device__ __forceinline__ double below(int s) const { // waves w' < wave, lowest first
-		double r = 0.0;
-#pragma unroll
-		for (int w = 0; w < W - 1; ++w) r += w < wave ? get(s, w) : 0.0;
-		return r;
-	}
-	__device__ __forceinline__ double sum(int s) const {
-		double r = get(s, 0);
-#pragma unroll
-		for (int w = 1; w < W; ++w) r += get(s, w);
-		return r;
-	}
-	__device__ __forceinline__ double vmax(int s) const {
-		double r = get(s, 0);
-#pragma unroll
-		for (int w = 1; w < W; ++w) r = fmax(r, get(s, w));
-		return r;
-	}
-};
-template <int W> __device__ __forceinline__ Xchg<W> mw_xchg(double *lds) {
-	Xchg<W> xc;
-	xc.lds = lds; xc.lane = threadIdx.x & 63; xc.wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); xc.t = 0u;
-	return xc;
-}
-// sum over the tile of a per-wave value (wave-uniform on entry), the same bits in every wave
-template <int W> __device__ __forceinline__ double mw_total(Xchg<W> &xc, double wave_value) {
-	xc.put(0, wave_value);
-	xc.sync();
-	const double r = xc.sum(0);
-	xc.next();
-	return r;
-}
-template <int W> __device__ __forceinline__ double mw_vsum(Xchg<W> &xc, const double (&x)[MW_NPL]) { return mw_total<W>(xc, wave_total(lsum<MW_NPL>(x))); }
-
-// x <- M x over the tile (wstep of wide_prims.h plus the exchange); NORM: returns the sum of x over the tile BEFORE the step
-template <int W, bool NORM>
-__device__ __forceinline__ double mw_step(const StructParN<MW_NPL> &c, double (&x)[MW_NPL], const WaveScanMasks &wm, Xchg<W> &xc)
-{
-	constexpr int NPL = MW_NPL;
-	double su[NPL], pv[NPL];
-	su[NPL - 1] = x[NPL - 1] * c.mS[NPL - 1];
-#pragma unroll
-	for (int i = NPL - 2; i >= 0; --i) su[i] = __builtin_fma(x[i], c.mS[i], su[i + 1]);
-	pv[0] = x[0] * c.mP[0];
-#pragma unroll
-	for (int i = 1; i < NPL; ++i) pv[i] = __builtin_fma(x[i], c.mP[i], pv[i - 1]);
-	double ES = wave_excl_suffix(su[0], wm), EP = wave_excl_prefix(pv[NPL - 1]);
-	xc.put(0, readlane_f64(ES + su[0], 0));        // the wave's whole suffix sum: lane 0's inclusive one
-	xc.put(1, readlane_f64(EP + pv[NPL - 1], 63)); // the wave's whole prefix sum: lane 63's inclusive one
-	if (NORM) xc.put(2, wave_total(lsum<NPL>(x)));
-	double t[NPL];
-#pragma unroll
-	for (int i = 0; i < NPL; ++i) t[i] = __builtin_fma(c.wS[i], su[i], __builtin_fma(c.wP[i], pv[i], c.dd[i] * x[i]));
-	xc.sync();
-	ES += xc.above(0); EP += xc.below(1);
-	const double tot = NORM ? xc.sum(2) : 0.0;
-	xc.next();
-#pragma unroll
-	for (int i = 0; i < NPL; ++i) x[i] = __builtin_fma(c.wS[i], ES, __builtin_fma(c.wP[i], EP, t[i]));
-	return tot;
-}
-// one backward step at position p: x = bt_{p+1} -> bt_p (own scaling at p % 4 == 0: 1/sum(bt_{p+1}))
-template <int W, bool NORM>
-__device__ __forceinline__ void mw_bstep(const StructParN<MW_NPL> &sc, const WaveScanMasks &wm, int sym, const double (&e0)[MW_NPL],
-                                         const double (&e1)[MW_NPL], double (&x)[MW_NPL], Xchg<W> &xc)
-{
-	double ev[MW_NPL];
-	emis<MW_NPL>(sym, e0, e1, ev);
-	const double tot = mw_step<W, NORM>(sc, x, wm, xc);
-	if (NORM) {
-		const double sb = rcp_newton(tot);
-#pragma unroll
-		for (int i = 0; i < MW_NPL; ++i) ev[i] *= sb;
-	}
-#pragma unroll
-	for (int i = 0; i < MW_NPL; ++i) x[i] *= ev[i];
-}
 // wmismatch of wide_prims.h over the tile: max_k |u/|u| - v/|v|| / max_k v/|v|; NaN anywhere: +inf.  Two exchanges.
 template <int W> __device__ __forceinline__ double mw_mismatch(const double (&u)[MW_NPL], const double (&v)[MW_NPL], Xchg<W> &xc)
 {
@@ -240,12 +144,6 @@ __global__ __launch_bounds__(64 * W) void k_mw_fwd(const double *__restrict__ pa
 		if (mw_mismatch<W>(u, x, xc) <= tol) break; // from exchanged values: the same decision in every wave
 		b = nb; c = chunks[b]; p0 = c.lo;
 	}
-}
-
-// the per-lane constants of the backward direction at the tile's width: mS = c, wS = R, mP = qa, wP = P (wide_prims.h load_par)
-template <int S> __device__ __forceinline__ void mw_load_bwd(const double *__restrict__ par, int k0, StructParN<MW_NPL> &sc) {
-	const double *sp = par + WP_SP * S + k0;
-	ld<MW_NPL>(sp + 3 * S, sc.mS); ld<MW_NPL>(sp + S, sc.wS); ld<MW_NPL>(sp + 2 * S, sc.mP); ld<MW_NPL>(sp, sc.wP); ld<MW_NPL>(sp + 4 * S, sc.dd);
 }
 
 // ------------------------------------------------------------------ backward

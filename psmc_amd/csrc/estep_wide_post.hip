@@ -12,7 +12,7 @@
 // are never written, and a tile writes the positions lo .. hi it owns and nothing else.
 //   k_wp_dec     the sweep: posterior rows | recombination | argmax (lowest state wins a tie) and its value | per-tile partial
 //                posterior-weighted counts, CB count columns per sweep
-//   k_wp_cnt_add the tiles' partials added in tile order (deterministic)
+//   k_wp_cnt_add the tiles' partials added in tile order (deterministic); also at the widths 512 / 768 / 1024 of estep_wide_post_mw.hip
 //   k_wp_scales  s_p = sum X_p / sum X_{p-1} / inv_p from X alone (X_{lo-1}: the tile's own `entry`), s_1 = sum_k a0_k e_k(o_1)
 #include <hip/hip_runtime.h>
 #include "wide_fast.h"
@@ -166,7 +166,6 @@ __global__ __launch_bounds__(64) void k_wp_scales(const Chunk *__restrict__ chun
 
 template <int NPL> static int launch_post(const WidePost &w)
 {
-	constexpr int S = 64 * NPL;
 	const dim3 grid(w.n_tiles), blk(64);
 	hipStream_t st = w.stream;
 #define WP_DEC(POST, REC, PATH, CNT, j0) \
@@ -179,8 +178,8 @@ template <int NPL> static int launch_post(const WidePost &w)
 	case WP_POST_REC: WP_DEC(true, true, false, false, 0); break;
 	case WP_COUNTS:
 		for (int j0 = 0; j0 < w.n_cnt; j0 += CB) WP_DEC(false, false, false, true, j0);
-		hipLaunchKernelGGL(k_wp_cnt_add<S>, dim3((w.n_states * w.n_cnt + 255) / 256), dim3(256), 0, st, w.part, w.n_tiles, w.n_cnt, w.n_states, w.cnt);
-		break;
+		if (hipGetLastError() != hipSuccess) return -1;
+		return launch_wide_post_cnt_add(w);
 	case WP_SCALES: hipLaunchKernelGGL(k_wp_scales<NPL>, grid, blk, 0, st, w.chunks, w.t0, w.X, w.inv, w.entry, w.s); break;
 	default: return -1;
 	}
@@ -188,10 +187,29 @@ template <int NPL> static int launch_post(const WidePost &w)
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+template <int S> static int launch_cnt_add(const WidePost &w)
+{
+	hipLaunchKernelGGL(k_wp_cnt_add<S>, dim3((w.n_states * w.n_cnt + 255) / 256), dim3(256), 0, w.stream, w.part, w.n_tiles, w.n_cnt, w.n_states, w.cnt);
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 } // namespace wide
+
+int launch_wide_post_cnt_add(const WidePost &w)
+{
+	switch (w.ns) {
+	case 192: return wide::launch_cnt_add<192>(w);
+	case 256: return wide::launch_cnt_add<256>(w);
+	case 512: return wide::launch_cnt_add<512>(w);
+	case 768: return wide::launch_cnt_add<768>(w);
+	case 1024: return wide::launch_cnt_add<1024>(w);
+	}
+	return -1;
+}
 
 int launch_wide_post(const WidePost &w)
 {
+	if (w.waves > 1) return launch_wide_post_mw(w); // 257..1024 states: estep_wide_post_mw.hip
 	if (w.ns == 192) return wide::launch_post<3>(w);
 	if (w.ns == 256) return wide::launch_post<4>(w);
 	return -1;

@@ -2,7 +2,7 @@
 //   api.hip        context, options, segments, parameter staging, tables, exact mode, the table reader
 //   api_fast.hip   fast mode: tile plan, sweep items, learning, the launch of one fast E-step and its entry points
 //   api_wide_fast.hip  fast mode at 129..256 states ("wide_fast") and 257..1024 states ("wide_fast" = 2): plan, rounds and launch of the factored E-step
-//   api_decode.hip psmc_hip_decode / _posterior / _post_counts / _scales from the exact, the fast or the wide fast tables
+//   api_decode.hip psmc_hip_decode / _posterior / _post_counts / _scales from the exact, the fast or the wide fast tables (one wave per tile or 2..4)
 //   api_batch.hip  psmc_hip_estep_batch (bootstrap replicates): exact launch groups, fast per-replicate plans
 //   api_probes.hip device self-test, microbenchmarks and probes (diagnostics)
 // Everything is built with -ffp-contract=off: no host or device expression is ever fused.
@@ -31,7 +31,7 @@ constexpr int DEC_FAST = 1;   // the fast tables X and bt (dense sweeps, or the 
 constexpr int DEC_EXACT = 2;  // the exact tables (65..128 states, a matrix without the PSMC form: fast mode ran the exact kernels)
 constexpr int DEC_NO_BT = 3;  // the fused or factored back half: no backward table
 constexpr int DEC_MERGED = 4; // the forward fix pass ("merge"): its X carries per-tile factors
-constexpr int DEC_WIDE = 5;   // never stored, decode_source returns it: the tables of the wide fast path (129..256 states, "wide_decode"): estep_wide_post.hip
+constexpr int DEC_WIDE = 5;   // never stored, decode_source returns it: the tables of the wide fast path ("wide_decode"; 129..256 states: estep_wide_post.hip, 257..1024 with "wide_fast" = 2: estep_wide_post_mw.hip)
 // psmc_hip_ctx::wd_kind: what the last wide fast E-step of the context left (set in api_wide_fast.hip, read by api_decode.hip decode_source)
 constexpr int WD_NONE = 0;    // there was none, or a batch came after it
 constexpr int WD_OK = 1;      // X, 1/d, entry and a converged bentry of every tile of its plan
@@ -233,12 +233,17 @@ struct psmc_hip_ctx {
 	double *d_wf_par = nullptr, *h_wf_par = nullptr;                     // e0 | e1 | a0 | P | R | qa | c | dd
 	double *d_wf_entry = nullptr, *d_wf_bentry = nullptr, *d_wf_bexit = nullptr, *d_wf_part = nullptr, *d_wf_ll = nullptr;
 	int *d_wf_dirty = nullptr, *d_wf_list = nullptr;
-	// "wide_decode" = 1 (with "wide_fast"): the decoding entry points of such a context read the tables of the wide path when the last
-	// single E-step was one of its own.  wd_serial: the table serial at that E-step -- an exact E-step or a batch moves tab_serial on,
+	// "wide_decode" = 1 (with "wide_fast"; beyond 256 states with "wide_fast" = 2): the decoding entry points of such a context read the
+	// tables of the wide path when the last single E-step was one of its own.  wd_serial: the table serial at that E-step -- an exact E-step or a batch moves tab_serial on,
 	// and the exact tables are the newer ones; wd_sel: the selection serial it ran with (psmc_hip_select moves sel_serial on)
 	int wide_decode = 0;
 	int wd_kind = 0; unsigned long long wd_serial = 0, wd_sel = 0, sel_serial = 0;
 };
+// the padded width of the wide fast path's own tables (api_wide_fast.hip writes them, api_decode.hip reads them): c->ns (192 or 256)
+// up to 256 states, beyond them the next multiple of 256 -- one wave of the tile per 256 states (c->ns stays what the wide exact
+// kernels pad to, a multiple of 64: 320 at 300 states, where this is 512)
+inline int wf_width(const psmc_hip_ctx *c) { return c->n <= 256 ? c->ns : 256 * ((c->n + 255) / 256); }
+inline int wf_waves(const psmc_hip_ctx *c) { return c->n <= 256 ? 1 : (c->n + 255) / 256; }
 inline double dbg_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline psmc_hip_ctx *dbg_root(psmc_hip_ctx *c) { return c->parent ? c->parent : c; }
 

@@ -1,6 +1,6 @@
 // wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states:
-// one wave per tile), of estep_wide_fast_mw.hip (257..1024 states: 2..4 waves per tile) and of estep_wide_post.hip (decoding from
-// the tables the one-wave E-step left).
+// one wave per tile), of estep_wide_fast_mw.hip (257..1024 states: 2..4 waves per tile), of estep_wide_post.hip (decoding from
+// the tables the one-wave E-step left) and of estep_wide_post_mw.hip (decoding from the tables the multi-wave E-step left).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "psmc_hip_internal.h"
@@ -31,7 +31,8 @@ enum { WP_PATH, WP_POST, WP_REC, WP_POST_REC, WP_COUNTS, WP_SCALES };
 
 struct WidePost {
 	hipStream_t stream;
-	int what, ns, n_states, t0, n_tiles;
+	int what, ns, n_states, t0, n_tiles; // ns: the padded width of the tables, as WideLaunch
+	int waves;                        // waves per tile of the E-step that wrote them: 1, or ns / 256
 	const double *par;                // as WideLaunch
 	const uint8_t *obs;
 	const Chunk *chunks;
@@ -43,6 +44,8 @@ struct WidePost {
 	double *part, *cnt;               // [n_tiles][n_cnt][ns] per-tile partials; [n_states][n_cnt] running totals (in / out)
 };
 
-int launch_wide_post(const WidePost &w); // estep_wide_post.hip
+int launch_wide_post(const WidePost &w);         // estep_wide_post.hip (waves > 1: hands on to the next)
+int launch_wide_post_mw(const WidePost &w);      // estep_wide_post_mw.hip
+int launch_wide_post_cnt_add(const WidePost &w); // estep_wide_post.hip: WP_COUNTS, the tiles' partials added in tile order, at every width
 
 } // namespace psmc

@@ -146,7 +146,7 @@ static int hb_tables(void *self, int seg, double *f, double *b, double *s)
 	return rc ? rc : psmc_hip_get_tables(c, l, f, b, s);
 }
 /* PSMC_HIP_DECODE=fast: the decoding E-step keeps the backward table (the fused and factored back halves never store it); on the
- * wide fast path (129..256 states) it is a factored wide E-step (hb_estep) and the decoding reads its tables ("wide_decode") */
+ * wide fast path (129..256 states, or 257..1024 with PSMC_HIP_WIDE=fast-all PSMC_HIP_DECODE=fast-all) it is a factored wide E-step (hb_estep) and the decoding reads its tables ("wide_decode") */
 static int hb_prepare_decode(void *self)
 {
 	hip_be *h = (hip_be *)self;

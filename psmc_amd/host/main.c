@@ -10,6 +10,10 @@
  *                                    path and the decoding reads its tables (option "wide_decode")
  *   PSMC_HIP_WIDE=fast-all           the same, and at 257..1024 states the factored fast E-steps of the multi-wave wide fast path
  *                                    ("wide_fast" = 2); a decoding run beyond 256 states stays on the exact kernels throughout
+ *                                    unless PSMC_HIP_DECODE=fast-all is set too
+ *   PSMC_HIP_DECODE=fast-all         what PSMC_HIP_DECODE=fast means, and with PSMC_HIP_WIDE=fast-all, 257..1024 states and
+ *                                    -d/-D/-c/-s the EM rounds stay on the multi-wave wide fast path and the decoding reads its
+ *                                    tables ("wide_fast" = 2 + "wide_decode")
  *   PSMC_HIP_DEVICE=<index>          one GPU
  *   PSMC_HIP_DEVICES=<i>,<j>,...     the segments of every E-step sharded over these GPUs (psmc_hip_group_*: LPT
  *                                    partition, one RCCL all-reduce of the statistics per EM iteration in fast mode,
@@ -53,7 +57,8 @@ int main(int argc, char *argv[])
 	const char *wide_s = getenv("PSMC_HIP_WIDE"), *dec_s = getenv("PSMC_HIP_DECODE");
 	const int decoding = o.decode || o.print_prob || o.cnt_file;
 	const int wide_level = !wide_s ? 0 : (strcmp(wide_s, "fast-all") == 0 ? 2 : (strcmp(wide_s, "fast") == 0 ? 1 : 0));
-	const int plan = psmc_mode_plan(mode_is_fast(), wide_level, dec_s && strcmp(dec_s, "fast") == 0, n_states, decoding);
+	const int dec_level = !dec_s ? 0 : (strcmp(dec_s, "fast-all") == 0 ? 2 : (strcmp(dec_s, "fast") == 0 ? 1 : 0));
+	const int plan = psmc_mode_plan(mode_is_fast(), wide_level, dec_level, n_states, decoding);
 	const int wide_fast = (plan & PSMC_PLAN_WIDE) != 0;
 	const char *mode_s = getenv("PSMC_HIP_MODE"), *dev_s = getenv("PSMC_HIP_DEVICE");
 	int mode = (mode_s && strcmp(mode_s, "fast") == 0) ? PSMC_HIP_MODE_FAST : PSMC_HIP_MODE_EXACT;
@@ -61,7 +66,7 @@ int main(int argc, char *argv[])
 		if (plan & PSMC_PLAN_WIDE_DECODE) /* (said below, once it is known that the factored E-step runs) */
 			;
 		else if (plan & PSMC_PLAN_FAST) /* opt-in: decode from the fast E-step's tables (include/psmc_hip.h: tolerances) */
-			fprintf(stderr, "psmc: PSMC_HIP_DECODE=fast: fast E-steps throughout; the decoding reads the fast forward/backward tables\n");
+			fprintf(stderr, "psmc: PSMC_HIP_DECODE=%s: fast E-steps throughout; the decoding reads the fast forward/backward tables\n", dec_s);
 		else {
 			fprintf(stderr, "psmc: decoding needs the exact forward/backward tables; using PSMC_HIP_MODE=exact\n");
 			mode = PSMC_HIP_MODE_EXACT;
@@ -76,7 +81,7 @@ int main(int argc, char *argv[])
 	const int use_factored = o.fast_mstep && mode == PSMC_HIP_MODE_FAST && (n_states <= 128 || wide_fast) && !(fs && atoi(fs) == 0);
 	/* (PSMC_FACTORED=0 or PSMC_FAST_MSTEP=0 ask for full counts, which beyond 128 states only the exact kernels compute) */
 	if (wide_fast && use_factored && (plan & PSMC_PLAN_WIDE_DECODE))
-		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s PSMC_HIP_DECODE=fast: factored E-steps on the wide fast kernels; the decoding reads the wide fast tables\n", n_states, wide_s);
+		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s PSMC_HIP_DECODE=%s: factored E-steps on the wide fast kernels; the decoding reads the wide fast tables\n", n_states, wide_s, dec_s);
 	else if (wide_fast && use_factored)
 		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s: factored E-steps on the wide fast kernels (full counts and decoding stay exact)\n", n_states, wide_s);
 	else if (n_states > 128 && mode_is_fast())

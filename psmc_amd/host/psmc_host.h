@@ -138,11 +138,11 @@ void psmc_options_free(psmc_options *o);
 /* Whole program given an E-step backend: header, RD 0, n_iters EM rounds,
  * optional decoding / simulation.  Returns the process exit status. */
 int psmc_run(psmc_options *o, psmc_estep_backend *be);
-/* What PSMC_HIP_MODE / PSMC_HIP_WIDE / PSMC_HIP_DECODE (each 1 when set to "fast") mean for a run with n_states hidden states and
- * `decoding` != 0 when -d / -D / -s / -c was given: a set of PSMC_PLAN_* bits. */
+/* What PSMC_HIP_MODE (1: "fast"), PSMC_HIP_WIDE (1: "fast", 2: "fast-all") and PSMC_HIP_DECODE (1: "fast", 2: "fast-all") mean for a
+ * run with n_states hidden states and `decoding` != 0 when -d / -D / -s / -c was given: a set of PSMC_PLAN_* bits. */
 #define PSMC_PLAN_FAST        1 /* the run is a fast-mode run (else: exact throughout) */
 #define PSMC_PLAN_WIDE        2 /* 129..256 states (wide_fast = 2: 129..1024): factored E-steps on the wide fast kernels (option "wide_fast") */
-#define PSMC_PLAN_WIDE_DECODE 4 /* ... and the decoding reads the wide fast tables (option "wide_decode") */
+#define PSMC_PLAN_WIDE_DECODE 4 /* ... and the decoding reads the wide fast tables (option "wide_decode"; beyond 256 states: decode_fast = 2) */
 int psmc_mode_plan(int mode_fast, int wide_fast, int decode_fast, int n_states, int decoding);
 /* ... in two halves: everything up to RD 0 -- all draws from the process-wide drand48 stream happen here -- and the EM rounds,
  * decoding and output (frees the state).  psmc_run_begin returns NULL after printing what went wrong. */

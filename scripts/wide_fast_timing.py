@@ -10,7 +10,8 @@
   (b) ms per E-step of the wide exact kernels (psmc_hip_estep) on the same input and the first parameters (one step after a
       warm-up of the allocations)
   (c) with --cli: wall clock of `psmc -N5 -p "100*2"` on the genome in exact mode and with PSMC_HIP_MODE=fast PSMC_HIP_WIDE=fast
-  (d) with --decode: decoding from the wide fast tables ("wide_decode", estep_wide_post.hip) -- after a warm-up pass, --repeats
+  (d) with --decode: decoding from the wide fast tables ("wide_decode", estep_wide_post.hip; beyond 256 states "wide_fast" = 2 and
+      the multi-wave kernels of estep_wide_post_mw.hip) -- after a warm-up pass, --repeats
       passes of each decoding call over ALL segments (decode = -d, recombination only and posterior rows + recombination = -D,
       post_counts with three columns = -c, scales = -s; the posterior rows of the longest segment only unless --full-post: all
       of them are 8 n bytes per bin to the host), min | median | max in ms; and what the same request costs without the option:
@@ -20,6 +21,7 @@ Library calls are synchronous.  Writes one JSON object to stdout (progress on st
 
     python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
     python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
+    python scripts/wide_fast_timing.py --decode --stress --states 300,1024
 """
 import argparse
 import json
@@ -121,7 +123,7 @@ def decode_calls(es, segs, n, full_post):
 def decode_part(hip, segs, n, repeats, full_post, exact):
     a, e, a0 = params_seq(n, 1)[0]
     r = {"longest_segment_bins": int(max(len(s) for s in segs))}
-    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=1, wide_decode=1)
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_decode=1)
     es.load_segments(segs)
     es.estep_factored(a, e[:2], a0)
     ms = []
