@@ -18,8 +18,8 @@
  * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 or 2 a fast-mode context of 129..256 states
  * runs psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip, and with "wide_fast" = 2 one
  * of 257..1024 states runs them on the multi-wave kernels of estep_wide_fast_mw.hip (PSMC-form matrices; full
- * counts, batch and psmc_hip_get_tables stay exact, and so does decoding unless "wide_decode" = 1 is set as well -- beyond 256
- * states together with "wide_fast" = 2: see "Decoding on a FAST context");
+ * counts and psmc_hip_get_tables stay exact; so does the batch unless "wide_batch" = 1 is set as well -- see psmc_hip_estep_batch --
+ * and so does decoding unless "wide_decode" = 1 is -- beyond 256 states together with "wide_fast" = 2: see "Decoding on a FAST context");
  * row-major FP64; a[k*n+l]=P(k->l) (khmm.h:34); e[b*n+k], b=0 hom / 1 het
  * (khmm.h:34; the missing-data row e[2][*]=1 of khmm.c:21 is implied);
  * a0[k] (khmm.h:36); observations are bytes 0/1/2 exactly as psmc_read_seq
@@ -45,8 +45,10 @@ extern "C" {
 #define PSMC_HIP_EDEVICE  -3 /* HIP runtime error; see psmc_hip_last_error() */
 #define PSMC_HIP_ENOTSUP  -4 /* not supported in this build (n > 1024; the device-resident / factored fast entry points with n > 128 -- the
                                 factored ones with n > 256 when "wide_fast" is 1; "wide_fast" = 2 covers them all -- or with n > 64 and a
-                                matrix without the PSMC form).  The decoding entry points never answer it beyond 128 states: where they
-                                cannot read the wide fast tables ("wide_decode") they read the exact ones */
+                                matrix without the PSMC form; psmc_hip_estep_batch on the wide fast path -- "wide_batch" -- for the reasons
+                                psmc_hip_estep_factored has there, the message naming the replicate).  The decoding entry points never
+                                answer it beyond 128 states: where they cannot read the wide fast tables ("wide_decode") they read the
+                                exact ones */
 #define PSMC_HIP_ESTATE   -5 /* call order violated (no segments loaded ...) */
 #define PSMC_HIP_ECONVERGE -6 /* fast mode: tile boundaries did not converge within max_rounds */
 
@@ -84,16 +86,16 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           "max_rounds" and "learn" (1: a repair walks on through the failing tiles after it in the same round;
  *                           0: one tile per wave and round); with "structured" = 0 it answers ENOTSUP, as the factored statistics
  *                           do up to 128 states.  It keeps an X table of its own: 8 x 192 or 8 x 256 bytes per bin
- *                           (46 / 61 GB at 30 M bins), beside the exact tables.  psmc_hip_estep, the batch, psmc_hip_get_tables and
- *                           (without "wide_decode") the decoding entry points stay on the exact kernels, bit for bit.  Exact mode and
- *                           <= 128 states: no effect.
+ *                           (46 / 61 GB at 30 M bins), beside the exact tables.  psmc_hip_estep, psmc_hip_get_tables, the batch (without
+ *                           "wide_batch": see psmc_hip_estep_batch) and the decoding entry points (without "wide_decode") stay on the
+ *                           exact kernels, bit for bit.  Exact mode and <= 128 states: no effect.
  *                           2: the same at 129..256 states (the same kernels, the same bits as 1), and a fast-mode context of 257..1024
  *                           states runs them on the kernels of estep_wide_fast_mw.hip: a tile is one work-group of 2, 3 or 4 waves
  *                           (padded widths 512, 768, 1024: 64 lanes x 4 states per wave), the waves exchange their scan totals through
  *                           LDS once per position.  Plan, options, ENOTSUP / ECONVERGE and diagnostics as for 1; the X table is 8 x 512,
  *                           8 x 768 or 8 x 1024 bytes per bin (PSMC_HIP_ENOMEM, with the table's size in the message, when it does
- *                           not fit).  Everything else such a context does stays on the exact kernels -- decoding too, unless
- *                           "wide_decode" = 1 is set as well.
+ *                           not fit).  Everything else such a context does stays on the exact kernels -- the batch too, unless
+ *                           "wide_batch" = 1 is set as well, and decoding, unless "wide_decode" = 1 is.
  *                           Other values: PSMC_HIP_EINVAL
  *  "wide_decode"   0        1, with "wide_fast" = 1 or 2 on a fast-mode context of 129..256 states, and with "wide_fast" = 2 on one of
  *                           257..1024 states: psmc_hip_decode, _posterior, _post_counts and _scales read what the LAST single E-step
@@ -104,6 +106,9 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           -- no effect.  (In the one release where "wide_fast" = 2 existed without this, the pair had no effect
  *                           beyond 256 states: a decode after a wide fast E-step read the exact tables of an OLDER E-step, or
  *                           answered ESTATE.)  Other values: PSMC_HIP_EINVAL
+ *  "wide_batch"    0        1: psmc_hip_estep_batch[_cb] of a fast-mode context of 129..1024 states whose size "wide_fast" covers, asked for
+ *                           sums and not for A, runs every replicate on the wide fast path (see psmc_hip_estep_batch, "wide fast batch").
+ *                           0, and every other context or call: the batch as without the option.  Other values: PSMC_HIP_EINVAL
  *  "merge"         0        1: a forward FIX pass between the forward sweep and the back half (64 states, fused back half): every tile's start
  *                           vector is checked there, and a tile that fails is rewritten from the true vector until its trajectory has the
  *                           direction of the stored one again (the factor between the two parts is kept for the counts and the likelihood) --
@@ -194,7 +199,7 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           three kernels.  auto: 2, and only when the tables of all replicates would not fit one launch group
  *
  * With 65..128 states "lanes8", "kc_sub", "ckpt", "merge" and "adapt" are accepted and ignored (their kernels are 64-state ones);
- * beyond 128 states only "batch_bins" and "batch_sort" are read.
+ * beyond 128 states the exact kernels read only "batch_bins" and "batch_sort" (the wide fast path: see "wide_fast").
  * Removed after losing their A/B or settling on one value (HISTORY.md keeps the measurements) -- round 3: "count_impl", "kc_warm",
  * "walk_heads", "walk_impl", "kcol_impl", "fuse_order", "exact_lds", the value 1 of "two_phase"; round 6: "lanes8b" (with its kernel),
  * "batch_slots", "expect_impl" (with the vector-instruction counts kernel), the value 1 of "fuse128" (with round 3's 128-state kernel),
@@ -249,12 +254,26 @@ int psmc_hip_reserve_tables(psmc_hip_ctx *ctx);
  *     fits the free memory.
  *   fast mode: one replicate fills the device, so they run back to back, each on its own learned tile plan (kept in
  *     a per-replicate child context that shares this context's observations and tables); sums = factored statistics.
- * Segment tables are in batch layout afterwards: decode / get_tables need a single E-step first. */
+ *   beyond 128 states: the exact launch groups above whatever the mode, bit for bit what an exact-mode context gives -- except the
+ *   wide fast batch: a call takes the wide fast path ("wide_fast") if and only if "wide_batch" = 1, the context is in fast mode, has
+ *     more than 128 states, "wide_fast" covers its size (1: up to 256 states, 2: up to 1024), A == NULL and sums != NULL.  A caller who
+ *     wants A, alone or beside sums, gets the exact launch groups.  The wide path learns nothing between E-steps (its plan depends on
+ *     the selection and the options alone), so there are no replicate contexts: for r = 0 .. n_rep-1, in order, the context selects
+ *     replicate r's multiset, runs the E-step of psmc_hip_estep_factored with a[r], e[r], a0[r] into the rows r of sums / E / LL --
+ *     the bits psmc_hip_select + psmc_hip_estep_factored give on a fresh context with the same options -- and calls done(user, 1, &r).
+ *     One X table, sized for all loaded segments, serves every replicate.  On every exit, errors included, the selection the context
+ *     had before the call is back: a later single E-step gives the bits it gave before.  PSMC_HIP_ECONVERGE from a replicate's
+ *     E-step: that replicate is repeated with the exact kernels (a line on stderr names it and the path that failed) and the batch
+ *     goes on wide.  PSMC_HIP_ENOTSUP ("structured" = 0, a matrix without the PSMC form) ends the call, the message names the
+ *     replicate.  Afterwards psmc_hip_fast_repairs / _fast_info / _fast_diag describe the last replicate's E-step, psmc_hip_batch_info
+ *     answers {n_rep, 0}; "batch_first" and "share_learn" are not read.
+ * Segment tables are in batch layout afterwards: decode / get_tables need a single E-step first (the wide fast batch included: with
+ * "wide_decode" = 1 a decoding call after it answers PSMC_HIP_ESTATE). */
 /* Exact mode: allocate the batch's tables now -- min(max_bins, what "batch_bins" allows or 0.9 of the free device memory;
  * max_bins <= 0: no upper bound), max_bins = the table bins all replicates together can need, e.g. n_rep x the padded
  * length of the loaded segments -- instead of inside the first psmc_hip_estep_batch.  The driver clears what it hands out:
  * ~250 GB take 4-6 s, which a caller can spend while it is still loading (psmc_boot does; the first EM iteration then costs
- * what the others do).  Fast mode: no-op.
+ * what the others do).  Fast mode: no-op (up to 128 states, and where "wide_batch" = 1 sends the batch down the wide fast path).
  * A SECOND call while that reservation stands (64 states, batch without the f table) adds what has become free since -- psmc_boot
  * --main: the main run that shared the device is over -- as a second chunk of table beside the first, up to max_bins in all: the batches
  * that follow plan their launches for both (an entry's table is an offset from the first chunk either way).  Growing the first chunk
@@ -263,7 +282,7 @@ int psmc_hip_reserve_batch_tables(psmc_hip_ctx *ctx, int64_t max_bins);
 int psmc_hip_estep_batch(psmc_hip_ctx *ctx, int n_rep, const double *a, const double *e, const double *a0,
                          const int32_t *sel_off, const int32_t *sel_idx, double *A, double *sums, double *E, double *LL);
 /* The same with a progress callback: `done(user, n, replicates)` is called on the calling thread, between two launches (exact mode)
- * or after each replicate's E-step (fast mode), with the replicates -- positions in this call -- whose rows of A / sums / E / LL are
+ * or after each replicate's E-step (fast mode, the wide fast batch), with the replicates -- positions in this call -- whose rows of A / sums / E / LL are
  * final from now on; every replicate is named exactly once, the last ones before the call returns.  What em.c:56-68 does next, the
  * M-step, needs nothing else: a caller can run the finished replicates' M-steps on its own threads while the device works on the
  * rest of the batch (psmc_boot does).  The callback must not call into this context.  done = NULL: psmc_hip_estep_batch. */
@@ -271,7 +290,7 @@ typedef void (*psmc_hip_batch_done_fn)(void *user, int n_done, const int32_t *re
 int psmc_hip_estep_batch_cb(psmc_hip_ctx *ctx, int n_rep, const double *a, const double *e, const double *a0,
                             const int32_t *sel_off, const int32_t *sel_idx, double *A, double *sums, double *E, double *LL,
                             psmc_hip_batch_done_fn done, void *user);
-/* Diagnostic: out = {launch groups of the last exact batch (fast: replicates run), replicate contexts alive}. */
+/* Diagnostic: out = {launch groups of the last exact batch (fast, wide fast batch: replicates run), replicate contexts alive}. */
 int psmc_hip_batch_info(psmc_hip_ctx *ctx, int out[2]);
 
 /* Exact mode, for multi-process sharding: per selected segment the reference's

@@ -1,6 +1,7 @@
 // api_batch.hip -- psmc_hip_estep_batch (bootstrap replicates over ONE loaded trunk set; replaces the
 // xargs farm of the reference's README:57-62): exact mode as launch groups that share the table memory, fast mode as one
-// plan-holding child context per replicate.
+// plan-holding child context per replicate; beyond 128 states the exact launch groups whatever the mode, unless "wide_batch" = 1
+// sends a fast-mode context's replicates through the wide fast E-step one after the other (batch_wide).
 #include "psmc_hip_ctx.h"
 
 // ---------------------------------------------------------------- batch (bootstrap replicates)
@@ -80,6 +81,7 @@ extern "C" int psmc_hip_reserve_batch_tables(psmc_hip_ctx *c, int64_t max_bins)
 {
 	if (!c) return PSMC_HIP_EINVAL;
 	if (c->mode != PSMC_HIP_MODE_EXACT && c->ns <= 128) return PSMC_HIP_OK; // fast mode keeps one replicate's tables: nothing to reserve
+	if (c->mode != PSMC_HIP_MODE_EXACT && c->wide_batch && c->wide_fast && (c->n <= 256 || c->wide_fast >= 2)) return PSMC_HIP_OK; // (so does the wide fast batch: its one X table)
 	HIPCHK(c, hipSetDevice(c->device));
 	if (c->n_seg < 1) return fail(c, PSMC_HIP_ESTATE, "reserve_batch_tables: no segments loaded");
 	// A SECOND call while the reservation stands and more memory has become free (psmc_boot --main: the main run that shared the device is over
@@ -507,10 +509,10 @@ static psmc_hip_ctx *batch_child(psmc_hip_ctx *c, int r)
 // such failure mode).  The batch does the same: an exact twin of the context over the same observations (borrowed, already in HBM), made on
 // first need, runs THAT replicate's selection; a line on stderr says so; the batch goes on in fast mode.  
 static int batch_exact_once(psmc_hip_ctx *c, int r, const int32_t *idx, int n_sel, const double *a, const double *e, const double *a0,
-                            double *A, double *sums, double *E, double *LL, const char *why)
+                            double *A, double *sums, double *E, double *LL, const char *why, const char *path = "fast")
 {
 	const int n = c->n;
-	fprintf(stderr, "[psmc_hip] replicate %d: fast E-step did not converge (%s); repeating this E-step with the exact kernels\n", c->batch_first + r, why);
+	fprintf(stderr, "[psmc_hip] replicate %d: %s E-step did not converge (%s); repeating this E-step with the exact kernels\n", r, path, why);
 	int rc = 0;
 	if (!c->x_twin) {
 		if ((rc = psmc_hip_create(&c->x_twin, n, c->device, PSMC_HIP_MODE_EXACT))) return fail(c, rc, "estep_batch: cannot create the exact twin context");
@@ -584,7 +586,7 @@ static int batch_fast(psmc_hip_ctx *c, int n_rep, const double *a, const double 
 			double *Ar = A ? A + (size_t)r * n * n : nullptr, *Sr = sums ? sums + (size_t)r * 5 * n : nullptr, *Er = E ? E + (size_t)r * 2 * n : nullptr, *Lr = LL ? LL + r : nullptr;
 			if (A) rc = psmc_hip_estep(k, ar, er, a0r, Ar, Er, nullptr, Lr, nullptr);
 			if (rc == 0 && sums) rc = psmc_hip_estep_factored(k, ar, er, a0r, Sr, Er, Lr);
-			if (rc == PSMC_HIP_ECONVERGE) rc = batch_exact_once(c, r, idx, n_sel, ar, er, a0r, Ar, Sr, Er, Lr, k->err.c_str());
+			if (rc == PSMC_HIP_ECONVERGE) rc = batch_exact_once(c, c->batch_first + r, idx, n_sel, ar, er, a0r, Ar, Sr, Er, Lr, k->err.c_str());
 		}
 		t_est += dbg_now() - t_e;
 		if (rc) { c->err = "replicate " + std::to_string(r) + ": " + k->err; return rc; }
@@ -599,6 +601,55 @@ static int batch_fast(psmc_hip_ctx *c, int n_rep, const double *a, const double 
 	c->tables_batch = true;
 	c->last_batch_groups = n_rep;
 	return PSMC_HIP_OK;
+}
+
+// "wide_batch" = 1, fast mode, 129..1024 states covered by "wide_fast", sums wanted and A not: every replicate's E-step on the wide fast
+// path.  That path learns nothing between E-steps -- its plan depends on the selection and the options alone (api_wide_fast.hip) -- so
+// there is nothing to keep per replicate: no child contexts, no shared learning, "batch_first" and "share_learn" are not read.  Replicate
+// r is psmc_hip_select(its multiset) + the single factored E-step on THIS context, with the bits those two calls give on a fresh
+// context; the X table is the context's one, sized for all loaded segments.  The selection the context had comes back on every exit.
+// ECONVERGE from a replicate: that replicate once more on the exact twin, the batch goes on wide; any other error ends the call.
+static bool batch_goes_wide(const psmc_hip_ctx *c, const double *A, const double *sums)
+{
+	return c->wide_batch && c->mode == PSMC_HIP_MODE_FAST && c->ns > 128 && c->wide_fast && (c->n <= 256 || c->wide_fast >= 2) && !A && sums;
+}
+
+static int batch_wide(psmc_hip_ctx *c, int n_rep, const double *a, const double *e, const double *a0, const int32_t *sel_off,
+                      const int32_t *sel_idx, double *sums, double *E, double *LL, psmc_hip_batch_done_fn done, void *user)
+{
+	const int n = c->n;
+	for (int r = 0; r < n_rep; ++r) { // nothing runs, and the selection stays untouched, when any replicate's multiset is unusable
+		if (sel_off[r + 1] - sel_off[r] < 1) return fail(c, PSMC_HIP_EINVAL, "estep_batch: empty selection");
+		for (int i = sel_off[r]; i < sel_off[r + 1]; ++i)
+			if (sel_idx[i] < 0 || sel_idx[i] >= c->n_seg) return fail(c, PSMC_HIP_EINVAL, "estep_batch: index out of range");
+	}
+	static const bool dbg_t = getenv("PSMC_HIP_DEBUG_TIMES") != nullptr;
+	const double t_call = dbg_now();
+	const std::vector<int32_t> keep = c->sel;
+	const int fallbacks0 = c->n_exact_fallbacks;
+	int rc = 0, r = 0;
+	for (; r < n_rep; ++r) {
+		const int n_sel = sel_off[r + 1] - sel_off[r];
+		const int32_t *idx = sel_idx + sel_off[r];
+		const double *ar = a + (size_t)r * n * n, *er = e + (size_t)r * 2 * n, *a0r = a0 + (size_t)r * n;
+		double *Sr = sums + (size_t)r * 5 * n, *Er = E ? E + (size_t)r * 2 * n : nullptr, *Lr = LL ? LL + r : nullptr;
+		if ((rc = psmc_hip_select(c, n_sel, idx)) == 0) rc = estep_factored_wide(c, ar, er, a0r, Sr, Er, Lr);
+		if (rc == PSMC_HIP_ECONVERGE) {
+			const std::string why = c->err;
+			rc = batch_exact_once(c, r, idx, n_sel, ar, er, a0r, nullptr, Sr, Er, Lr, why.c_str(), "wide fast");
+		}
+		if (rc) { c->err = "replicate " + std::to_string(r) + ": " + c->err; break; }
+		if (done) { const int32_t rr = r; done(user, 1, &rr); }
+	}
+	const std::string err = c->err;
+	const int rc_sel = psmc_hip_select(c, (int)keep.size(), keep.data()); // the caller's selection, whatever happened
+	if (rc) c->err = err;
+	c->wd_kind = WD_NONE; // (the last replicate's E-step set it: after a batch there is nothing to decode)
+	c->tables_batch = true;
+	c->last_batch_groups = r;
+	if (dbg_t) fprintf(stderr, "[psmc_hip] wide fast batch on device %d: %d replicates %.3f s, %d of them repeated on the exact kernels\n",
+	                   c->device, r, dbg_now() - t_call, c->n_exact_fallbacks - fallbacks0);
+	return rc ? rc : rc_sel;
 }
 
 extern "C" int psmc_hip_estep_batch(psmc_hip_ctx *c, int n_rep, const double *a, const double *e, const double *a0,
@@ -616,7 +667,8 @@ extern "C" int psmc_hip_estep_batch_cb(psmc_hip_ctx *c, int n_rep, const double 
 	if (c->n_seg < 1) return fail(c, PSMC_HIP_ESTATE, "estep_batch: no segments loaded");
 	HIPCHK(c, hipSetDevice(c->device));
 	c->wd_kind = WD_NONE; // (decoding after a batch needs a single E-step first, on the wide fast path as everywhere)
-	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return batch_exact(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user); // (beyond 128 states: the wide exact kernels whatever the mode)
+	if (batch_goes_wide(c, A, sums)) return batch_wide(c, n_rep, a, e, a0, sel_off, sel_idx, sums, E, LL, done, user);
+	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return batch_exact(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user); // (beyond 128 states: the wide exact kernels whatever the mode, unless "wide_batch" sent the call the other way)
 	return batch_fast(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user);
 }
 

@@ -3,8 +3,8 @@
 // "wide_fast" = 2 (kernels: estep_wide_fast_mw.hip, 2..4 waves per tile at the padded widths 512, 768 and 1024; plan, rounds and
 // options are the same, only WideLaunch knows the width and the waves).  With "wide_decode" = 1 the decoding entry points read
 // what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip up to 256 states, estep_wide_post_mw.hip beyond).  Everything else a context of that size does --
-// psmc_hip_estep, the batch, psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide
-// exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
+// psmc_hip_estep, the batch without "wide_batch" (with it: api_batch.hip batch_wide calls estep_factored_wide once per replicate),
+// psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
 //
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
 // of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,

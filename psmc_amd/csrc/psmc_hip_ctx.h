@@ -238,6 +238,9 @@ struct psmc_hip_ctx {
 	// and the exact tables are the newer ones; wd_sel: the selection serial it ran with (psmc_hip_select moves sel_serial on)
 	int wide_decode = 0;
 	int wd_kind = 0; unsigned long long wd_serial = 0, wd_sel = 0, sel_serial = 0;
+	// "wide_batch" = 1: psmc_hip_estep_batch[_cb] of such a context, asked for sums only, runs every replicate's E-step on the wide fast
+	// path -- on this context itself, one selection after the other: the path learns nothing, so no child contexts (api_batch.hip batch_wide)
+	int wide_batch = 0;
 };
 // the padded width of the wide fast path's own tables (api_wide_fast.hip writes them, api_decode.hip reads them): c->ns (192 or 256)
 // up to 256 states, beyond them the next multiple of 256 -- one wave of the tile per 256 states (c->ns stays what the wide exact

@@ -1,7 +1,8 @@
 /* boot.c -- config 4: the bootstrap farm of lh3/psmc (README:57-62 there: `seq 100 | xargs -i echo psmc -N25 ... -b
  * -o round-{}.psmc split.fa | sh`) as ONE process that keeps the trunks in HBM once and runs all replicates' EM
  * iterations together: the E-steps of a device's replicates go to it as one batch (psmc_hip_estep_batch_cb: exact
- * mode packs hundreds of trunk sweeps into one grid; fast mode keeps a learned tile plan per replicate), the
+ * mode packs hundreds of trunk sweeps into one grid; fast mode keeps a learned tile plan per replicate; beyond 128 states the
+ * exact grid whatever the mode, or with PSMC_HIP_WIDE the replicates' E-steps one after the other on the wide fast path), the
  * Hooke-Jeeves M-steps (host, em.c:56-68) run on host threads, one replicate each -- starting as soon as the batch
  * reports a replicate's statistics final, while the device is still busy with the rest of the batch.
  *
@@ -241,7 +242,7 @@ int psmc_boot_run(psmc_options *o, int n_rep, long seed0, const char *out_patter
 		if (rc) goto done_input;
 	}
 	replicate *rep = (replicate *)calloc((size_t)n_rep, sizeof(replicate));
-	const int factored = o->fast_mstep && bb->can_factor && N <= 128;
+	const int factored = o->fast_mstep && bb->can_factor && (N <= 128 || bb->wide_factor); /* (beyond 128 states only the wide fast batch has the sums without the counts) */
 	for (int r = 0; r < n_rep; ++r) { /* serial: drand48 is one global stream, re-seeded per replicate like a fresh process */
 		replicate *R = &rep[r];
 		char fn[4096];

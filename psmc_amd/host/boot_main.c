@@ -7,7 +7,10 @@
  * e.g.  psmc_boot -R 100 -S 1 -O round-%d.psmc -- -N25 -t15 -r5 -p "4+25*2+4+6" split.psmcfa
  * writes what  for r in 0..99: PSMC_SEED=$((1+r)) psmc -N25 -t15 -r5 -b -p ... -o round-$r.psmc split.psmcfa  would
  * (-b is implied).  PSMC_HIP_MODE=exact|fast and PSMC_FAST_MSTEP as for psmc; PSMC_HIP_DEVICES=0,1,.. (a device may be
- * listed several times = as many contexts on it; default: all visible devices, three times each in fast mode); OMP_NUM_THREADS bounds
+ * listed several times = as many contexts on it; default: all visible devices, three times each in fast mode); PSMC_HIP_WIDE=fast |
+ * fast-all as for psmc: with PSMC_HIP_MODE=fast and 129..256 (fast-all: 129..1024) states the replicates' E-steps run on the wide fast
+ * kernels (options "wide_fast" + "wide_batch"; one context per device by default: each keeps an X table over all trunks) and --main's
+ * run on them as psmc's would -- without it every E-step beyond 128 states uses the exact kernels; OMP_NUM_THREADS bounds
  * the M-step threads (default: the processors the control group's CPU quota allows, less the device threads); PSMC_TIMING=1 prints
  * per-iteration times to stderr.  A replicate's M-step starts when the batch reports its statistics final (psmc_hip_estep_batch_cb)
  * and runs under the rest of the batch.
@@ -79,7 +82,7 @@ static void usage(void)
 	fprintf(stderr, "Usage: psmc_boot -R <replicates> [-S <first seed>] -O <output pattern with %%d> [--main <out.psmc> --main-input <unsplit.psmcfa>]\n"
 	                "                 -- <psmc options> input.psmcfa\n"
 	                "       (replicate r = `PSMC_SEED=<seed+r> psmc -b <psmc options> -o <pattern %% r>`; --main: `psmc <psmc options> -o <out.psmc>\n"
-	                "        <unsplit.psmcfa>` beside them in the same job; PSMC_HIP_MODE, PSMC_HIP_DEVICES, PSMC_BOOT_MAIN_CUS)\n");
+	                "        <unsplit.psmcfa>` beside them in the same job; PSMC_HIP_MODE, PSMC_HIP_WIDE, PSMC_HIP_DEVICES, PSMC_BOOT_MAIN_CUS)\n");
 }
 
 int main(int argc, char *argv[])
@@ -131,6 +134,14 @@ int main(int argc, char *argv[])
 	const int mode = (mode_s && strcmp(mode_s, "fast") == 0) ? PSMC_HIP_MODE_FAST : PSMC_HIP_MODE_EXACT;
 	o.fast_mstep = fm ? atoi(fm) != 0 : (mode == PSMC_HIP_MODE_FAST);
 	om.fast_mstep = o.fast_mstep;
+	/* PSMC_HIP_WIDE as psmc reads it (main.c); no decoding here.  The wide fast path has the factored statistics only: it needs the O(N)
+	 * objective (PSMC_FACTORED=0 or PSMC_FAST_MSTEP=0 ask for full counts, which beyond 128 states only the exact kernels compute) */
+	const char *wide_s = getenv("PSMC_HIP_WIDE"), *fs = getenv("PSMC_FACTORED");
+	const int wide_level = !wide_s ? 0 : (strcmp(wide_s, "fast-all") == 0 ? 2 : (strcmp(wide_s, "fast") == 0 ? 1 : 0));
+	const int plan = psmc_mode_plan(mode == PSMC_HIP_MODE_FAST, wide_level, 0, n_states, 0);
+	const int wide = (plan & PSMC_PLAN_WIDE) && o.fast_mstep && mode == PSMC_HIP_MODE_FAST && !(fs && atoi(fs) == 0);
+	if (wide)
+		fprintf(stderr, "psmc_boot: %d hidden states: PSMC_HIP_WIDE=%s: the replicates' E-steps run on the wide fast kernels (factored statistics; full counts stay exact)\n", n_states, wide_s);
 	hip_bb h;
 	memset(&h, 0, sizeof h);
 	h.n_states = n_states;
@@ -144,18 +155,21 @@ int main(int argc, char *argv[])
 		 * E-step is a chain of short launches with host decisions in between, and the other threads' replicates fill the
 		 * gaps of the first (100 replicates of a 30 M-bin genome, per EM iteration: one context 1.19 s, two 0.69, three 0.585,
 		 * four 0.72, six 0.66: profiles/r05_fast_contexts.txt).  Exact mode packs the device with one batch already, and
-		 * wants all of the memory for its tables. */
-		const int nd = psmc_hip_device_count(), per = mode == PSMC_HIP_MODE_FAST ? 3 : 1;
+		 * wants all of the memory for its tables.  The wide fast path: one -- every context keeps an X table of 8 x the padded states
+		 * bytes per bin over ALL trunks. */
+		const int nd = psmc_hip_device_count(), per = mode == PSMC_HIP_MODE_FAST && !wide ? 3 : 1;
 		for (int d = 0; d < nd && n_list + per <= MAX_DEV; ++d)
 			for (int k = 0; k < per; ++k) list[n_list++] = d;
 	}
 	if (n_list > n_rep) n_list = n_rep;
 	if (n_list < 1) { fprintf(stderr, "psmc_boot: no MI355X visible; this build has no CPU path\n"); psmc_options_free(&o); return 2; }
 	for (int d = 0; d < n_list; ++d) {
-		const int rc = psmc_hip_create(&h.ctx[d], n_states, list[d], mode);
+		int rc = psmc_hip_create(&h.ctx[d], n_states, list[d], mode);
+		if (rc == 0) h.n_dev = d + 1;
+		if (rc == 0 && wide && (rc = psmc_hip_set_option(h.ctx[d], "wide_fast", wide_level)) == 0) rc = psmc_hip_set_option(h.ctx[d], "wide_batch", 1);
 		if (rc) {
 			fprintf(stderr, "psmc_boot: cannot start the E-step on device %d (%s); this build has no CPU path\n", list[d], psmc_hip_strerror(rc));
-			for (int k = 0; k < d; ++k) psmc_hip_destroy(h.ctx[k]);
+			for (int k = 0; k < h.n_dev; ++k) psmc_hip_destroy(h.ctx[k]);
 			psmc_options_free(&o);
 			return 2;
 		}
@@ -164,15 +178,15 @@ int main(int argc, char *argv[])
 	}
 	h.main_dev = -1;
 	h.n_rep = n_rep;
-	const char *fs = getenv("PSMC_FACTORED");
-	psmc_batch_backend bb = {&h, h.n_dev, bb_load, bb_estep_batch, bb_error, bb_destroy, mode == PSMC_HIP_MODE_FAST && !(fs && atoi(fs) == 0), bb_reserve, 0};
+	psmc_batch_backend bb = {&h, h.n_dev, bb_load, bb_estep_batch, bb_error, bb_destroy, mode == PSMC_HIP_MODE_FAST && !(fs && atoi(fs) == 0), bb_reserve, 0, wide};
 	/* the main run: a context of its own on the first device, begun (header, input, RD 0, tables) before the batch sizes its tables */
 	psmc_estep_backend be_main;
 	psmc_run_state *main_run = 0;
 	memset(&be_main, 0, sizeof be_main);
 	if (main_out) {
-		const int use_factored = om.fast_mstep && mode == PSMC_HIP_MODE_FAST && n_states <= 128 && !(fs && atoi(fs) == 0);
+		const int use_factored = om.fast_mstep && mode == PSMC_HIP_MODE_FAST && (n_states <= 128 || wide) && !(fs && atoi(fs) == 0);
 		int rc = psmc_hipbe_create(&be_main, n_states, mode, use_factored, 0, list[0]);
+		if (rc == 0 && wide) rc = psmc_hipbe_set_option(&be_main, "wide_fast", wide_level); /* as psmc does (main.c) */
 		if (rc == 0 && mode == PSMC_HIP_MODE_EXACT) { /* split the first device: [0, m) main run, [m, all) the batch contexts on it */
 			h.main_dev = list[0]; bb.main_done = bb_main_done;
 			const char *ms = getenv("PSMC_BOOT_MAIN_CUS");

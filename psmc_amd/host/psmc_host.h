@@ -190,6 +190,9 @@ typedef struct psmc_batch_backend {
 	/* optional (may be NULL): the main run that shared the first device (psmc_boot --main) has finished; called once per device, by
 	 * the thread that drives it, between two of its batches: the backend can give the batch the whole device back */
 	void (*main_done)(void *self, int dev);
+	/* can_factor holds beyond 128 states too (psmc_boot with PSMC_HIP_WIDE: the batch runs on the wide fast path, option "wide_batch").
+	 * Last, so that a backend initialised without it says no. */
+	int  wide_factor;
 } psmc_batch_backend;
 /* main_run (may be NULL): a psmc_run_begin()'ed run -- the un-resampled main run of README:49-53 on its own input -- whose EM
  * rounds psmc_boot_run drives on a thread of its own beside the replicates (psmc_boot --main) */

@@ -17,11 +17,19 @@
       of them are 8 n bytes per bin to the host), min | median | max in ms; and what the same request costs without the option:
       one exact E-step (full counts) + the same calls on the exact tables, once
 
+  (e) with --batch R: the bootstrap batch on the wide fast path ("wide_batch") -- R replicates, each a seeded multiset of the input's
+      segments (as many draws as segments, with replacement) with parameters of its own (the moving parameters of (a)):
+      seconds per replicate of psmc_hip_estep_batch with "wide_batch" = 1 (after one warm-up call: allocations), every replicate's
+      own time from the progress callback, one single wide E-step over ALL segments in the same process, and -- --batch-leg exact,
+      a process of its own so that a job can give each leg its time limit -- the same batch with "wide_batch" = 0: the exact
+      launch groups, what such a context ran before the option existed
+
 Library calls are synchronous.  Writes one JSON object to stdout (progress on stderr).
 
     python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
     python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
     python scripts/wide_fast_timing.py --decode --stress --states 300,1024
+    python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
 """
 import argparse
 import json
@@ -94,6 +102,43 @@ def library_part(hip, segs, n, steps, exact_steps):
         r["exact_ms"] = float(np.min(xs)) if xs else r["exact_first_ms"]
         r["exact_over_fast"] = r["exact_ms"] / r["fast_later_ms_mean"]
         print(json.dumps({"n%d" % n: {k: r[k] for k in ("exact_first_ms", "exact_ms", "exact_over_fast")}}), file=sys.stderr, flush=True)
+    return r
+
+
+def batch_part(hip, segs, n, n_rep, leg):
+    """(e): the replicates are the same for both legs (seeded)"""
+    ps = params_seq(n, n_rep)
+    rng = np.random.default_rng(97 + n)
+    sel = [[int(i) for i in rng.integers(0, len(segs), size=len(segs))] for _ in range(n_rep)]
+    r = {"replicates": n_rep, "selections": sel,
+         "unique_bins": [int(sum(len(segs[i]) for i in set(x))) for x in sel], "all_bins": int(sum(len(s) for s in segs))}
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_batch=1 if leg == "wide" else 0)
+    es.load_segments(segs)
+    if leg == "wide":
+        es.estep_batch(ps[:1], sel[:1], want="sums")   # warm-up: the X table and the plan's buffers
+        stamps = []
+        t = time.perf_counter()
+        es.estep_batch(ps, sel, want="sums", on_done=lambda reps, out: stamps.append(time.perf_counter()))
+        wall = time.perf_counter() - t
+        d = es.fast_diag()
+        r.update(wide_batch_s=wall, wide_batch_s_per_replicate=wall / n_rep,
+                 wide_replicate_s=[float(x) for x in np.diff([t] + stamps)],
+                 last_replicate=dict(tiles=d["n_chunks"], tile_len=d["tile_len"], fwd_rounds=d["fwd_rounds"], bwd_rounds=d["bwd_rounds"],
+                                     fwd_tiles=d["fwd_tiles"], bwd_tiles=d["bwd_tiles"]))
+        a, e, a0 = ps[0]
+        ms = []
+        for _ in range(4):   # the single E-step over all segments; the first one re-plans and is left out
+            t = time.perf_counter(); es.estep_factored(a, e[:2], a0); ms.append(time.perf_counter() - t)
+        d = es.fast_diag()
+        r.update(single_estep_s=float(np.mean(ms[1:])), single_estep_first_s=ms[0], single_tiles=d["n_chunks"], single_tile_len=d["tile_len"],
+                 batch_over_single=wall / n_rep / float(np.mean(ms[1:])))
+    else:
+        t = time.perf_counter()
+        es.estep_batch(ps, sel, want="sums")
+        wall = time.perf_counter() - t
+        r.update(exact_batch_s=wall, exact_batch_s_per_replicate=wall / n_rep, exact_launch_groups=es.batch_info()["groups"])
+    es.close()
+    print(json.dumps({"n%d" % n: r}), file=sys.stderr, flush=True)
     return r
 
 
@@ -185,6 +230,8 @@ def main():
     ap.add_argument("--decode", action="store_true", help="time the decoding calls on the wide fast tables (and on the exact ones) instead of (a), (b)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--full-post", action="store_true")
+    ap.add_argument("--batch", type=int, default=0, help="(e): the bootstrap batch of this many replicates on the wide fast path instead of (a), (b)")
+    ap.add_argument("--batch-leg", choices=["wide", "exact"], default="wide", help="with --batch: \"wide_batch\" = 1 and the single E-step, or the exact launch groups")
     ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
     args = ap.parse_args()
     from psmc_amd import hip, sim
@@ -199,7 +246,9 @@ def main():
         segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
         out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
     for n in [int(x) for x in args.states.split(",") if x]:
-        if args.decode:
+        if args.batch > 0:
+            out["n%d" % n] = batch_part(hip, segs, n, args.batch, args.batch_leg)
+        elif args.decode:
             out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0)
         else:
             out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps)
