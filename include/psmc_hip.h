@@ -19,7 +19,8 @@
  * runs psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip, and with "wide_fast" = 2 one
  * of 257..1024 states runs them on the multi-wave kernels of estep_wide_fast_mw.hip (PSMC-form matrices; full
  * counts and psmc_hip_get_tables stay exact; so does the batch unless "wide_batch" = 1 is set as well -- see psmc_hip_estep_batch --
- * and so does decoding unless "wide_decode" = 1 is -- beyond 256 states together with "wide_fast" = 2: see "Decoding on a FAST context");
+ * and so does decoding unless "wide_decode" = 1 is -- beyond 256 states together with "wide_fast" = 2: see "Decoding on a FAST context";
+ * the path's forward table X takes 8 x (192, 256, 512, 768 or 1024) bytes per bin, with the option "wide_ckpt" = 1 an eighth of that);
  * row-major FP64; a[k*n+l]=P(k->l) (khmm.h:34); e[b*n+k], b=0 hom / 1 het
  * (khmm.h:34; the missing-data row e[2][*]=1 of khmm.c:21 is implied);
  * a0[k] (khmm.h:36); observations are bytes 0/1/2 exactly as psmc_read_seq
@@ -86,14 +87,16 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           "max_rounds" and "learn" (1: a repair walks on through the failing tiles after it in the same round;
  *                           0: one tile per wave and round); with "structured" = 0 it answers ENOTSUP, as the factored statistics
  *                           do up to 128 states.  It keeps an X table of its own: 8 x 192 or 8 x 256 bytes per bin
- *                           (46 / 61 GB at 30 M bins), beside the exact tables.  psmc_hip_estep, psmc_hip_get_tables, the batch (without
+ *                           (46 / 61 GB at 30 M bins; with "wide_ckpt" = 1: 192 or 256 bytes per bin, 5.8 / 7.7 GB), beside the exact
+ *                           tables.  psmc_hip_estep, psmc_hip_get_tables, the batch (without
  *                           "wide_batch": see psmc_hip_estep_batch) and the decoding entry points (without "wide_decode") stay on the
  *                           exact kernels, bit for bit.  Exact mode and <= 128 states: no effect.
  *                           2: the same at 129..256 states (the same kernels, the same bits as 1), and a fast-mode context of 257..1024
  *                           states runs them on the kernels of estep_wide_fast_mw.hip: a tile is one work-group of 2, 3 or 4 waves
  *                           (padded widths 512, 768, 1024: 64 lanes x 4 states per wave), the waves exchange their scan totals through
  *                           LDS once per position.  Plan, options, ENOTSUP / ECONVERGE and diagnostics as for 1; the X table is 8 x 512,
- *                           8 x 768 or 8 x 1024 bytes per bin (PSMC_HIP_ENOMEM, with the table's size in the message, when it does
+ *                           8 x 768 or 8 x 1024 bytes per bin -- 123, 184 or 246 GB at 30 M bins; with "wide_ckpt" = 1: 512, 768 or 1024
+ *                           bytes per bin, 15, 23 or 31 GB -- (PSMC_HIP_ENOMEM, with the table's size in the message, when it does
  *                           not fit).  Everything else such a context does stays on the exact kernels -- the batch too, unless
  *                           "wide_batch" = 1 is set as well, and decoding, unless "wide_decode" = 1 is.
  *                           Other values: PSMC_HIP_EINVAL
@@ -106,6 +109,20 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           -- no effect.  (In the one release where "wide_fast" = 2 existed without this, the pair had no effect
  *                           beyond 256 states: a decode after a wide fast E-step read the exact tables of an OLDER E-step, or
  *                           answered ESTATE.)  Other values: PSMC_HIP_EINVAL
+ *  "wide_ckpt"     0        1: a wide fast E-step ("wide_fast", at every size it covers: psmc_hip_estep_factored[_device], the wide fast batch
+ *                           -- "wide_batch" --, every shard of a psmc_hip_group) keeps X at every 8th position only, plus the last row
+ *                           of every tile, and its accumulate sweep recomputes the seven rows between two checkpoints with the forward
+ *                           sweep's own arithmetic: the results are the full table's, bit for bit.  The table then takes S bytes per bin
+ *                           (S = 192, 256, 512, 768, 1024 padded states) plus 2 x 8 S bytes per tile instead of 8 S bytes per bin:
+ *                           7.7 GB instead of 61 GB at 200 states and 30 M bins, 31 GB instead of 246 GB at 1024 states.  The table is
+ *                           sized anew when the interval changes between two E-steps of a context (psmc_hip_wide_table_info reports it;
+ *                           psmc_hip_fast_info out[5] is 1 after a checkpointed E-step).  "wide_decode" = 1 wins: the decoding kernels
+ *                           read full rows, so while it is set a wide fast E-step keeps the full table whatever "wide_ckpt" says
+ *                           (PSMC_HIP_ENOMEM as under "wide_fast" when that does not fit) -- set "wide_decode" before the one E-step
+ *                           that is decoded, and the EM rounds before it run checkpointed.  Decoding from checkpoints is out of
+ *                           scope: psmc_hip_decode, _posterior, _post_counts and _scales after a checkpointed E-step ("wide_decode"
+ *                           set afterwards, no new E-step) answer PSMC_HIP_ESTATE.  Exact mode, up to 128 states (their own "ckpt"),
+ *                           "wide_fast" = 0: accepted, no effect.  Other values: PSMC_HIP_EINVAL
  *  "wide_batch"    0        1: psmc_hip_estep_batch[_cb] of a fast-mode context of 129..1024 states whose size "wide_fast" covers, asked for
  *                           sums and not for A, runs every replicate on the wide fast path (see psmc_hip_estep_batch, "wide fast batch").
  *                           0, and every other context or call: the batch as without the option.  Other values: PSMC_HIP_EINVAL
@@ -338,6 +355,12 @@ int psmc_hip_estep_factored(psmc_hip_ctx *ctx, const double *a, const double *e,
  * sweeps are chosen automatically when a[][] has the two rank-1
  * triangles psmc_update_hmm builds (core.c:112-122); otherwise the dense sweeps run. */
 int psmc_hip_fast_info(psmc_hip_ctx *ctx, int out[8]);
+
+/* Diagnostic: the forward table of the wide fast path ("wide_fast").  out = {rows of X currently allocated for it (the table; with
+ * "wide_ckpt" also every tile's last row, kept beside it), the padded width S of a row in states (8 S bytes), the checkpoint interval
+ * of the last wide fast E-step (1: every position, 8: "wide_ckpt"; 0: none ran yet), bytes held = rows x S x 8}.  All zeros on a
+ * context that never ran the path. */
+int psmc_hip_wide_table_info(psmc_hip_ctx *ctx, int64_t out[4]);
 
 /* Copies the forward/backward tables of one loaded segment to the host after
  * an E-step (replaces reading hd->f, hd->b, hd->s: aux.c:159-200).  f,b: L*n,

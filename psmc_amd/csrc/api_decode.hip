@@ -24,6 +24,10 @@ static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_t
 			snprintf(msg, sizeof msg, "%s: the last wide fast E-step returned an error (no converged tile boundaries to decode from)", who);
 			return fail(c, PSMC_HIP_ESTATE, msg);
 		}
+		if (c->wf_last_iv != 1) { // ("wide_ckpt" without "wide_decode" at that E-step: the decoding kernels read full X rows)
+			snprintf(msg, sizeof msg, "%s: the last wide E-step kept checkpoints only (\"wide_ckpt\": X at every 8th bin); run an E-step with \"wide_decode\" = 1 first", who);
+			return fail(c, PSMC_HIP_ESTATE, msg);
+		}
 		if (c->wd_sel != c->sel_serial) {
 			snprintf(msg, sizeof msg, "%s: the selection changed since the last E-step", who);
 			return fail(c, PSMC_HIP_ESTATE, msg);

@@ -771,7 +771,7 @@ extern "C" int psmc_hip_fast_info(psmc_hip_ctx *c, int out[8])
 	if (!c || !out) return PSMC_HIP_EINVAL;
 	if (c->wf_ran) { // the wide path (129..256 states: one tile per wave; 257..1024: one per work-group): no items
 		const int nc = (int)c->wf_chunks.size();
-		out[0] = 1; out[1] = c->wf_T; out[2] = nc; out[3] = nc; out[4] = 3; out[5] = 0; out[6] = 1; out[7] = 0;
+		out[0] = 1; out[1] = c->wf_T; out[2] = nc; out[3] = nc; out[4] = 3; out[5] = c->wf_last_iv == 8 ? 1 : 0; out[6] = 1; out[7] = 0;
 		return PSMC_HIP_OK;
 	}
 	out[0] = c->use_struct ? 1 : 0; out[1] = c->chunk_used; out[2] = c->use_struct ? c->n_items_f : (int)c->chunks.size();

@@ -5,6 +5,9 @@
 // what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip up to 256 states, estep_wide_post_mw.hip beyond).  Everything else a context of that size does --
 // psmc_hip_estep, the batch without "wide_batch" (with it: api_batch.hip batch_wide calls estep_factored_wide once per replicate),
 // psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
+// "wide_ckpt" = 1: X at every 8th position only (S bytes per bin) plus every tile's last row, the accumulate sweep recomputes the rest
+// (estep_wide_fast.hip); "wide_decode" = 1 wins, because the decoding kernels read full rows.  The table is sized anew when the interval
+// changes between two E-steps, and what ran is recorded for fast_info, psmc_hip_wide_table_info and decode_source.
 //
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
 // of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,
@@ -21,13 +24,17 @@ static constexpr int WF_NACC = 7; // SL SU DG CL CU E0 E1 per tile
 void free_wide_fast(psmc_hip_ctx *c)
 {
 	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
-	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list};
+	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi};
 	for (void *q : p) if (q) (void)hipFree(q);
 	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
 	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
 	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
+	c->d_wf_xhi = nullptr; c->wf_xhi_cap = 0; c->wf_rows = 0; c->wf_tab_iv = c->wf_last_iv = 0;
 	c->wf_cap = 0; c->wf_bins = 0;
 }
+
+// rows of the X table over `bins` positions at one row per `iv` positions (iv = 8: the rows at p % 8 == 0, by absolute position)
+static inline int64_t wide_table_rows(int64_t bins, int iv) { return (bins + iv - 1) / iv; }
 
 // Tiles of T bins (option "chunk", else about WF_TILES tiles: four waves per SIMD of an MI355X -- the forward sweep fits four at
 // up to 110 VGPRs; the accumulate sweep, at 154 / 206 VGPRs, fits three (192 states) or two (256) and runs the tiles in two generations), every one speculating "warmup" bins in both directions -- by default WF_WARMUP, not the 3072 of
@@ -133,15 +140,25 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	if (!c->d_wf_par && (rc = dev_alloc(c, &c->d_wf_par, (size_t)WF_PAR * S))) return rc;
 	if ((c->plan_dirty || c->wf_chunks.empty()) && (rc = plan_wide(c))) return rc;
 	const int64_t bins = c->total + 128;
-	if (c->wf_bins < bins) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins; 8 KB per bin at S = 1024)
-		if ((rc = dev_alloc(c, &c->d_wf_X, (size_t)bins * S))) {
-			c->wf_bins = 0;
-			snprintf(msg, sizeof msg, "estep_factored: no device memory for the X table of the wide fast path: %lld bytes (%lld bins x %d padded states x 8)",
-			         (long long)bins * S * 8, (long long)bins, S);
+	// "wide_ckpt": one X row per 8 positions -- unless "wide_decode" is on: the decoding kernels read full rows, so that E-step keeps them
+	const int iv = c->wide_ckpt && !c->wide_decode ? 8 : 1;
+	const int nt = (int)c->wf_chunks.size();
+	c->wf_last_iv = 0;
+	if (c->wf_bins < bins || c->wf_tab_iv != iv) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins; 8 KB per bin at S = 1024), with "wide_ckpt" S bytes per bin; sized anew when the interval changes, whether it grows or shrinks
+		const int64_t rows = wide_table_rows(bins, iv);
+		c->wf_bins = 0; c->wf_rows = 0; c->wf_tab_iv = 0;
+		if ((rc = dev_alloc(c, &c->d_wf_X, (size_t)rows * S))) {
+			snprintf(msg, sizeof msg, "estep_factored: no device memory for the X table of the wide fast path: %lld bytes (%lld bins x %d padded states x 8%s)",
+			         (long long)rows * S * 8, (long long)bins, S, iv == 8 ? " / 8: \"wide_ckpt\"" : "");
 			return fail(c, PSMC_HIP_ENOMEM, msg);
 		}
-		if ((rc = dev_alloc(c, &c->d_wf_inv, (size_t)bins))) { c->wf_bins = 0; return rc; }
-		c->wf_bins = bins;
+		if ((rc = dev_alloc(c, &c->d_wf_inv, (size_t)bins))) return rc;
+		c->wf_bins = bins; c->wf_rows = rows; c->wf_tab_iv = iv;
+	}
+	if (iv == 8 && c->wf_xhi_cap < nt) { // every tile's last row X_hi
+		c->wf_xhi_cap = 0;
+		if ((rc = dev_alloc(c, &c->d_wf_xhi, (size_t)nt * S))) return rc;
+		c->wf_xhi_cap = nt;
 	}
 	HIPCHK(c, hipStreamSynchronize(c->stream)); // the previous upload out of the pinned staging block
 	double *hp = c->h_wf_par;
@@ -156,14 +173,14 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	WideLaunch w;
 	memset(&w, 0, sizeof(w));
 	w.stream = st; w.ns = S; w.n_states = n; w.n_tiles = (int)c->wf_chunks.size(); w.chain = c->learn ? 1 : 0;
-	w.waves = wf_waves(c);
+	w.waves = wf_waves(c); w.ckpt = iv; w.xhi = iv == 8 ? c->d_wf_xhi : nullptr;
 	w.tol = c->warm_tol; w.tiny_total = (double)c->sel.size() * HMM_TINY_H;
 	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks; w.list = c->d_wf_list; w.dirty = c->d_wf_dirty;
 	w.cnt = c->d_cnt; w.warm = c->d_warm;
 	w.X = c->d_wf_X; w.inv = c->d_wf_inv; w.entry = c->d_wf_entry; w.bentry = c->d_wf_bentry; w.bexit = c->d_wf_bexit;
 	w.part = c->d_wf_part; w.LLpart = c->d_wf_ll; w.stage = c->d_stage; w.out = d_out;
 	c->report = FastReport{0, 0, 0, 0, 0, 0, 2};
-	c->wf_ran = true; c->last_fused = 3;
+	c->wf_ran = true; c->last_fused = 3; c->wf_last_iv = iv;
 	if (launch_wide_fast(w, WF_FWD) || launch_wide_fast(w, WF_BWARM)) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
 	int r = 0, t = 0;
 	rc = wide_rounds(c, w, false, r, t);
@@ -198,5 +215,15 @@ int estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const
 	for (double &v : c->last_ms) v = 0.0;
 	c->last_ms[0] = ms;
 	unpack_factored(h.data(), n, sums, E, LL);
+	return PSMC_HIP_OK;
+}
+
+// rows of X held for the wide fast path (the table, and with "wide_ckpt" the tiles' last rows beside it), their width, the interval
+// of the last wide fast E-step, bytes
+extern "C" int psmc_hip_wide_table_info(psmc_hip_ctx *c, int64_t out[4])
+{
+	if (!c || !out) return PSMC_HIP_EINVAL;
+	const int64_t rows = c->wf_rows + c->wf_xhi_cap;
+	out[0] = rows; out[1] = rows ? wf_width(c) : 0; out[2] = c->wf_last_iv; out[3] = rows * out[1] * 8;
 	return PSMC_HIP_OK;
 }

@@ -21,6 +21,24 @@
 // A chain never enters a tile that is itself the head of a repair in the same launch, nor the neighbour whose boundary vector such a
 // head starts from: no wave of a repair launch reads or writes what another wave of it writes, so the result does not depend on
 // scheduling.  A tile a chain stops in front of is flagged again by the next verify round.
+//
+// "wide_ckpt" (compile-time variants CKPT of k_wf_fwd and k_wf_acc; the full-table kernels keep their code): X keeps the rows at
+// p % 8 == 0 only, by absolute position (wide_prims.h ckpt_row), and every tile's last row goes to xhi[b], which k_wf_verify, the
+// start of a forward repair and k_wf_ll read instead of X_{lo-1} / X_L.  The accumulate sweep recomputes the seven rows between two
+// checkpoints into LDS with fstep (wide_prims.h), the forward sweep's own step, from the scale factors that sweep stored: the same
+// bits as the full table.  A chained repair rewrites the checkpoints and last rows of the tiles it walks through; what it may
+// not enter is unchanged (a head reads its neighbour's xhi row where it read the neighbour's last X row).
+//
+// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; scratch is 0 everywhere; LDS in bytes per wave):
+//   kernel                      S=192: VGPRs  LDS     S=256: VGPRs       LDS
+//   k_wf_fwd    / repair             86 /  90   0          108 / 112       0
+//   k_wf_fwd    / repair, CKPT       88 /  92   0          110 / 114       0
+//   k_wf_acc    / repair            154 / 178   0          206 / 228       0
+//   k_wf_acc    / repair, CKPT      196 / 220   10752      256 / 256+24 AGPRs  14336
+//   k_wf_verify                      33 /  36 (backward)    36 /  39       0
+//   k_wf_ll                          37          0           38            0
+// The CKPT accumulate sweep runs two tiles per SIMD at either width (the full-table one three at 192 states): eight waves' staged
+// rows are 84 / 112 KB of the compute unit's 160 KB.
 #include <hip/hip_runtime.h>
 #include "wave_prims.h"
 #include "struct_prims.h"
@@ -34,11 +52,13 @@ namespace wide {
 constexpr int WACC = 7; // SL SU DG CL CU E0 E1
 
 // ------------------------------------------------------------------ forward
-template <int NPL, bool REPAIR>
+// CKPT ("wide_ckpt"): X keeps the rows at p % 8 == 0 only (ckpt_row), and the tile's last row X_hi goes to xhi[b] -- what the
+// neighbour's verify and repair and k_wf_ll read; the accumulate sweep recomputes the rest.
+template <int NPL, bool REPAIR, bool CKPT>
 __global__ __launch_bounds__(64) void k_wf_fwd(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                  const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
                                                  const int *__restrict__ dirty, int chain, double tol, double *__restrict__ X,
-                                                 double *__restrict__ inv, double *__restrict__ entry)
+                                                 double *__restrict__ inv, double *__restrict__ entry, double *__restrict__ xhi)
 {
 	constexpr int S = 64 * NPL;
 	const int lane = threadIdx.x, k0 = NPL * lane;
@@ -53,7 +73,7 @@ __global__ __launch_bounds__(64) void k_wf_fwd(const double *__restrict__ par, c
 	double x[NPL];
 	int p0;
 	if (REPAIR) { // from the neighbour's X_{lo-1} (a repaired tile is never a segment's first)
-		ld<NPL>(X + (c.off + c.lo - 2) * S + k0, x);
+		if (CKPT) ld<NPL>(xhi + (int64_t)(b - 1) * S + k0, x); else ld<NPL>(X + (c.off + c.lo - 2) * S + k0, x);
 		p0 = c.lo;
 	} else {
 		const int ws = max(1, c.lo - c.wf);
@@ -63,7 +83,8 @@ __global__ __launch_bounds__(64) void k_wf_fwd(const double *__restrict__ par, c
 			emis<NPL>((int)obs[c.off] & 3, e0, e1, ev);
 #pragma unroll
 			for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
-			if (c.lo == 1) st<NPL>(X + c.off * S + k0, x);
+			if (CKPT) { if (c.lo == 1 && c.hi == 1) st<NPL>(xhi + (int64_t)b * S + k0, x); } // (the accumulate sweep recomputes X_1)
+			else if (c.lo == 1) st<NPL>(X + c.off * S + k0, x);
 			p0 = 2;
 		} else p0 = ws;
 	}
@@ -79,18 +100,16 @@ __global__ __launch_bounds__(64) void k_wf_fwd(const double *__restrict__ par, c
 				const int p = 4 * g + j + 1;
 				if (p < p0 || p > hi) continue;
 				if (p == lo && p != p0) st<NPL>(entry + (int64_t)b * S + k0, x);
-				double ev[NPL];
-				emis<NPL>((int)((w >> (8 * j)) & 3u), e0, e1, ev);
-				if (j == 3) { // p % 4 == 0: 1/d_p, a power of two (struct_prims.h pow2_rcp)
-					const double iv = pow2_rcp(wave_total(lsum<NPL>(x)));
-#pragma unroll
-					for (int i = 0; i < NPL; ++i) ev[i] *= iv;
+				const int sym = (int)((w >> (8 * j)) & 3u);
+				if (j == 3) { // p % 4 == 0: scaled by 1/d_p
+					const double iv = fstep<NPL, true, false>(sc, wm, sym, e0, e1, x, 1.0);
 					if (p >= lo && lane == 0) io[p - 1] = iv;
+				} else fstep<NPL, false, false>(sc, wm, sym, e0, e1, x, 1.0);
+				if (!CKPT) { if (p >= lo) st<NPL>(fo + (int64_t)(p - 1) * S, x); }
+				else if (p >= lo) {
+					if (j == 3 && (p & (WCK - 1)) == 0) st<NPL>(X + ckpt_row(c.off, p) * S + k0, x);
+					if (p == hi) st<NPL>(xhi + (int64_t)b * S + k0, x);
 				}
-				wstep<NPL>(sc, x, wm);
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
-				if (p >= lo) st<NPL>(fo + (int64_t)(p - 1) * S, x);
 			}
 		}
 		if (!REPAIR || !chain) break;
@@ -188,11 +207,16 @@ __device__ __forceinline__ void astep(const StructParN<NPL> &sc, const WaveScanM
 		I_lane *= f;
 	}
 }
-template <int NPL, bool REPAIR>
+// CKPT ("wide_ckpt"): X holds the rows at p % 8 == 0 only.  The tile is swept in blocks of the positions 8m .. 8m+7, the top block
+// first: the block's rows are recomputed forward with fstep -- the forward sweep's own step and its stored scale factors, so its
+// bits -- from the checkpoint X_{8m}, or in the tile's lowest block from entry[b] (the X_{lo-1} the tile was built on) or from
+// X_1 = a0 e[o_1], into LDS (rows 8m+1 .. 8m+7: 7 S doubles, every lane reads back what it wrote itself, so no barrier); then astep runs
+// over them, highest position first, X_{8m} read from the table.
+template <int NPL, bool REPAIR, bool CKPT>
 __global__ __launch_bounds__(64) void k_wf_acc(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                  const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
                                                  const int *__restrict__ dirty, int chain, double tol, const double *__restrict__ X,
-                                                 const double *__restrict__ inv, double *__restrict__ bentry,
+                                                 const double *__restrict__ inv, const double *__restrict__ entry, double *__restrict__ bentry,
                                                  double *__restrict__ bexit, double *__restrict__ part)
 {
 	constexpr int S = 64 * NPL;
@@ -217,7 +241,43 @@ __global__ __launch_bounds__(64) void k_wf_acc(const double *__restrict__ par, c
 		for (int q = 0; q < WACC; ++q)
 #pragma unroll
 			for (int i = 0; i < NPL; ++i) acc[q][i] = 0.0;
-		if (top >= lo) {
+		if (CKPT && top >= lo) {
+			__shared__ double rows[(WCK - 1) * S];
+			double *my = rows + k0;
+			StructParN<NPL> fs;
+			fwd_roles<NPL>(sc, fs);
+			for (int q = top & ~(WCK - 1); q + WCK - 1 >= lo; q -= WCK) { // the block of the positions q .. q+7, within lo .. top
+				const int pb = max(lo, q), pe = min(top, q + WCK - 1);
+				double xf[NPL];
+				int p;
+				if (q >= lo) { ld<NPL>(X + ckpt_row(c.off, q) * S + k0, xf); p = q + 1; }
+				else if (lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, xf); p = lo; }
+				else { // X_1 = a0 e[o_1], as the forward sweep starts a segment
+					double ev[NPL];
+					ld<NPL>(par + WP_A0 * S + k0, xf);
+					emis<NPL>((int)o[0] & 3, e0, e1, ev);
+#pragma unroll
+					for (int i = 0; i < NPL; ++i) xf[i] *= ev[i];
+					st<NPL>(my, xf);
+					p = 2;
+				}
+				for (; p <= pe; ++p) {
+					const int sym = (int)o[p - 1] & 3;
+					if ((p & 3) == 0) fstep<NPL, true, true>(fs, wm, sym, e0, e1, xf, io[p - 1]);
+					else fstep<NPL, false, true>(fs, wm, sym, e0, e1, xf, 1.0);
+					st<NPL>(my + ((p & (WCK - 1)) - 1) * S, xf);
+				}
+				for (p = pe; p >= pb; --p) {
+					double Xc[NPL];
+					if (p & (WCK - 1)) ld<NPL>(my + ((p & (WCK - 1)) - 1) * S, Xc); else ld<NPL>(X + ckpt_row(c.off, p) * S + k0, Xc);
+					const int sym = (int)o[p - 1] & 3;
+					if ((p & 3) == 0) astep<NPL, true>(sc, wm, sym, e0, e1, Xc, x, io[p - 1], acc, accI);
+					else astep<NPL, false>(sc, wm, sym, e0, e1, Xc, x, 1.0, acc, accI);
+				}
+			}
+			st<NPL>(bexit + (int64_t)b * S + k0, x); // bt_lo
+		}
+		if (!CKPT && top >= lo) {
 			double Xc[NPL], Xn[NPL];
 			ld<NPL>(fo + (int64_t)(top - 1) * S, Xc);
 			for (int g = (top - 1) >> 2; g >= 0 && 4 * g + 4 >= lo; --g) {
@@ -265,7 +325,7 @@ __global__ __launch_bounds__(64) void k_wf_acc(const double *__restrict__ par, c
 // ------------------------------------------------------------------ verify, LL, reduce
 template <int NPL, bool BWD>
 __global__ __launch_bounds__(64) void k_wf_verify(const Chunk *__restrict__ chunks, int n, double tol, const double *__restrict__ X,
-                                                    const double *__restrict__ mine, const double *__restrict__ bexit,
+                                                    const double *__restrict__ xhi, const double *__restrict__ mine, const double *__restrict__ bexit,
                                                     int *__restrict__ dirty, int *__restrict__ cnt, unsigned long long *__restrict__ warm)
 {
 	constexpr int S = 64 * NPL;
@@ -278,7 +338,8 @@ __global__ __launch_bounds__(64) void k_wf_verify(const Chunk *__restrict__ chun
 	if (check) {
 		double u[NPL], v[NPL];
 		ld<NPL>(mine + (int64_t)b * S + k0, u);
-		ld<NPL>(BWD ? bexit + (int64_t)(b + 1) * S + k0 : X + (c.off + c.lo - 2) * S + k0, v);
+		// (xhi: "wide_ckpt" -- the neighbour's last row X_{lo-1} is in the per-tile array, not in X)
+		ld<NPL>(BWD ? bexit + (int64_t)(b + 1) * S + k0 : (xhi ? xhi + (int64_t)(b - 1) * S + k0 : X + (c.off + c.lo - 2) * S + k0), v);
 		m = wmismatch<NPL>(u, v);
 	}
 	if (lane == 0) {
@@ -290,8 +351,8 @@ __global__ __launch_bounds__(64) void k_wf_verify(const Chunk *__restrict__ chun
 }
 
 template <int NPL>
-__global__ __launch_bounds__(64) void k_wf_ll(const Chunk *__restrict__ chunks, const double *__restrict__ X, const double *__restrict__ inv,
-                                                const double *__restrict__ entry, double *__restrict__ LLpart)
+__global__ __launch_bounds__(64) void k_wf_ll(const Chunk *__restrict__ chunks, const double *__restrict__ X, const double *__restrict__ xhi,
+                                                const double *__restrict__ inv, const double *__restrict__ entry, double *__restrict__ LLpart)
 {
 	constexpr int S = 64 * NPL;
 	const int lane = threadIdx.x, k0 = NPL * lane, b = blockIdx.x;
@@ -308,11 +369,11 @@ __global__ __launch_bounds__(64) void k_wf_ll(const Chunk *__restrict__ chunks, 
 	double u[NPL];
 	if (c.lo > 1) { // the tile was computed from entry = X_{lo-1} up to a factor: put the telescoping sum back in step
 		double v[NPL];
-		ld<NPL>(X + (c.off + c.lo - 2) * S + k0, u); ld<NPL>(entry + (int64_t)b * S + k0, v);
+		ld<NPL>(xhi ? xhi + (int64_t)(b - 1) * S + k0 : X + (c.off + c.lo - 2) * S + k0, u); ld<NPL>(entry + (int64_t)b * S + k0, v); // (xhi: "wide_ckpt", as k_wf_verify)
 		ll += log(wave_total(lsum<NPL>(u))) - log(wave_total(lsum<NPL>(v)));
 	}
 	if (c.hi == c.L) {
-		ld<NPL>(X + (c.off + c.L - 1) * S + k0, u);
+		ld<NPL>(xhi ? xhi + (int64_t)b * S + k0 : X + (c.off + c.L - 1) * S + k0, u);
 		// a segment of one bin: LL is this logarithm alone, log sum_k a0[k] e[o_1][k], and the rounding of the sum is all its
 		// error (log at 0.93 magnifies one unit in the last place 14 times) -- add it up without one.  Longer segments keep
 		// the plain sum: their LL adds hundreds of logarithms, and the last unit of this one is far below what those leave.
@@ -364,16 +425,31 @@ template <int NPL> static int launch_all(const WideLaunch &w, int what, int n_li
 	constexpr int S = 64 * NPL;
 	const int nc = w.n_tiles;
 	hipStream_t st = w.stream;
+	const bool ck = w.ckpt == WCK;                      // "wide_ckpt": X at every 8th position, the tiles' last rows in w.xhi
+	const double *xhi = ck ? w.xhi : nullptr;
+	if (w.ckpt != 1 && !(ck && w.xhi)) return -1;
 	switch (what) {
-	case WF_FWD: hipLaunchKernelGGL((k_wf_fwd<NPL, false>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry); break;
-	case WF_FWD_REPAIR: hipLaunchKernelGGL((k_wf_fwd<NPL, true>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry); break;
+	case WF_FWD:
+		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, false, true>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi);
+		else hipLaunchKernelGGL((k_wf_fwd<NPL, false, false>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi);
+		break;
+	case WF_FWD_REPAIR:
+		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, true, true>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi);
+		else hipLaunchKernelGGL((k_wf_fwd<NPL, true, false>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi);
+		break;
 	case WF_BWARM: hipLaunchKernelGGL(k_wf_bwarm<NPL>, dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, w.bentry); break;
-	case WF_ACC: hipLaunchKernelGGL((k_wf_acc<NPL, false>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.bentry, w.bexit, w.part); break;
-	case WF_ACC_REPAIR: hipLaunchKernelGGL((k_wf_acc<NPL, true>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.bentry, w.bexit, w.part); break;
-	case WF_VERIFY_F: hipLaunchKernelGGL((k_wf_verify<NPL, false>), dim3(nc), dim3(64), 0, st, w.chunks, nc, w.tol, w.X, w.entry, w.bexit, w.dirty, w.cnt, w.warm); break;
-	case WF_VERIFY_B: hipLaunchKernelGGL((k_wf_verify<NPL, true>), dim3(nc), dim3(64), 0, st, w.chunks, nc, w.tol, w.X, w.bentry, w.bexit, w.dirty, w.cnt + 1, w.warm + 1); break;
+	case WF_ACC:
+		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, false, true>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		else hipLaunchKernelGGL((k_wf_acc<NPL, false, false>), dim3(nc), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		break;
+	case WF_ACC_REPAIR:
+		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, true, true>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		else hipLaunchKernelGGL((k_wf_acc<NPL, true, false>), dim3(n_list), dim3(64), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		break;
+	case WF_VERIFY_F: hipLaunchKernelGGL((k_wf_verify<NPL, false>), dim3(nc), dim3(64), 0, st, w.chunks, nc, w.tol, w.X, xhi, w.entry, w.bexit, w.dirty, w.cnt, w.warm); break;
+	case WF_VERIFY_B: hipLaunchKernelGGL((k_wf_verify<NPL, true>), dim3(nc), dim3(64), 0, st, w.chunks, nc, w.tol, w.X, xhi, w.bentry, w.bexit, w.dirty, w.cnt + 1, w.warm + 1); break;
 	case WF_FINISH:
-		hipLaunchKernelGGL(k_wf_ll<NPL>, dim3(nc), dim3(64), 0, st, w.chunks, w.X, w.inv, w.entry, w.LLpart);
+		hipLaunchKernelGGL(k_wf_ll<NPL>, dim3(nc), dim3(64), 0, st, w.chunks, w.X, xhi, w.inv, w.entry, w.LLpart);
 		hipLaunchKernelGGL(k_wf_reduce1<S>, dim3(WACC + 1, RED_ROWS), dim3(S), 0, st, w.part, nc, w.LLpart, w.stage);
 		hipLaunchKernelGGL(k_wf_reduce2<S>, dim3(WACC + 1), dim3(S), 0, st, w.stage, w.tiny_total, w.n_states, w.out);
 		break;

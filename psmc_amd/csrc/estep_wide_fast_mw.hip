@@ -33,6 +33,13 @@
 //   k_mw_verify                  40   192           40   288           40   384
 //   k_mw_ll                      38   192           38   288           38   384
 //   k_mw_reduce1 / 2           8 / 42 VGPRs at every width, no LDS
+// "wide_ckpt" (compile-time variants CKPT, as in estep_wide_fast.hip: X at p % 8 == 0 only, the tiles' last rows in xhi, the accumulate
+// sweep recomputes the rest with mw_fstep); LDS = the exchange slots + 7 rows of S doubles:
+//   k_mw_fwd   CKPT             116   192          120   288          128   384
+//   k_mw_fwd   CKPT (repair)    126   192          130   288          138   384
+//   k_mw_acc   CKPT             220   28864        224   43296        226   57728
+//   k_mw_acc   CKPT (repair)    248   28864        252   43296        252   57728
+// Two waves per SIMD as without CKPT: four (W = 2) or two (W = 3, 4) work-groups per compute unit, at most 115 KB of its 160 KB of LDS.
 #include <hip/hip_runtime.h>
 #include "wave_prims.h"
 #include "struct_prims.h"
@@ -70,11 +77,12 @@ template <int W> __device__ __forceinline__ double mw_mismatch(const double (&u)
 }
 
 // ------------------------------------------------------------------ forward
-template <int W, bool REPAIR>
+// CKPT ("wide_ckpt"): as k_wf_fwd -- X keeps the rows at p % 8 == 0 only, the tile's last row goes to xhi[b]
+template <int W, bool REPAIR, bool CKPT>
 __global__ __launch_bounds__(64 * W) void k_mw_fwd(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                      const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
                                                      const int *__restrict__ dirty, int chain, double tol, double *__restrict__ X,
-                                                     double *__restrict__ inv, double *__restrict__ entry)
+                                                     double *__restrict__ inv, double *__restrict__ entry, double *__restrict__ xhi)
 {
 	constexpr int NPL = MW_NPL, S = 64 * NPL * W;
 	__shared__ double xs[2 * MW_SLOTS * W];
@@ -94,7 +102,7 @@ __global__ __launch_bounds__(64 * W) void k_mw_fwd(const double *__restrict__ pa
 	double x[NPL];
 	int p0;
 	if (REPAIR) { // from the neighbour's X_{lo-1} (a repaired tile is never a segment's first)
-		ld<NPL>(X + (c.off + c.lo - 2) * S + k0, x);
+		if (CKPT) ld<NPL>(xhi + (int64_t)(b - 1) * S + k0, x); else ld<NPL>(X + (c.off + c.lo - 2) * S + k0, x);
 		p0 = c.lo;
 	} else {
 		const int ws = max(1, c.lo - c.wf);
@@ -104,7 +112,8 @@ __global__ __launch_bounds__(64 * W) void k_mw_fwd(const double *__restrict__ pa
 			emis<NPL>((int)obs[c.off] & 3, e0, e1, ev);
 #pragma unroll
 			for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
-			if (c.lo == 1) st<NPL>(X + c.off * S + k0, x);
+			if (CKPT) { if (c.lo == 1 && c.hi == 1) st<NPL>(xhi + (int64_t)b * S + k0, x); } // (the accumulate sweep recomputes X_1)
+			else if (c.lo == 1) st<NPL>(X + c.off * S + k0, x);
 			p0 = 2;
 		} else p0 = ws;
 	}
@@ -120,17 +129,16 @@ __global__ __launch_bounds__(64 * W) void k_mw_fwd(const double *__restrict__ pa
 				const int p = 4 * g + j + 1;
 				if (p < p0 || p > hi) continue; // (the same in every wave: the exchange below is reached by all or none)
 				if (p == lo && p != p0) st<NPL>(entry + (int64_t)b * S + k0, x);
-				double ev[NPL];
-				emis<NPL>((int)((w >> (8 * j)) & 3u), e0, e1, ev);
-				if (j == 3) { // p % 4 == 0: 1/d_p, a power of two (struct_prims.h pow2_rcp)
-					const double iv = pow2_rcp(mw_step<W, true>(sc, x, wm, xc));
-#pragma unroll
-					for (int i = 0; i < NPL; ++i) ev[i] *= iv;
+				const int sym = (int)((w >> (8 * j)) & 3u);
+				if (j == 3) { // p % 4 == 0: scaled by 1/d_p, a power of two (struct_prims.h pow2_rcp)
+					const double iv = mw_fstep<W, true, false>(sc, wm, sym, e0, e1, x, 1.0, xc);
 					if (p >= lo && tid == 0) io[p - 1] = iv;
-				} else mw_step<W, false>(sc, x, wm, xc);
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
-				if (p >= lo) st<NPL>(fo + (int64_t)(p - 1) * S, x);
+				} else mw_fstep<W, false, false>(sc, wm, sym, e0, e1, x, 1.0, xc);
+				if (!CKPT) { if (p >= lo) st<NPL>(fo + (int64_t)(p - 1) * S, x); }
+				else if (p >= lo) {
+					if (j == 3 && (p & (WCK - 1)) == 0) st<NPL>(X + ckpt_row(c.off, p) * S + k0, x);
+					if (p == hi) st<NPL>(xhi + (int64_t)b * S + k0, x);
+				}
 			}
 		}
 		if (!REPAIR || !chain) break;
@@ -238,11 +246,15 @@ __device__ __forceinline__ void mw_astep(const StructParN<MW_NPL> &sc, const Wav
 		I_lane *= f;
 	}
 }
-template <int W, bool REPAIR>
+// CKPT ("wide_ckpt"): as k_wf_acc -- block by block from the tile's top block down, the block's rows recomputed forward with
+// mw_fstep (every recomputed step's exchange as k_mw_fwd does it) into LDS (7 S doubles: 56 KB at W = 4, beside the exchange slots;
+// every thread reads back what it wrote itself), X_{8m} read from the table.  The block bounds come from the tile descriptor
+// alone, so every wave of the work-group goes through the same exchanges.
+template <int W, bool REPAIR, bool CKPT>
 __global__ __launch_bounds__(64 * W) void k_mw_acc(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                      const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
                                                      const int *__restrict__ dirty, int chain, double tol, const double *__restrict__ X,
-                                                     const double *__restrict__ inv, double *__restrict__ bentry,
+                                                     const double *__restrict__ inv, const double *__restrict__ entry, double *__restrict__ bentry,
                                                      double *__restrict__ bexit, double *__restrict__ part)
 {
 	constexpr int NPL = MW_NPL, S = 64 * NPL * W;
@@ -269,7 +281,43 @@ __global__ __launch_bounds__(64 * W) void k_mw_acc(const double *__restrict__ pa
 		for (int q = 0; q < MW_ACC; ++q)
 #pragma unroll
 			for (int i = 0; i < NPL; ++i) acc[q][i] = 0.0;
-		if (top >= lo) { // (the same in every wave)
+		if (CKPT && top >= lo) { // (the same in every wave, and so is every bound below)
+			__shared__ double rows[(WCK - 1) * S];
+			double *my = rows + k0;
+			StructParN<NPL> fs;
+			fwd_roles<NPL>(sc, fs);
+			for (int q = top & ~(WCK - 1); q + WCK - 1 >= lo; q -= WCK) { // the block of the positions q .. q+7, within lo .. top
+				const int pb = max(lo, q), pe = min(top, q + WCK - 1);
+				double xf[NPL];
+				int p;
+				if (q >= lo) { ld<NPL>(X + ckpt_row(c.off, q) * S + k0, xf); p = q + 1; }
+				else if (lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, xf); p = lo; }
+				else { // X_1 = a0 e[o_1], as the forward sweep starts a segment
+					double ev[NPL];
+					ld<NPL>(par + WP_A0 * S + k0, xf);
+					emis<NPL>((int)o[0] & 3, e0, e1, ev);
+#pragma unroll
+					for (int i = 0; i < NPL; ++i) xf[i] *= ev[i];
+					st<NPL>(my, xf);
+					p = 2;
+				}
+				for (; p <= pe; ++p) {
+					const int sym = (int)o[p - 1] & 3;
+					if ((p & 3) == 0) mw_fstep<W, true, true>(fs, wm, sym, e0, e1, xf, io[p - 1], xc);
+					else mw_fstep<W, false, true>(fs, wm, sym, e0, e1, xf, 1.0, xc);
+					st<NPL>(my + ((p & (WCK - 1)) - 1) * S, xf);
+				}
+				for (p = pe; p >= pb; --p) {
+					double Xc[NPL];
+					if (p & (WCK - 1)) ld<NPL>(my + ((p & (WCK - 1)) - 1) * S, Xc); else ld<NPL>(X + ckpt_row(c.off, p) * S + k0, Xc);
+					const int sym = (int)o[p - 1] & 3;
+					if ((p & 3) == 0) mw_astep<W, true>(sc, wm, sym, e0, e1, Xc, x, io[p - 1], acc, accI, xc);
+					else mw_astep<W, false>(sc, wm, sym, e0, e1, Xc, x, 1.0, acc, accI, xc);
+				}
+			}
+			st<NPL>(bexit + (int64_t)b * S + k0, x); // bt_lo
+		}
+		if (!CKPT && top >= lo) { // (the same in every wave)
 			double Xc[NPL], Xn[NPL];
 			ld<NPL>(fo + (int64_t)(top - 1) * S, Xc);
 			for (int g = (top - 1) >> 2; g >= 0 && 4 * g + 4 >= lo; --g) {
@@ -317,7 +365,7 @@ __global__ __launch_bounds__(64 * W) void k_mw_acc(const double *__restrict__ pa
 // ------------------------------------------------------------------ verify, LL, reduce
 template <int W, bool BWD>
 __global__ __launch_bounds__(64 * W) void k_mw_verify(const Chunk *__restrict__ chunks, int n, double tol, const double *__restrict__ X,
-                                                        const double *__restrict__ mine, const double *__restrict__ bexit,
+                                                        const double *__restrict__ xhi, const double *__restrict__ mine, const double *__restrict__ bexit,
                                                         int *__restrict__ dirty, int *__restrict__ cnt, unsigned long long *__restrict__ warm)
 {
 	constexpr int NPL = MW_NPL, S = 64 * NPL * W;
@@ -332,7 +380,8 @@ __global__ __launch_bounds__(64 * W) void k_mw_verify(const Chunk *__restrict__ 
 	if (check) { // (the same in every wave)
 		double u[NPL], v[NPL];
 		ld<NPL>(mine + (int64_t)b * S + k0, u);
-		ld<NPL>(BWD ? bexit + (int64_t)(b + 1) * S + k0 : X + (c.off + c.lo - 2) * S + k0, v);
+		// (xhi: "wide_ckpt" -- the neighbour's last row X_{lo-1} is in the per-tile array, not in X)
+		ld<NPL>(BWD ? bexit + (int64_t)(b + 1) * S + k0 : (xhi ? xhi + (int64_t)(b - 1) * S + k0 : X + (c.off + c.lo - 2) * S + k0), v);
 		m = mw_mismatch<W>(u, v, xc);
 	}
 	if (tid == 0) {
@@ -358,7 +407,7 @@ __device__ __forceinline__ void mw_wave_comp(const double (&x)[MW_NPL], double &
 }
 
 template <int W>
-__global__ __launch_bounds__(64 * W) void k_mw_ll(const Chunk *__restrict__ chunks, const double *__restrict__ X, const double *__restrict__ inv,
+__global__ __launch_bounds__(64 * W) void k_mw_ll(const Chunk *__restrict__ chunks, const double *__restrict__ X, const double *__restrict__ xhi, const double *__restrict__ inv,
                                                     const double *__restrict__ entry, double *__restrict__ LLpart)
 {
 	constexpr int NPL = MW_NPL, S = 64 * NPL * W;
@@ -378,12 +427,12 @@ __global__ __launch_bounds__(64 * W) void k_mw_ll(const Chunk *__restrict__ chun
 	double u[NPL];
 	if (c.lo > 1) { // the tile was computed from entry = X_{lo-1} up to a factor: put the telescoping sum back in step
 		double v[NPL];
-		ld<NPL>(X + (c.off + c.lo - 2) * S + k0, u); ld<NPL>(entry + (int64_t)b * S + k0, v);
+		ld<NPL>(xhi ? xhi + (int64_t)(b - 1) * S + k0 : X + (c.off + c.lo - 2) * S + k0, u); ld<NPL>(entry + (int64_t)b * S + k0, v); // (xhi: "wide_ckpt", as k_mw_verify)
 		const double su = mw_vsum<W>(xc, u), sv = mw_vsum<W>(xc, v);
 		ll += log(su) - log(sv);
 	}
 	if (c.hi == c.L) {
-		ld<NPL>(X + (c.off + c.L - 1) * S + k0, u);
+		ld<NPL>(xhi ? xhi + (int64_t)b * S + k0 : X + (c.off + c.L - 1) * S + k0, u);
 		if (c.L == 1) { // a segment of one bin: LL is this logarithm alone -- add the sum up without a rounding (estep_wide_fast.hip k_wf_ll)
 			double h, l, t;
 			mw_wave_comp(u, h, l);
@@ -442,16 +491,31 @@ template <int W> static int launch_mw(const WideLaunch &w, int what, int n_list)
 	constexpr int S = 64 * MW_NPL * W, T = 64 * W;
 	const int nc = w.n_tiles;
 	hipStream_t st = w.stream;
+	const bool ck = w.ckpt == WCK;                      // "wide_ckpt": X at every 8th position, the tiles' last rows in w.xhi
+	const double *xhi = ck ? w.xhi : nullptr;
+	if (w.ckpt != 1 && !(ck && w.xhi)) return -1;
 	switch (what) {
-	case WF_FWD: hipLaunchKernelGGL((k_mw_fwd<W, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry); break;
-	case WF_FWD_REPAIR: hipLaunchKernelGGL((k_mw_fwd<W, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry); break;
+	case WF_FWD:
+		if (ck) hipLaunchKernelGGL((k_mw_fwd<W, false, true>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi);
+		else hipLaunchKernelGGL((k_mw_fwd<W, false, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi);
+		break;
+	case WF_FWD_REPAIR:
+		if (ck) hipLaunchKernelGGL((k_mw_fwd<W, true, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi);
+		else hipLaunchKernelGGL((k_mw_fwd<W, true, false>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi);
+		break;
 	case WF_BWARM: hipLaunchKernelGGL(k_mw_bwarm<W>, dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, w.bentry); break;
-	case WF_ACC: hipLaunchKernelGGL((k_mw_acc<W, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.bentry, w.bexit, w.part); break;
-	case WF_ACC_REPAIR: hipLaunchKernelGGL((k_mw_acc<W, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.bentry, w.bexit, w.part); break;
-	case WF_VERIFY_F: hipLaunchKernelGGL((k_mw_verify<W, false>), dim3(nc), dim3(T), 0, st, w.chunks, nc, w.tol, w.X, w.entry, w.bexit, w.dirty, w.cnt, w.warm); break;
-	case WF_VERIFY_B: hipLaunchKernelGGL((k_mw_verify<W, true>), dim3(nc), dim3(T), 0, st, w.chunks, nc, w.tol, w.X, w.bentry, w.bexit, w.dirty, w.cnt + 1, w.warm + 1); break;
+	case WF_ACC:
+		if (ck) hipLaunchKernelGGL((k_mw_acc<W, false, true>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		else hipLaunchKernelGGL((k_mw_acc<W, false, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		break;
+	case WF_ACC_REPAIR:
+		if (ck) hipLaunchKernelGGL((k_mw_acc<W, true, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		else hipLaunchKernelGGL((k_mw_acc<W, true, false>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		break;
+	case WF_VERIFY_F: hipLaunchKernelGGL((k_mw_verify<W, false>), dim3(nc), dim3(T), 0, st, w.chunks, nc, w.tol, w.X, xhi, w.entry, w.bexit, w.dirty, w.cnt, w.warm); break;
+	case WF_VERIFY_B: hipLaunchKernelGGL((k_mw_verify<W, true>), dim3(nc), dim3(T), 0, st, w.chunks, nc, w.tol, w.X, xhi, w.bentry, w.bexit, w.dirty, w.cnt + 1, w.warm + 1); break;
 	case WF_FINISH:
-		hipLaunchKernelGGL(k_mw_ll<W>, dim3(nc), dim3(T), 0, st, w.chunks, w.X, w.inv, w.entry, w.LLpart);
+		hipLaunchKernelGGL(k_mw_ll<W>, dim3(nc), dim3(T), 0, st, w.chunks, w.X, xhi, w.inv, w.entry, w.LLpart);
 		hipLaunchKernelGGL(k_mw_reduce1<S>, dim3(MW_ACC + 1, RED_ROWS), dim3(S), 0, st, w.part, nc, w.LLpart, w.stage);
 		hipLaunchKernelGGL(k_mw_reduce2<S>, dim3(MW_ACC + 1), dim3(S), 0, st, w.stage, w.tiny_total, w.n_states, w.out);
 		break;

@@ -233,6 +233,13 @@ struct psmc_hip_ctx {
 	double *d_wf_par = nullptr, *h_wf_par = nullptr;                     // e0 | e1 | a0 | P | R | qa | c | dd
 	double *d_wf_entry = nullptr, *d_wf_bentry = nullptr, *d_wf_bexit = nullptr, *d_wf_part = nullptr, *d_wf_ll = nullptr;
 	int *d_wf_dirty = nullptr, *d_wf_list = nullptr;
+	// "wide_ckpt" = 1: a wide fast E-step keeps X at every 8th position only (by absolute position: row (off >> 3) + (p >> 3) - 1 for
+	// p % 8 == 0) and every tile's last row in d_wf_xhi; its accumulate sweep recomputes the rest.  "wide_decode" = 1 wins: the
+	// decoding kernels read full rows.  wf_rows / wf_tab_iv: rows of d_wf_X and the interval it was sized for; wf_last_iv: the
+	// interval of the last wide fast E-step (0: none ran) -- fast_info, psmc_hip_wide_table_info, decode_source
+	int wide_ckpt = 0;
+	double *d_wf_xhi = nullptr; int wf_xhi_cap = 0; // [tiles][padded width]
+	int64_t wf_rows = 0; int wf_tab_iv = 0, wf_last_iv = 0;
 	// "wide_decode" = 1 (with "wide_fast"; beyond 256 states with "wide_fast" = 2): the decoding entry points of such a context read the
 	// tables of the wide path when the last single E-step was one of its own.  wd_serial: the table serial at that E-step -- an exact E-step or a batch moves tab_serial on,
 	// and the exact tables are the newer ones; wd_sel: the selection serial it ran with (psmc_hip_select moves sel_serial on)

@@ -13,6 +13,7 @@ struct WideLaunch {
 	hipStream_t stream;
 	int ns, n_states, n_tiles, chain; // ns: padded states, 192 or 256 (one wave per tile), 512, 768 or 1024 (waves = 2, 3, 4); chain: repairs walk on through glued runs
 	int waves;                        // waves per tile: 1, or ns / 256 on the multi-wave path
+	int ckpt;                         // positions per stored X row: 1 (X [bins][ns]), or 8 ("wide_ckpt": X [bins / 8][ns], the rows at p % 8 == 0 by absolute position, and xhi)
 	double tol, tiny_total;
 	const double *par;                // e0 | e1 | a0 | P | R | qa | c | dd, ns doubles each
 	const uint8_t *obs;
@@ -21,6 +22,7 @@ struct WideLaunch {
 	int *dirty, *cnt;                 // [n_tiles] verify flags; [2] failing tiles, forward | backward
 	unsigned long long *warm;         // [2] largest mismatch of the last verify, forward | backward (bits of a double)
 	double *X, *inv, *entry, *bentry, *bexit, *part, *LLpart, *stage, *out;
+	double *xhi;                      // ckpt == 8: [n_tiles][ns] every tile's last row X_hi (what its neighbour's verify / repair and the LL read)
 };
 
 int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip (waves > 1: hands on to the next)

@@ -96,6 +96,25 @@ __device__ __forceinline__ double mw_step(const StructParN<MW_NPL> &c, double (&
 	for (int i = 0; i < NPL; ++i) x[i] = __builtin_fma(c.wS[i], ES, __builtin_fma(c.wP[i], EP, t[i]));
 	return tot;
 }
+// one forward position over the tile (fstep of wide_prims.h with mw_step): x = X_{p-1} -> X_p, scaled at p % 4 == 0 (NORM) by
+// 1/d_p -- GIVEN: the factor the forward sweep stored, else computed from x.  Returns the factor.  One exchange either way.
+template <int W, bool NORM, bool GIVEN>
+__device__ __forceinline__ double mw_fstep(const StructParN<MW_NPL> &sc, const WaveScanMasks &wm, int sym, const double (&e0)[MW_NPL],
+                                           const double (&e1)[MW_NPL], double (&x)[MW_NPL], double given, Xchg<W> &xc)
+{
+	double ev[MW_NPL];
+	emis<MW_NPL>(sym, e0, e1, ev);
+	double iv = 1.0;
+	if (NORM && !GIVEN) iv = pow2_rcp(mw_step<W, true>(sc, x, wm, xc));
+	else { mw_step<W, false>(sc, x, wm, xc); if (NORM) iv = given; }
+	if (NORM) {
+#pragma unroll
+		for (int i = 0; i < MW_NPL; ++i) ev[i] *= iv;
+	}
+#pragma unroll
+	for (int i = 0; i < MW_NPL; ++i) x[i] *= ev[i];
+	return iv;
+}
 // one backward step at position p: x = bt_{p+1} -> bt_p (own scaling at p % 4 == 0: 1/sum(bt_{p+1}))
 template <int W, bool NORM>
 __device__ __forceinline__ void mw_bstep(const StructParN<MW_NPL> &sc, const WaveScanMasks &wm, int sym, const double (&e0)[MW_NPL],

@@ -87,6 +87,35 @@ template <int NPL> __device__ __forceinline__ void wstep(const StructParN<NPL> &
 		x[i] = __builtin_fma(c.wS[i], ES, __builtin_fma(c.wP[i], EP, t));
 	}
 }
+// one forward position p: x = X_{p-1} -> X_p = e[o_p] . (M x), scaled at p % 4 == 0 (NORM) by 1/d_p, a power of two (struct_prims.h
+// pow2_rcp) -- GIVEN: the factor the forward sweep stored (`given`), else computed from x.  Returns the factor.  The forward sweep
+// and the checkpointed accumulate sweep's recomputation (estep_wide_fast.hip) both step through here: the same arithmetic, so the same bits.
+template <int NPL, bool NORM, bool GIVEN>
+__device__ __forceinline__ double fstep(const StructParN<NPL> &c, const WaveScanMasks &wm, int sym, const double (&e0)[NPL],
+                                        const double (&e1)[NPL], double (&x)[NPL], double given)
+{
+	double ev[NPL];
+	emis<NPL>(sym, e0, e1, ev);
+	double iv = 1.0;
+	if (NORM) {
+		iv = GIVEN ? given : pow2_rcp(wave_total(lsum<NPL>(x)));
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) ev[i] *= iv;
+	}
+	wstep<NPL>(c, x, wm);
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
+	return iv;
+}
+// the checkpointed X table ("wide_ckpt"): one row per position p with p % 8 == 0.  Segments start at off % 64 == 0, so the rows of
+// all segments lie in one table by absolute position: the row of position p of the segment at `off`
+constexpr int WCK = 8;
+__device__ __forceinline__ int64_t ckpt_row(int64_t off, int p) { return (off >> 3) + (p >> 3) - 1; }
+// the forward roles of the five vectors, from a backward set (load_par: the same vectors in other roles)
+template <int NPL> __device__ __forceinline__ void fwd_roles(const StructParN<NPL> &b, StructParN<NPL> &f) {
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) { f.mS[i] = b.wP[i]; f.wS[i] = b.mP[i]; f.mP[i] = b.wS[i]; f.wP[i] = b.mS[i]; f.dd[i] = b.dd[i]; }
+}
 // max_k |u/|u| - v/|v|| / max_k v/|v| (u: the vector a tile built on, v: what its neighbour computed); NaN anywhere: +inf
 template <int NPL> __device__ __forceinline__ double wmismatch(const double (&u)[NPL], const double (&v)[NPL]) {
 	const double iu = 1.0 / wave_total(lsum<NPL>(u)), iv = 1.0 / wave_total(lsum<NPL>(v));

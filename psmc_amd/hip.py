@@ -32,7 +32,7 @@ EXPORTS = [
     "psmc_hip_group_selfcheck", "psmc_hip_fast_plan",
     "psmc_hip_group_create", "psmc_hip_group_destroy", "psmc_hip_group_last_error", "psmc_hip_group_set_option",
     "psmc_hip_group_load_segments", "psmc_hip_group_estep", "psmc_hip_group_estep_factored", "psmc_hip_group_info",
-    "psmc_hip_group_route", "psmc_hip_estep_factored_device",
+    "psmc_hip_group_route", "psmc_hip_estep_factored_device", "psmc_hip_wide_table_info",
 ]
 
 # every symbol include/psmc_hip_diag.h declares: libpsmc_hip_diag.so, the lab bench -- not part of the drop-in library
@@ -309,6 +309,14 @@ class HipEStep:
                     fwd_rounds=rp[0], bwd_rounds=rp[1], fwd_tiles=rp[2], bwd_tiles=rp[3], merged=rp[4], recounted=rp[5],
                     structured=bool(fi[0]), tile_len=fi[1], items_fwd=fi[2], items_bwd=fi[3], back_half=fi[4], ckpt=bool(fi[5]),
                     fused_launches=fi[6], merged_phase1=fi[7])
+
+    def wide_table_info(self):
+        """The wide fast path's X table (psmc_hip_wide_table_info): rows allocated, padded width, the last E-step's checkpoint
+        interval (1, 8 with "wide_ckpt", 0: none ran), bytes."""
+        o = (C.c_int64 * 4)()
+        self.lib.psmc_hip_wide_table_info.argtypes = [C.c_void_p, _i64p]
+        self._chk(self.lib.psmc_hip_wide_table_info(self.h, o), "wide_table_info")
+        return dict(rows=int(o[0]), width=int(o[1]), interval=int(o[2]), bytes=int(o[3]))
 
     def fast_plan(self):
         """The plan of the next fast E-step: tiles, tile length, mean / longest warm-ups (bins), glued tiles."""

@@ -24,10 +24,14 @@
       a process of its own so that a job can give each leg its time limit -- the same batch with "wide_batch" = 0: the exact
       launch groups, what such a context ran before the option existed
 
+  --ckpt sets "wide_ckpt" = 1 on the wide contexts of (a) and (e): X at every 8th bin only, the rest recomputed in the accumulate
+  sweep.  Beside every time, (a) and (e) print what psmc_hip_wide_table_info reports: the bytes of X the context holds.
+
 Library calls are synchronous.  Writes one JSON object to stdout (progress on stderr).
 
     python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
     python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
+    python scripts/wide_fast_timing.py --stress --states 200,300,1024 --steps 4 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --decode --stress --states 300,1024
     python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
 """
@@ -75,10 +79,20 @@ def params_seq(n, steps, seed=11):
     return out
 
 
-def library_part(hip, segs, n, steps, exact_steps):
+def table_info(es):
+    """psmc_hip_wide_table_info; None with a library from before the entry point existed (PSMC_HIP_LIB: A/B against an older build)"""
+    try:
+        return es.wide_table_info()
+    except AttributeError:
+        return None
+
+
+def library_part(hip, segs, n, steps, exact_steps, ckpt=False):
     ps = params_seq(n, steps)
     r = {}
     es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1)
+    if ckpt:
+        es.set_option("wide_ckpt", 1)
     es.load_segments(segs)
     ms, rounds = [], []
     for a, e, a0 in ps:
@@ -86,6 +100,8 @@ def library_part(hip, segs, n, steps, exact_steps):
         d = es.fast_diag()
         rounds.append(dict(fwd_rounds=d["fwd_rounds"], bwd_rounds=d["bwd_rounds"], fwd_tiles=d["fwd_tiles"], bwd_tiles=d["bwd_tiles"]))
     d = es.fast_diag()
+    ti = table_info(es)
+    r.update(wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None, fast_later_ms_median=float(np.median(ms[1:])))
     r.update(tiles=d["n_chunks"], tile_len=d["tile_len"], warmup=d["warmup"], fast_ms=ms, fast_first_ms=ms[0],
              fast_later_ms_mean=float(np.mean(ms[1:])), fast_later_ms_min=float(np.min(ms[1:])), repairs=rounds)
     es.close()
@@ -105,7 +121,7 @@ def library_part(hip, segs, n, steps, exact_steps):
     return r
 
 
-def batch_part(hip, segs, n, n_rep, leg):
+def batch_part(hip, segs, n, n_rep, leg, ckpt=False):
     """(e): the replicates are the same for both legs (seeded)"""
     ps = params_seq(n, n_rep)
     rng = np.random.default_rng(97 + n)
@@ -113,6 +129,8 @@ def batch_part(hip, segs, n, n_rep, leg):
     r = {"replicates": n_rep, "selections": sel,
          "unique_bins": [int(sum(len(segs[i]) for i in set(x))) for x in sel], "all_bins": int(sum(len(s) for s in segs))}
     es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_batch=1 if leg == "wide" else 0)
+    if ckpt:
+        es.set_option("wide_ckpt", 1)
     es.load_segments(segs)
     if leg == "wide":
         es.estep_batch(ps[:1], sel[:1], want="sums")   # warm-up: the X table and the plan's buffers
@@ -121,6 +139,8 @@ def batch_part(hip, segs, n, n_rep, leg):
         es.estep_batch(ps, sel, want="sums", on_done=lambda reps, out: stamps.append(time.perf_counter()))
         wall = time.perf_counter() - t
         d = es.fast_diag()
+        ti = table_info(es)
+        r.update(wide_ckpt=int(ckpt), x_table_bytes=ti["bytes"] if ti else None)
         r.update(wide_batch_s=wall, wide_batch_s_per_replicate=wall / n_rep,
                  wide_replicate_s=[float(x) for x in np.diff([t] + stamps)],
                  last_replicate=dict(tiles=d["n_chunks"], tile_len=d["tile_len"], fwd_rounds=d["fwd_rounds"], bwd_rounds=d["bwd_rounds"],
@@ -232,6 +252,7 @@ def main():
     ap.add_argument("--full-post", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="(e): the bootstrap batch of this many replicates on the wide fast path instead of (a), (b)")
     ap.add_argument("--batch-leg", choices=["wide", "exact"], default="wide", help="with --batch: \"wide_batch\" = 1 and the single E-step, or the exact launch groups")
+    ap.add_argument("--ckpt", action="store_true", help="\"wide_ckpt\" = 1 on the wide contexts of (a) and (e): X at every 8th bin only; the table's bytes are printed beside each time")
     ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
     args = ap.parse_args()
     from psmc_amd import hip, sim
@@ -247,11 +268,11 @@ def main():
         out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
     for n in [int(x) for x in args.states.split(",") if x]:
         if args.batch > 0:
-            out["n%d" % n] = batch_part(hip, segs, n, args.batch, args.batch_leg)
+            out["n%d" % n] = batch_part(hip, segs, n, args.batch, args.batch_leg, args.ckpt)
         elif args.decode:
             out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0)
         else:
-            out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps)
+            out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps, args.ckpt)
     if args.cli:
         out["cli"] = cli_part(segs)
     print(json.dumps(out))
