@@ -119,10 +119,23 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           psmc_hip_fast_info out[5] is 1 after a checkpointed E-step).  "wide_decode" = 1 wins: the decoding kernels
  *                           read full rows, so while it is set a wide fast E-step keeps the full table whatever "wide_ckpt" says
  *                           (PSMC_HIP_ENOMEM as under "wide_fast" when that does not fit) -- set "wide_decode" before the one E-step
- *                           that is decoded, and the EM rounds before it run checkpointed.  Decoding from checkpoints is out of
- *                           scope: psmc_hip_decode, _posterior, _post_counts and _scales after a checkpointed E-step ("wide_decode"
- *                           set afterwards, no new E-step) answer PSMC_HIP_ESTATE.  Exact mode, up to 128 states (their own "ckpt"),
- *                           "wide_fast" = 0: accepted, no effect.  Other values: PSMC_HIP_EINVAL
+ *                           that is decoded, and the EM rounds before it run checkpointed -- or set "wide_decode_ckpt" = 1 as well,
+ *                           and that E-step keeps checkpoints too.  Without "wide_decode_ckpt", psmc_hip_decode, _posterior,
+ *                           _post_counts and _scales after a checkpointed E-step ("wide_decode" set afterwards, no new E-step) answer
+ *                           PSMC_HIP_ESTATE.  Exact mode, up to 128 states (their own "ckpt"), "wide_fast" = 0: accepted, no effect.
+ *                           Other values: PSMC_HIP_EINVAL
+ *  "wide_decode_ckpt" 0     1: decoding from checkpoints.  A wide fast E-step with "wide_ckpt" = 1 keeps checkpoints even while
+ *                           "wide_decode" = 1 (interval 8 in psmc_hip_wide_table_info, psmc_hip_fast_info out[5] = 1: the E-step's
+ *                           table no longer depends on "wide_decode"), and psmc_hip_decode, _posterior, _post_counts and _scales after
+ *                           such an E-step read its checkpoints, the tiles' last rows, 1/d and the tile boundaries: the CKPT kernels of
+ *                           estep_wide_post.hip / estep_wide_post_mw.hip recompute the seven rows between two checkpoints with the
+ *                           forward sweep's own arithmetic, block by block as the E-step's accumulate sweep does, and return the bits
+ *                           of decoding from the full table.  "wide_decode" may be switched on after that E-step: nothing is re-run.
+ *                           The option is read by every decoding call too: back at 0, a call after a checkpointed E-step answers
+ *                           PSMC_HIP_ESTATE as before.  A decoding call allocates nothing proportional to bins x S (posterior rows it
+ *                           was asked for aside); psmc_hip_post_counts recomputes the rows once per four count columns.  Every other
+ *                           state rule of "Decoding on a FAST context" is unchanged.  Without "wide_ckpt", in exact mode, up to 128
+ *                           states or with "wide_fast" = 0: accepted, no effect.  Other values: PSMC_HIP_EINVAL
  *  "wide_batch"    0        1: psmc_hip_estep_batch[_cb] of a fast-mode context of 129..1024 states whose size "wide_fast" covers, asked for
  *                           sums and not for A, runs every replicate on the wide fast path (see psmc_hip_estep_batch, "wide fast batch").
  *                           0, and every other context or call: the batch as without the option.  Other values: PSMC_HIP_EINVAL
@@ -424,6 +437,12 @@ int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
  *   - PSMC_HIP_ESTATE before any single E-step, after a batch, after a wide fast E-step that returned an error (ECONVERGE: its
  *     boundaries are not converged), after psmc_hip_select / a reload since that E-step, or for a segment that was not in its
  *     selection.
+ *   - a wide fast factored E-step that kept checkpoints only ("wide_ckpt" = 1 while "wide_decode" was 0, or with
+ *     "wide_decode_ckpt" = 1): with "wide_decode_ckpt" = 1 at the decoding call the same sweep, every block of eight positions
+ *     recomputed forward from its checkpoint X_{8m} (in a tile's lowest block from the tile's start vector, or from a0 e(o_1)) with
+ *     the stored 1/d -- the formulas, tolerances and state rules above, and the bits of decoding from the full table; the scales
+ *     from one forward pass per tile.  With "wide_decode_ckpt" = 0: PSMC_HIP_ESTATE (the message names the checkpoints) until an
+ *     E-step has kept the full table;
  * With "wide_decode" = 0 -- and beyond 256 states with "wide_fast" = 1 -- such a context decodes from the exact tables whatever
  * ran last (ESTATE when there are none).  psmc_hip_get_tables always reads the exact tables.
  * What it is worth beyond 256 states, on the 2.2 M-bin stress fixture (scripts/wide_fast_timing.py --decode --stress, one E-step plus

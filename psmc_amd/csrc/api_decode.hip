@@ -3,7 +3,9 @@
 //   DEC_EXACT  f, b and s of the exact kernels (estep_exact.hip, estep_wide.hip beyond 128 states)
 //   DEC_FAST   X and bt of a fast E-step with the unfused back half, up to 128 states (estep_post_fast.hip)
 //   DEC_WIDE   X, 1/d, entry and bentry of a wide fast E-step with "wide_decode": 129..256 states (estep_wide_post.hip), and
-//              257..1024 states with "wide_fast" = 2 (estep_wide_post_mw.hip; the tables are 512, 768 or 1024 states wide)
+//              257..1024 states with "wide_fast" = 2 (estep_wide_post_mw.hip; the tables are 512, 768 or 1024 states wide).  After a
+//              checkpointed E-step ("wide_ckpt") with "wide_decode_ckpt" = 1: its checkpoints and the tiles' last rows instead of X
+//              (the CKPT kernels of the same files; nothing of the table's size is allocated)
 // Every entry point is written once: argument check, decode_source, device scratch of its own (freed before it returns), uploads, a
 // switch on the source that holds nothing but the launch, downloads, one synchronise, one error mapping.
 #include "psmc_hip_ctx.h"
@@ -24,8 +26,10 @@ static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_t
 			snprintf(msg, sizeof msg, "%s: the last wide fast E-step returned an error (no converged tile boundaries to decode from)", who);
 			return fail(c, PSMC_HIP_ESTATE, msg);
 		}
-		if (c->wf_last_iv != 1) { // ("wide_ckpt" without "wide_decode" at that E-step: the decoding kernels read full X rows)
-			snprintf(msg, sizeof msg, "%s: the last wide E-step kept checkpoints only (\"wide_ckpt\": X at every 8th bin); run an E-step with \"wide_decode\" = 1 first", who);
+		// a checkpointed E-step ("wide_ckpt"): the CKPT decoding kernels read its checkpoints when "wide_decode_ckpt" is on NOW;
+		// without it the decoding kernels read full X rows, which that E-step did not keep
+		if (c->wf_last_iv != 1 && !(c->wf_last_iv == 8 && c->wide_decode_ckpt)) {
+			snprintf(msg, sizeof msg, "%s: the last wide E-step kept checkpoints only (\"wide_ckpt\": X at every 8th bin); run an E-step with \"wide_decode\" = 1 first, or set \"wide_decode_ckpt\" = 1", who);
 			return fail(c, PSMC_HIP_ESTATE, msg);
 		}
 		if (c->wd_sel != c->sel_serial) {
@@ -90,6 +94,7 @@ static void wide_post_common(const psmc_hip_ctx *c, WidePost &w, int what, int t
 	w.stream = c->stream; w.what = what; w.ns = wf_width(c); w.waves = wf_waves(c); w.n_states = c->n; w.t0 = t0; w.n_tiles = nt;
 	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks;
 	w.X = c->d_wf_X; w.inv = c->d_wf_inv; w.entry = c->d_wf_entry; w.bentry = c->d_wf_bentry;
+	w.ckpt = c->wf_last_iv; w.xhi = c->wf_last_iv == 8 ? c->d_wf_xhi : nullptr; // (8: decode_source let it through, "wide_decode_ckpt")
 }
 
 extern "C" int psmc_hip_decode(psmc_hip_ctx *c, int seg, int32_t *path, double *maxp)

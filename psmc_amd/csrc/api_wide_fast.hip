@@ -6,7 +6,9 @@
 // psmc_hip_estep, the batch without "wide_batch" (with it: api_batch.hip batch_wide calls estep_factored_wide once per replicate),
 // psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
 // "wide_ckpt" = 1: X at every 8th position only (S bytes per bin) plus every tile's last row, the accumulate sweep recomputes the rest
-// (estep_wide_fast.hip); "wide_decode" = 1 wins, because the decoding kernels read full rows.  The table is sized anew when the interval
+// (estep_wide_fast.hip); "wide_decode" = 1 wins, because the full-table decoding kernels read every row -- unless "wide_decode_ckpt" = 1:
+// then the table does not depend on "wide_decode", and decoding recomputes the rows between the checkpoints as the accumulate sweep
+// does (the CKPT kernels of estep_wide_post.hip / estep_wide_post_mw.hip).  The table is sized anew when the interval
 // changes between two E-steps, and what ran is recorded for fast_info, psmc_hip_wide_table_info and decode_source.
 //
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
@@ -140,8 +142,9 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	if (!c->d_wf_par && (rc = dev_alloc(c, &c->d_wf_par, (size_t)WF_PAR * S))) return rc;
 	if ((c->plan_dirty || c->wf_chunks.empty()) && (rc = plan_wide(c))) return rc;
 	const int64_t bins = c->total + 128;
-	// "wide_ckpt": one X row per 8 positions -- unless "wide_decode" is on: the decoding kernels read full rows, so that E-step keeps them
-	const int iv = c->wide_ckpt && !c->wide_decode ? 8 : 1;
+	// "wide_ckpt": one X row per 8 positions -- unless "wide_decode" is on without "wide_decode_ckpt": the full-table decoding kernels
+	// read every row, so that E-step keeps them
+	const int iv = c->wide_ckpt && (!c->wide_decode || c->wide_decode_ckpt) ? 8 : 1;
 	const int nt = (int)c->wf_chunks.size();
 	c->wf_last_iv = 0;
 	if (c->wf_bins < bins || c->wf_tab_iv != iv) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins; 8 KB per bin at S = 1024), with "wide_ckpt" S bytes per bin; sized anew when the interval changes, whether it grows or shrinks

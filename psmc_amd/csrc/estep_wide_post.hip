@@ -1,4 +1,4 @@
-// estep_wide_post.hip -- decoding on the wide fast path (129..256 states, options "wide_fast" + "wide_decode"; api_wide_fast.hip
+// estep_wide_post.hip -- decoding on the wide fast path (129..256 states, options "wide_fast" + "wide_decode"; api_decode.hip
 // drives it): psmc_hip_decode / _posterior / _post_counts / _scales from what the last wide fast E-step left, without a backward table.
 //
 // The E-step keeps the lag-normalised forward table X (and 1/d_p at p % 4 == 0), every tile's forward start vector `entry` and its
@@ -14,6 +14,29 @@
 //                posterior-weighted counts, CB count columns per sweep
 //   k_wp_cnt_add the tiles' partials added in tile order (deterministic); also at the widths 512 / 768 / 1024 of estep_wide_post_mw.hip
 //   k_wp_scales  s_p = sum X_p / sum X_{p-1} / inv_p from X alone (X_{lo-1}: the tile's own `entry`), s_1 = sum_k a0_k e_k(o_1)
+//
+// "wide_decode_ckpt" (compile-time variants CKPT of k_wp_dec, and k_wp_scales_ck; the full-table kernels keep their code): after a
+// "wide_ckpt" E-step X holds the rows at p % 8 == 0 only (wide_prims.h ckpt_row) and xhi[b] every tile's last row.  k_wp_dec CKPT
+// sweeps the tile in blocks of eight positions, the top block first, recomputing the block's rows forward into LDS with fstep --
+// the forward sweep's own step and its stored scale factors, as k_wf_acc CKPT of estep_wide_fast.hip -- and then runs the same
+// backward step and emit over them; k_wp_scales_ck makes one forward pass per tile.  The same bits as from the full table.
+//
+// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; scratch is 0 everywhere; LDS in bytes per wave):
+//   kernel                            S=192: VGPRs  LDS     S=256: VGPRs  LDS
+//   k_wp_dec  path                            98    0              122    0
+//   k_wp_dec  posterior                       96    0              122    0
+//   k_wp_dec  recombination                  106    0              134    0
+//   k_wp_dec  posterior + recomb.            106    0              136    0
+//   k_wp_dec  counts                         118    0              152    0
+//   k_wp_dec  path, CKPT                     102    10752          126    14336
+//   k_wp_dec  posterior, CKPT                 92    10752          116    14336
+//   k_wp_dec  recombination, CKPT            104    10752          132    14336
+//   k_wp_dec  posterior + recomb., CKPT      104    10752          132    14336
+//   k_wp_dec  counts, CKPT                   116    10752          148    14336
+//   k_wp_scales / k_wp_scales_ck         16 / 80    0         16 / 102    0
+//   k_wp_cnt_add                               8    0 (every width)
+// With CKPT the staged rows bound a compute unit at 15 waves (192 states) or 11 (256) of its 160 KB of LDS, where the registers alone
+// allow 16 and 12 to 16, as without CKPT.
 #include <hip/hip_runtime.h>
 #include "wide_fast.h"
 #include "wide_prims.h"
@@ -63,12 +86,20 @@ __device__ __forceinline__ void emit(int p, int lane, int n, const double (&g)[N
 
 // Tile t0 + blockIdx.x of the plan (the tiles of one segment are consecutive).  Output pointers are the SEGMENT's (position 1 first).
 // CNT: part[(blockIdx.x * n_cnt + j) * S + k] for the columns j0 .. j0 + CB - 1 that exist.
-template <int NPL, bool POST, bool REC, bool PATH, bool CNT>
+// CKPT ("wide_decode_ckpt" after a "wide_ckpt" E-step): X holds the rows at p % 8 == 0 only.  As k_wf_acc CKPT (estep_wide_fast.hip) the
+// tile is swept in blocks of the positions 8m .. 8m+7, the top block first: the block's rows are recomputed forward with fstep and
+// the stored scale factors -- the forward sweep's own bits -- from the checkpoint X_{8m}, or in the tile's lowest block from
+// entry[b] or from X_1 = a0 e[o_1], into LDS (7 S doubles; every lane reads back what it wrote itself, so no barrier); then the
+// backward step and emit of the full-table sweep run over them, highest position first, X_{8m} read from the table.  X_L: xhi[b].
+// With CNT every sweep of CB columns recomputes the rows again.
+template <int NPL, bool POST, bool REC, bool PATH, bool CNT, bool CKPT>
 __global__ __launch_bounds__(64) void k_wp_dec(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                  const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
-                                                 const double *__restrict__ bentry, int n, double *__restrict__ post,
-                                                 double *__restrict__ recomb, int32_t *__restrict__ path, double *__restrict__ maxp,
-                                                 const int32_t *__restrict__ cnt1, int n_cnt, int j0, int min_l, double *__restrict__ part)
+                                                 const double *__restrict__ inv, const double *__restrict__ entry,
+                                                 const double *__restrict__ xhi, const double *__restrict__ bentry, int n,
+                                                 double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
+                                                 double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0,
+                                                 int min_l, double *__restrict__ part)
 {
 	constexpr int S = 64 * NPL;
 	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
@@ -89,10 +120,64 @@ __global__ __launch_bounds__(64) void k_wp_dec(const double *__restrict__ par, c
 	const double *fo = X + c.off * S + k0;
 	if (c.hi == c.L) { // position L: beta_L = 1
 		double g[NPL];
-		ld<NPL>(fo + (int64_t)(c.L - 1) * S, g);
+		if (CKPT) ld<NPL>(xhi + (int64_t)b * S + k0, g); else ld<NPL>(fo + (int64_t)(c.L - 1) * S, g);
 		emit<NPL, POST, REC, PATH, CNT>(c.L, lane, n, g, wave_total(lsum<NPL>(g)), 0.0, true, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc);
 	}
-	if (top >= lo) {
+	if (CKPT && top >= lo) {
+		__shared__ double rows[(WCK - 1) * S];
+		double *my = rows + k0;
+		const double *io = inv + c.off;
+		double x[NPL];
+		ld<NPL>(bentry + (int64_t)b * S + k0, x);
+		for (int q = top & ~(WCK - 1); q + WCK - 1 >= lo; q -= WCK) { // the block of the positions q .. q+7, within lo .. top
+			const int pb = max(lo, q), pe = min(top, q + WCK - 1);
+			{
+				StructParN<NPL> fs;
+				fwd_roles<NPL>(sc, fs);
+				double xf[NPL];
+				int p;
+				if (q >= lo) { ld<NPL>(X + ckpt_row(c.off, q) * S + k0, xf); p = q + 1; }
+				else if (lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, xf); p = lo; }
+				else { // X_1 = a0 e[o_1], as the forward sweep starts a segment
+					double ev[NPL];
+					ld<NPL>(par + WP_A0 * S + k0, xf);
+					emis<NPL>((int)o[0] & 3, e0, e1, ev);
+#pragma unroll
+					for (int i = 0; i < NPL; ++i) xf[i] *= ev[i];
+					st<NPL>(my, xf);
+					p = 2;
+				}
+				for (; p <= pe; ++p) {
+					const int sym = (int)o[p - 1] & 3;
+					if ((p & 3) == 0) fstep<NPL, true, true>(fs, wm, sym, e0, e1, xf, io[p - 1]);
+					else fstep<NPL, false, true>(fs, wm, sym, e0, e1, xf, 1.0);
+					st<NPL>(my + ((p & (WCK - 1)) - 1) * S, xf);
+				}
+			}
+			for (int p = pe; p >= pb; --p) {
+				double Xc[NPL], ev[NPL], y[NPL], g[NPL];
+				if (p & (WCK - 1)) ld<NPL>(my + ((p & (WCK - 1)) - 1) * S, Xc); else ld<NPL>(X + ckpt_row(c.off, p) * S + k0, Xc);
+				emis<NPL>((int)o[p - 1] & 3, e0, e1, ev);
+				if ((p & 3) == 0) { // the backward sweep's own scaling, as bstep
+					const double sb = rcp_newton(wave_total(lsum<NPL>(x)));
+#pragma unroll
+					for (int i = 0; i < NPL; ++i) ev[i] *= sb;
+				}
+				double r = 0.0;
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) {
+					y[i] = x[i];
+					if (REC) r = __builtin_fma(Xc[i] * akk[i], x[i], r);
+				}
+				wstep<NPL>(sc, y, wm); // (a bt_{p+1})
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) { g[i] = Xc[i] * y[i]; x[i] = y[i] * ev[i]; }
+				if (REC) r = wave_total(r);
+				emit<NPL, POST, REC, PATH, CNT>(p, lane, n, g, wave_total(lsum<NPL>(g)), r, false, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc);
+			}
+		}
+	}
+	if (!CKPT && top >= lo) {
 		double x[NPL], Xc[NPL], Xn[NPL];
 		ld<NPL>(bentry + (int64_t)b * S + k0, x);
 		ld<NPL>(fo + (int64_t)(top - 1) * S, Xc);
@@ -164,13 +249,55 @@ __global__ __launch_bounds__(64) void k_wp_scales(const Chunk *__restrict__ chun
 	}
 }
 
-template <int NPL> static int launch_post(const WidePost &w)
+// CKPT: the scales without the table -- one forward pass over the tile from entry[b] (or X_1 = a0 e[o_1], stored as it stands) through
+// fstep with the stored factors: the forward sweep's rows, so the row sums (one wave_total each) and the quotients of k_wp_scales
+template <int NPL>
+__global__ __launch_bounds__(64) void k_wp_scales_ck(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                       const Chunk *__restrict__ chunks, int t0, const double *__restrict__ inv,
+                                                       const double *__restrict__ entry, double *__restrict__ s)
+{
+	constexpr int S = 64 * NPL;
+	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
+	const WaveScanMasks wm = wave_scan_masks(lane);
+	const Chunk c = chunks[b];
+	StructParN<NPL> fs;
+	load_par<NPL>(par, k0, true, fs);
+	double e0[NPL], e1[NPL], x[NPL], prev;
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+	const uint8_t *o = obs + c.off;
+	const double *io = inv + c.off;
+	int p = c.lo;
+	if (c.lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, x); prev = wave_total(lsum<NPL>(x)); }
+	else {
+		double ev[NPL];
+		ld<NPL>(par + WP_A0 * S + k0, x);
+		emis<NPL>((int)o[0] & 3, e0, e1, ev);
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
+		prev = wave_total(lsum<NPL>(x));
+		if (lane == 0) s[0] = prev;
+		p = 2;
+	}
+	for (; p <= c.hi; ++p) {
+		const int sym = (int)o[p - 1] & 3;
+		const bool norm = (p & (NORM_EVERY - 1)) == 0;
+		if (norm) fstep<NPL, true, true>(fs, wm, sym, e0, e1, x, io[p - 1]);
+		else fstep<NPL, false, true>(fs, wm, sym, e0, e1, x, 1.0);
+		const double cur = wave_total(lsum<NPL>(x));
+		double v = cur / prev;
+		if (norm) v /= io[p - 1];
+		if (lane == 0) s[p - 1] = v;
+		prev = cur;
+	}
+}
+
+template <int NPL, bool CKPT> static int launch_post(const WidePost &w)
 {
 	const dim3 grid(w.n_tiles), blk(64);
 	hipStream_t st = w.stream;
 #define WP_DEC(POST, REC, PATH, CNT, j0) \
-	hipLaunchKernelGGL((k_wp_dec<NPL, POST, REC, PATH, CNT>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.bentry, w.n_states, \
-	                   w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part)
+	hipLaunchKernelGGL((k_wp_dec<NPL, POST, REC, PATH, CNT, CKPT>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.inv, w.entry, w.xhi, \
+	                   w.bentry, w.n_states, w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part)
 	switch (w.what) {
 	case WP_PATH: WP_DEC(false, false, true, false, 0); break;
 	case WP_POST: WP_DEC(true, false, false, false, 0); break;
@@ -180,7 +307,10 @@ template <int NPL> static int launch_post(const WidePost &w)
 		for (int j0 = 0; j0 < w.n_cnt; j0 += CB) WP_DEC(false, false, false, true, j0);
 		if (hipGetLastError() != hipSuccess) return -1;
 		return launch_wide_post_cnt_add(w);
-	case WP_SCALES: hipLaunchKernelGGL(k_wp_scales<NPL>, grid, blk, 0, st, w.chunks, w.t0, w.X, w.inv, w.entry, w.s); break;
+	case WP_SCALES:
+		if (CKPT) hipLaunchKernelGGL(k_wp_scales_ck<NPL>, grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.inv, w.entry, w.s);
+		else hipLaunchKernelGGL(k_wp_scales<NPL>, grid, blk, 0, st, w.chunks, w.t0, w.X, w.inv, w.entry, w.s);
+		break;
 	default: return -1;
 	}
 #undef WP_DEC
@@ -209,9 +339,11 @@ int launch_wide_post_cnt_add(const WidePost &w)
 
 int launch_wide_post(const WidePost &w)
 {
+	const bool ck = w.ckpt == wide::WCK; // the E-step kept checkpoints ("wide_ckpt"): X at every 8th position, the tiles' last rows in w.xhi
+	if (w.ckpt != 1 && !(ck && w.xhi)) return -1;
 	if (w.waves > 1) return launch_wide_post_mw(w); // 257..1024 states: estep_wide_post_mw.hip
-	if (w.ns == 192) return wide::launch_post<3>(w);
-	if (w.ns == 256) return wide::launch_post<4>(w);
+	if (w.ns == 192) return ck ? wide::launch_post<3, true>(w) : wide::launch_post<3, false>(w);
+	if (w.ns == 256) return ck ? wide::launch_post<4, true>(w) : wide::launch_post<4, false>(w);
 	return -1;
 }
 

@@ -244,6 +244,10 @@ struct psmc_hip_ctx {
 	// tables of the wide path when the last single E-step was one of its own.  wd_serial: the table serial at that E-step -- an exact E-step or a batch moves tab_serial on,
 	// and the exact tables are the newer ones; wd_sel: the selection serial it ran with (psmc_hip_select moves sel_serial on)
 	int wide_decode = 0;
+	// "wide_decode_ckpt" = 1: a "wide_ckpt" E-step keeps checkpoints whatever "wide_decode" says, and the decoding entry points read
+	// them (wf_last_iv == 8: the CKPT kernels of estep_wide_post.hip / estep_wide_post_mw.hip recompute the rows between them).  Read
+	// by the E-step (the interval) and again by decode_source at every decoding call
+	int wide_decode_ckpt = 0;
 	int wd_kind = 0; unsigned long long wd_serial = 0, wd_sel = 0, sel_serial = 0;
 	// "wide_batch" = 1: psmc_hip_estep_batch[_cb] of such a context, asked for sums only, runs every replicate's E-step on the wide fast
 	// path -- on this context itself, one selection after the other: the path learns nothing, so no child contexts (api_batch.hip batch_wide)

@@ -35,6 +35,8 @@ struct WidePost {
 	hipStream_t stream;
 	int what, ns, n_states, t0, n_tiles; // ns: the padded width of the tables, as WideLaunch
 	int waves;                        // waves per tile of the E-step that wrote them: 1, or ns / 256
+	int ckpt;                         // as WideLaunch: 1 (X holds every row), or 8 (the E-step kept checkpoints; "wide_decode_ckpt": the CKPT kernels recompute the rows between them)
+	const double *xhi;                // ckpt == 8: [tiles of the plan][ns] every tile's last row X_hi (X_L of a segment's last tile)
 	const double *par;                // as WideLaunch
 	const uint8_t *obs;
 	const Chunk *chunks;

@@ -114,6 +114,10 @@ static int hb_estep(void *self, const double *a, const double *e, const double *
 		if (rc == PSMC_HIP_ENOTSUP) { /* "structured" = 0, a matrix without the PSMC form (-C): nothing of the wide path to decode */
 			fprintf(stderr, "psmc: the wide fast E-step cannot run (%s); repeating the decoding E-step with the exact kernels\n", hb_error(h));
 			rc = exact_once(h, a, e, a0, A, E, LL, 1);
+		} else if (rc == 0) { /* what that E-step kept ("wide_ckpt" + "wide_decode_ckpt" through PSMC_HIP_OPTIONS: checkpoints) */
+			psmc_hip_ctx *c = h->ctx; int l; int64_t ti[4] = {0, 0, 0, 0};
+			if ((!h->grp || psmc_hip_group_route(h->grp, 0, &c, &l) == 0) && psmc_hip_wide_table_info(c, ti) == 0 && ti[2] == 8)
+				fprintf(stderr, "psmc: the decoding reads the wide fast tables (checkpoints: X at every 8th bin)\n");
 		}
 	} else rc = h->grp ? psmc_hip_group_estep(h->grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->ctx, a, e, a0, A, E, 0, LL, h->chk);
 	if (rc == PSMC_HIP_ECONVERGE && h->mode == PSMC_HIP_MODE_FAST) rc = exact_once(h, a, e, a0, A, E, LL, 0);

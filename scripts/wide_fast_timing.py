@@ -26,6 +26,8 @@
 
   --ckpt sets "wide_ckpt" = 1 on the wide contexts of (a) and (e): X at every 8th bin only, the rest recomputed in the accumulate
   sweep.  Beside every time, (a) and (e) print what psmc_hip_wide_table_info reports: the bytes of X the context holds.
+  With --decode it sets "wide_ckpt" = 1 and "wide_decode_ckpt" = 1 on the wide context of (d): the decoding E-step keeps checkpoints
+  and every decoding call recomputes the rows between them; (d) prints the X table's bytes beside the decode times either way.
 
 Library calls are synchronous.  Writes one JSON object to stdout (progress on stderr).
 
@@ -33,6 +35,7 @@ Library calls are synchronous.  Writes one JSON object to stdout (progress on st
     python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
     python scripts/wide_fast_timing.py --stress --states 200,300,1024 --steps 4 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --decode --stress --states 300,1024
+    python scripts/wide_fast_timing.py --decode --stress --states 200,300,1024 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
 """
 import argparse
@@ -185,16 +188,21 @@ def decode_calls(es, segs, n, full_post):
     return out
 
 
-def decode_part(hip, segs, n, repeats, full_post, exact):
+def decode_part(hip, segs, n, repeats, full_post, exact, ckpt=False):
     a, e, a0 = params_seq(n, 1)[0]
     r = {"longest_segment_bins": int(max(len(s) for s in segs))}
     es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_decode=1)
+    if ckpt:
+        es.set_option("wide_ckpt", 1)
+        es.set_option("wide_decode_ckpt", 1)
     es.load_segments(segs)
     es.estep_factored(a, e[:2], a0)
     ms = []
     for _ in range(3):
         t = time.perf_counter(); es.estep_factored(a, e[:2], a0); ms.append((time.perf_counter() - t) * 1e3)
     r["wide_estep_ms"] = _spread(ms)
+    ti = table_info(es)
+    r.update(wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None)
     decode_calls(es, segs, n, full_post)   # warm-up
     passes = [decode_calls(es, segs, n, full_post) for _ in range(repeats)]
     r["wide_decode_ms"] = {k: _spread([p[k] for p in passes]) for k in passes[0]}
@@ -252,7 +260,7 @@ def main():
     ap.add_argument("--full-post", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="(e): the bootstrap batch of this many replicates on the wide fast path instead of (a), (b)")
     ap.add_argument("--batch-leg", choices=["wide", "exact"], default="wide", help="with --batch: \"wide_batch\" = 1 and the single E-step, or the exact launch groups")
-    ap.add_argument("--ckpt", action="store_true", help="\"wide_ckpt\" = 1 on the wide contexts of (a) and (e): X at every 8th bin only; the table's bytes are printed beside each time")
+    ap.add_argument("--ckpt", action="store_true", help="\"wide_ckpt\" = 1 on the wide contexts of (a) and (e): X at every 8th bin only; the table's bytes are printed beside each time.  With --decode: \"wide_ckpt\" = 1 and \"wide_decode_ckpt\" = 1 on the wide context of (d), decoding from checkpoints")
     ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
     args = ap.parse_args()
     from psmc_amd import hip, sim
@@ -270,7 +278,7 @@ def main():
         if args.batch > 0:
             out["n%d" % n] = batch_part(hip, segs, n, args.batch, args.batch_leg, args.ckpt)
         elif args.decode:
-            out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0)
+            out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0, args.ckpt)
         else:
             out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps, args.ckpt)
     if args.cli:
