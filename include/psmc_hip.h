@@ -17,8 +17,9 @@
  * _estep_segments, _estep_batch, the table readers and the decoding entry points; the device-resident and factored fast entry
  * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 or 2 a fast-mode context of 129..256 states
  * runs psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip, and with "wide_fast" = 2 one
- * of 257..1024 states runs them on the multi-wave kernels of estep_wide_fast_mw.hip (PSMC-form matrices; full
- * counts and psmc_hip_get_tables stay exact; so does the batch unless "wide_batch" = 1 is set as well -- see psmc_hip_estep_batch --
+ * of 257..1024 states runs them on the multi-wave kernels of estep_wide_fast_mw.hip (PSMC-form matrices; psmc_hip_get_tables stays
+ * exact; so do the full counts of psmc_hip_estep unless "wide_counts" = 1 is set as well -- then A comes from that E-step's tables
+ * through a GEMM on the FP64 matrix cores, estep_wide_counts.hip; so does the batch unless "wide_batch" = 1 is set as well -- see psmc_hip_estep_batch --
  * and so does decoding unless "wide_decode" = 1 is -- beyond 256 states together with "wide_fast" = 2: see "Decoding on a FAST context";
  * the path's forward table X takes 8 x (192, 256, 512, 768 or 1024) bytes per bin, with the option "wide_ckpt" = 1 an eighth of that);
  * row-major FP64; a[k*n+l]=P(k->l) (khmm.h:34); e[b*n+k], b=0 hom / 1 het
@@ -46,7 +47,9 @@ extern "C" {
 #define PSMC_HIP_EDEVICE  -3 /* HIP runtime error; see psmc_hip_last_error() */
 #define PSMC_HIP_ENOTSUP  -4 /* not supported in this build (n > 1024; the device-resident / factored fast entry points with n > 128 -- the
                                 factored ones with n > 256 when "wide_fast" is 1; "wide_fast" = 2 covers them all -- or with n > 64 and a
-                                matrix without the PSMC form; psmc_hip_estep_batch on the wide fast path -- "wide_batch" -- for the reasons
+                                matrix without the PSMC form; psmc_hip_estep never answers it beyond 128 states: where "wide_counts" does
+                                not apply it runs the wide exact kernels, and psmc_hip_estep_device beyond 128 states always answers it,
+                                "wide_counts" or not; psmc_hip_estep_batch on the wide fast path -- "wide_batch" -- for the reasons
                                 psmc_hip_estep_factored has there, the message naming the replicate).  The decoding entry points never
                                 answer it beyond 128 states: where they cannot read the wide fast tables ("wide_decode") they read the
                                 exact ones */
@@ -137,8 +140,34 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           state rule of "Decoding on a FAST context" is unchanged.  Without "wide_ckpt", in exact mode, up to 128
  *                           states or with "wide_fast" = 0: accepted, no effect.  Other values: PSMC_HIP_EINVAL
  *  "wide_batch"    0        1: psmc_hip_estep_batch[_cb] of a fast-mode context of 129..1024 states whose size "wide_fast" covers, asked for
- *                           sums and not for A, runs every replicate on the wide fast path (see psmc_hip_estep_batch, "wide fast batch").
+ *                           sums and not for A -- with "wide_counts" = 1: for A as well --, runs every replicate on the wide fast path (see
+ *                           psmc_hip_estep_batch, "wide fast batch").
  *                           0, and every other context or call: the batch as without the option.  Other values: PSMC_HIP_EINVAL
+ *  "wide_counts"   0        1: psmc_hip_estep of a fast-mode context of 129..1024 states whose size "wide_fast" covers (1: up to 256 states,
+ *                           2: up to 1024), with "structured" = 1 and a matrix of the PSMC form, returns the full count matrix A from the
+ *                           wide fast path: the factored wide E-step as it stands (its sweeps, verify / repair rounds, E and LL, bit for
+ *                           bit), then a counts pass (estep_wide_counts.hip): per slab of whole tiles one more backward sweep from the
+ *                           converged tile boundaries that writes V_p = mult bt_{p+1} / G_p, then C += X^T V as a split-K GEMM on
+ *                           v_mfma_f64_16x16x4 with one owner per partial matrix and no atomics, at the end A = a . C.  A0 = zeros and
+ *                           chk = 1.0 as after every fast-mode E-step; PSMC_HIP_ECONVERGE as the factored wide E-step answers it.  The
+ *                           result depends on the call's inputs and the options alone -- not on the device, on timing or on earlier
+ *                           calls: bit-reproducible.  That E-step keeps the full X table (interval 1) whatever "wide_ckpt" says, as
+ *                           "wide_decode" without "wide_decode_ckpt" does: counts from checkpoints are not built.  Device memory the
+ *                           counts pass adds, whatever the number of bins: one slab of V (8 S bytes per slab bin, S = the padded width;
+ *                           auto: at most 4 GB, or one tile if that is longer), the partial matrices (at most 64 MB), a and A (8 n^2 bytes each)
+ *                           and one slab's row ranges -- plus four bytes per tile of the plan; PSMC_HIP_ENOMEM with the size in the
+ *                           message when it does not fit.  Afterwards the E-step is "the last single E-step" exactly as a wide factored
+ *                           one is (decoding with "wide_decode", psmc_hip_get_tables: the exact tables stay what they were);
+ *                           psmc_hip_fast_info out[4] is 4 ("full counts of the wide path"; 3 after the factored statistics),
+ *                           psmc_hip_fast_repairs out[5] stays 2.  In every other case -- the option at 0, exact mode, up to 128 states, a
+ *                           matrix without the PSMC form, "structured" = 0, 257+ states with "wide_fast" = 1 -- psmc_hip_estep runs the
+ *                           wide exact kernels, bit for bit as without the option.  psmc_hip_estep_device beyond 128 states is not
+ *                           covered (PSMC_HIP_ENOTSUP as before); psmc_hip_group_estep reaches the path through its per-shard
+ *                           psmc_hip_estep.  With "wide_batch" = 1 the batch returns A this way too (psmc_hip_estep_batch).
+ *                           Other values: PSMC_HIP_EINVAL
+ *  "wide_counts_slab" 0     bins per slab of that counts pass (whole tiles in plan order; a tile longer than the slab is a slab of its
+ *                           own); 0 = auto: 2^29 / S bins (fewer tiles per slab serialise the V pass).  Slabs, row ranges and the split factor are functions of the tile plan and
+ *                           this option alone.  Negative: PSMC_HIP_EINVAL
  *  "merge"         0        1: a forward FIX pass between the forward sweep and the back half (64 states, fused back half): every tile's start
  *                           vector is checked there, and a tile that fails is rewritten from the true vector until its trajectory has the
  *                           direction of the stored one again (the factor between the two parts is kept for the counts and the likelihood) --
@@ -287,7 +316,9 @@ int psmc_hip_reserve_tables(psmc_hip_ctx *ctx);
  *   beyond 128 states: the exact launch groups above whatever the mode, bit for bit what an exact-mode context gives -- except the
  *   wide fast batch: a call takes the wide fast path ("wide_fast") if and only if "wide_batch" = 1, the context is in fast mode, has
  *     more than 128 states, "wide_fast" covers its size (1: up to 256 states, 2: up to 1024), A == NULL and sums != NULL.  A caller who
- *     wants A, alone or beside sums, gets the exact launch groups.  The wide path learns nothing between E-steps (its plan depends on
+ *     wants A, alone or beside sums, gets the exact launch groups -- unless "wide_counts" = 1 (and "structured" = 1): then the call
+ *     takes the wide path with A != NULL too, replicate r's A has the bits psmc_hip_select + psmc_hip_estep give on a fresh context
+ *     with the same options, and its sums are the factored statistics of the same E-step.  The wide path learns nothing between E-steps (its plan depends on
  *     the selection and the options alone), so there are no replicate contexts: for r = 0 .. n_rep-1, in order, the context selects
  *     replicate r's multiset, runs the E-step of psmc_hip_estep_factored with a[r], e[r], a0[r] into the rows r of sums / E / LL --
  *     the bits psmc_hip_select + psmc_hip_estep_factored give on a fresh context with the same options -- and calls done(user, 1, &r).

@@ -233,6 +233,8 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "wide_decode_ckpt") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_decode_ckpt = (int)v; } // api_wide_fast.hip, api_decode.hip
 	else if (k == "wide_ckpt") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_ckpt = (int)v; c->plan_dirty = true; } // api_wide_fast.hip
 	else if (k == "wide_batch") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_batch = (int)v; }
+	else if (k == "wide_counts") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_counts = (int)v; } // api_wide_fast.hip estep_counts_wide
+	else if (k == "wide_counts_slab") { if (v < 0 || v > 2147483647.0) return PSMC_HIP_EINVAL; c->wide_counts_slab = (int)v; }
 	else if (k == "rep_impl") c->rep_impl = v < 0 ? -1 : (v != 0 ? 1 : 0);
 	else return PSMC_HIP_EINVAL;
 	return PSMC_HIP_OK;
@@ -662,8 +664,13 @@ extern "C" int psmc_hip_estep(psmc_hip_ctx *c, const double *a, const double *e,
                               double *A0, double *LL, double *chk)
 {
 	if (!c || !a || !e || !a0) return fail(c, PSMC_HIP_EINVAL, "estep: bad argument");
-	// beyond 128 states there is no fast path: a fast-mode context runs the wide exact kernels (inside every fast tolerance)
-	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return estep_exact(c, a, e, a0, A, E, A0, LL, chk);
+	// beyond 128 states a fast-mode context runs the wide exact kernels (inside every fast tolerance) -- unless "wide_counts" sends the
+	// call to the wide fast path: the factored wide E-step, then the counts pass (api_wide_fast.hip)
+	if (c->mode != PSMC_HIP_MODE_EXACT && c->ns > 128 && counts_go_wide(c, a)) {
+		HIPCHK(c, hipSetDevice(c->device));
+		return estep_counts_wide(c, a, e, a0, A, nullptr, E, A0, LL, chk);
+	}
+	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) { c->wc_ran = false; return estep_exact(c, a, e, a0, A, E, A0, LL, chk); }
 	HIPCHK(c, hipSetDevice(c->device));
 	int rc = ensure_fast_buffers(c); // d_stats must exist before the first enqueue (the plan follows stage_params)
 	if (rc) return rc;

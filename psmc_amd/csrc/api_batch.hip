@@ -603,19 +603,20 @@ static int batch_fast(psmc_hip_ctx *c, int n_rep, const double *a, const double 
 	return PSMC_HIP_OK;
 }
 
-// "wide_batch" = 1, fast mode, 129..1024 states covered by "wide_fast", sums wanted and A not: every replicate's E-step on the wide fast
-// path.  That path learns nothing between E-steps -- its plan depends on the selection and the options alone (api_wide_fast.hip) -- so
+// "wide_batch" = 1, fast mode, 129..1024 states covered by "wide_fast", sums wanted and A not -- or, with "wide_counts" = 1, A wanted, alone
+// or beside sums: every replicate's E-step on the wide fast path.  That path learns nothing between E-steps -- its plan depends on the selection and the options alone (api_wide_fast.hip) -- so
 // there is nothing to keep per replicate: no child contexts, no shared learning, "batch_first" and "share_learn" are not read.  Replicate
 // r is psmc_hip_select(its multiset) + the single factored E-step on THIS context, with the bits those two calls give on a fresh
 // context; the X table is the context's one, sized for all loaded segments.  The selection the context had comes back on every exit.
 // ECONVERGE from a replicate: that replicate once more on the exact twin, the batch goes on wide; any other error ends the call.
 static bool batch_goes_wide(const psmc_hip_ctx *c, const double *A, const double *sums)
 {
-	return c->wide_batch && c->mode == PSMC_HIP_MODE_FAST && c->ns > 128 && c->wide_fast && (c->n <= 256 || c->wide_fast >= 2) && !A && sums;
+	if (!(c->wide_batch && c->mode == PSMC_HIP_MODE_FAST && c->ns > 128 && c->wide_fast && (c->n <= 256 || c->wide_fast >= 2))) return false;
+	return A ? c->wide_counts && c->struct_opt : sums != nullptr; // A, alone or beside sums: only with "wide_counts" (api_wide_fast.hip estep_counts_wide)
 }
 
 static int batch_wide(psmc_hip_ctx *c, int n_rep, const double *a, const double *e, const double *a0, const int32_t *sel_off,
-                      const int32_t *sel_idx, double *sums, double *E, double *LL, psmc_hip_batch_done_fn done, void *user)
+                      const int32_t *sel_idx, double *A, double *sums, double *E, double *LL, psmc_hip_batch_done_fn done, void *user)
 {
 	const int n = c->n;
 	for (int r = 0; r < n_rep; ++r) { // nothing runs, and the selection stays untouched, when any replicate's multiset is unusable
@@ -632,11 +633,14 @@ static int batch_wide(psmc_hip_ctx *c, int n_rep, const double *a, const double 
 		const int n_sel = sel_off[r + 1] - sel_off[r];
 		const int32_t *idx = sel_idx + sel_off[r];
 		const double *ar = a + (size_t)r * n * n, *er = e + (size_t)r * 2 * n, *a0r = a0 + (size_t)r * n;
-		double *Sr = sums + (size_t)r * 5 * n, *Er = E ? E + (size_t)r * 2 * n : nullptr, *Lr = LL ? LL + r : nullptr;
-		if ((rc = psmc_hip_select(c, n_sel, idx)) == 0) rc = estep_factored_wide(c, ar, er, a0r, Sr, Er, Lr);
+		double *Ar = A ? A + (size_t)r * n * n : nullptr, *Sr = sums ? sums + (size_t)r * 5 * n : nullptr;
+		double *Er = E ? E + (size_t)r * 2 * n : nullptr, *Lr = LL ? LL + r : nullptr;
+		// with A ("wide_counts"): the wide-counts E-step, whose factored statistics are the sums (a matrix without the PSMC form: ENOTSUP, as for the sums alone)
+		if ((rc = psmc_hip_select(c, n_sel, idx)) == 0)
+			rc = Ar ? estep_counts_wide(c, ar, er, a0r, Ar, Sr, Er, nullptr, Lr, nullptr) : estep_factored_wide(c, ar, er, a0r, Sr, Er, Lr);
 		if (rc == PSMC_HIP_ECONVERGE) {
 			const std::string why = c->err;
-			rc = batch_exact_once(c, r, idx, n_sel, ar, er, a0r, nullptr, Sr, Er, Lr, why.c_str(), "wide fast");
+			rc = batch_exact_once(c, r, idx, n_sel, ar, er, a0r, Ar, Sr, Er, Lr, why.c_str(), "wide fast");
 		}
 		if (rc) { c->err = "replicate " + std::to_string(r) + ": " + c->err; break; }
 		if (done) { const int32_t rr = r; done(user, 1, &rr); }
@@ -667,7 +671,7 @@ extern "C" int psmc_hip_estep_batch_cb(psmc_hip_ctx *c, int n_rep, const double 
 	if (c->n_seg < 1) return fail(c, PSMC_HIP_ESTATE, "estep_batch: no segments loaded");
 	HIPCHK(c, hipSetDevice(c->device));
 	c->wd_kind = WD_NONE; // (decoding after a batch needs a single E-step first, on the wide fast path as everywhere)
-	if (batch_goes_wide(c, A, sums)) return batch_wide(c, n_rep, a, e, a0, sel_off, sel_idx, sums, E, LL, done, user);
+	if (batch_goes_wide(c, A, sums)) return batch_wide(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user);
 	if (c->mode == PSMC_HIP_MODE_EXACT || c->ns > 128) return batch_exact(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user); // (beyond 128 states: the wide exact kernels whatever the mode, unless "wide_batch" sent the call the other way)
 	return batch_fast(c, n_rep, a, e, a0, sel_off, sel_idx, A, sums, E, LL, done, user);
 }

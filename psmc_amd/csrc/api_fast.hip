@@ -693,6 +693,8 @@ extern "C" int psmc_hip_estep_device(psmc_hip_ctx *c, const double *a, const dou
 {
 	if (!c || !a || !e || !a0 || !d_stats) return fail(c, PSMC_HIP_EINVAL, "estep_device: bad argument");
 	if (c->mode != PSMC_HIP_MODE_FAST) return fail(c, PSMC_HIP_ENOTSUP, "estep_device: fast mode only");
+	// (the kernels behind enqueue_fast are built for 64 and 128 padded states: nothing of them may be launched on a wider context)
+	if (c->ns > 128) return fail(c, PSMC_HIP_ENOTSUP, "estep_device: the device-resident full counts stop at 128 states; beyond them psmc_hip_estep runs the wide exact kernels, or with \"wide_counts\" the wide fast path");
 	c->timing_valid = false;
 	return enqueue_fast(c, a, e, a0, (double *)d_stats, (hipStream_t)stream);
 }
@@ -769,9 +771,9 @@ extern "C" int psmc_hip_estep_factored_device(psmc_hip_ctx *c, const double *a, 
 extern "C" int psmc_hip_fast_info(psmc_hip_ctx *c, int out[8])
 {
 	if (!c || !out) return PSMC_HIP_EINVAL;
-	if (c->wf_ran) { // the wide path (129..256 states: one tile per wave; 257..1024: one per work-group): no items
+	if (c->wf_ran) { // the wide path (129..256 states: one tile per wave; 257..1024: one per work-group): no items; back half 3 = its factored statistics, 4 = its full counts ("wide_counts")
 		const int nc = (int)c->wf_chunks.size();
-		out[0] = 1; out[1] = c->wf_T; out[2] = nc; out[3] = nc; out[4] = 3; out[5] = c->wf_last_iv == 8 ? 1 : 0; out[6] = 1; out[7] = 0;
+		out[0] = 1; out[1] = c->wf_T; out[2] = nc; out[3] = nc; out[4] = c->wc_ran ? 4 : 3; out[5] = c->wf_last_iv == 8 ? 1 : 0; out[6] = 1; out[7] = 0;
 		return PSMC_HIP_OK;
 	}
 	out[0] = c->use_struct ? 1 : 0; out[1] = c->chunk_used; out[2] = c->use_struct ? c->n_items_f : (int)c->chunks.size();

@@ -3,13 +3,17 @@
 // "wide_fast" = 2 (kernels: estep_wide_fast_mw.hip, 2..4 waves per tile at the padded widths 512, 768 and 1024; plan, rounds and
 // options are the same, only WideLaunch knows the width and the waves).  With "wide_decode" = 1 the decoding entry points read
 // what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip up to 256 states, estep_wide_post_mw.hip beyond).  Everything else a context of that size does --
-// psmc_hip_estep, the batch without "wide_batch" (with it: api_batch.hip batch_wide calls estep_factored_wide once per replicate),
+// psmc_hip_estep without "wide_counts", the batch without "wide_batch" (with it: api_batch.hip batch_wide calls estep_factored_wide once per replicate),
 // psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
 // "wide_ckpt" = 1: X at every 8th position only (S bytes per bin) plus every tile's last row, the accumulate sweep recomputes the rest
 // (estep_wide_fast.hip); "wide_decode" = 1 wins, because the full-table decoding kernels read every row -- unless "wide_decode_ckpt" = 1:
 // then the table does not depend on "wide_decode", and decoding recomputes the rows between the checkpoints as the accumulate sweep
 // does (the CKPT kernels of estep_wide_post.hip / estep_wide_post_mw.hip).  The table is sized anew when the interval
 // changes between two E-steps, and what ran is recorded for fast_info, psmc_hip_wide_table_info and decode_source.
+//
+// "wide_counts" = 1: psmc_hip_estep of such a context (and, with "wide_batch", the batch asked for A) runs the factored E-step below with
+// the full table (it wins over "wide_ckpt" for that E-step, as "wide_decode" does) and then the counts pass of estep_wide_counts.hip
+// -- per slab of whole tiles a V pass and a split-K GEMM on the f64 matrix cores, at the end A = a . C (estep_counts_wide, below).
 //
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
 // of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,
@@ -26,13 +30,15 @@ static constexpr int WF_NACC = 7; // SL SU DG CL CU E0 E1 per tile
 void free_wide_fast(psmc_hip_ctx *c)
 {
 	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
-	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi};
+	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi, c->d_wc_V, c->d_wc_P, c->d_wc_a, c->d_wc_out, c->d_wc_kr, c->d_wc_vrow};
 	for (void *q : p) if (q) (void)hipFree(q);
 	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
 	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
 	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
 	c->d_wf_xhi = nullptr; c->wf_xhi_cap = 0; c->wf_rows = 0; c->wf_tab_iv = c->wf_last_iv = 0;
 	c->wf_cap = 0; c->wf_bins = 0;
+	c->d_wc_V = c->d_wc_P = c->d_wc_a = c->d_wc_out = nullptr; c->d_wc_kr = nullptr; c->d_wc_vrow = nullptr;
+	c->wc_v_cap = c->wc_p_cap = c->wc_kr_cap = c->wc_vrow_cap = 0;
 }
 
 // rows of the X table over `bins` positions at one row per `iv` positions (iv = 8: the rows at p % 8 == 0, by absolute position)
@@ -143,8 +149,8 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	if ((c->plan_dirty || c->wf_chunks.empty()) && (rc = plan_wide(c))) return rc;
 	const int64_t bins = c->total + 128;
 	// "wide_ckpt": one X row per 8 positions -- unless "wide_decode" is on without "wide_decode_ckpt": the full-table decoding kernels
-	// read every row, so that E-step keeps them
-	const int iv = c->wide_ckpt && (!c->wide_decode || c->wide_decode_ckpt) ? 8 : 1;
+	// read every row, so that E-step keeps them; and so does a wide-counts E-step ("wide_counts": the GEMM reads every row)
+	const int iv = c->wide_ckpt && !c->wc_now && (!c->wide_decode || c->wide_decode_ckpt) ? 8 : 1;
 	const int nt = (int)c->wf_chunks.size();
 	c->wf_last_iv = 0;
 	if (c->wf_bins < bins || c->wf_tab_iv != iv) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins; 8 KB per bin at S = 1024), with "wide_ckpt" S bytes per bin; sized anew when the interval changes, whether it grows or shrinks
@@ -183,7 +189,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	w.X = c->d_wf_X; w.inv = c->d_wf_inv; w.entry = c->d_wf_entry; w.bentry = c->d_wf_bentry; w.bexit = c->d_wf_bexit;
 	w.part = c->d_wf_part; w.LLpart = c->d_wf_ll; w.stage = c->d_stage; w.out = d_out;
 	c->report = FastReport{0, 0, 0, 0, 0, 0, 2};
-	c->wf_ran = true; c->last_fused = 3; c->wf_last_iv = iv;
+	c->wf_ran = true; c->wc_ran = false; c->last_fused = 3; c->wf_last_iv = iv;
 	if (launch_wide_fast(w, WF_FWD) || launch_wide_fast(w, WF_BWARM)) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
 	int r = 0, t = 0;
 	rc = wide_rounds(c, w, false, r, t);
@@ -218,6 +224,132 @@ int estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const
 	for (double &v : c->last_ms) v = 0.0;
 	c->last_ms[0] = ms;
 	unpack_factored(h.data(), n, sums, E, LL);
+	return PSMC_HIP_OK;
+}
+
+// ---------------------------------------------------------------- "wide_counts": the full count matrix (estep_wide_counts.hip)
+// does psmc_hip_estep with this matrix run on the wide fast path?  (everything else: the wide exact kernels, as without the option)
+bool counts_go_wide(const psmc_hip_ctx *c, const double *a)
+{
+	if (!c->wide_counts || c->mode != PSMC_HIP_MODE_FAST || c->ns <= 128 || !c->wide_fast || (c->n > 256 && c->wide_fast < 2) || !c->struct_opt) return false;
+	std::vector<double> sp((size_t)5 * c->n);
+	return factor_structure(c->n, c->n, a, sp.data());
+}
+
+// The plan of the counts pass, from the tile plan and "wide_counts_slab" alone.  A tile owns the transitions of its positions
+// lo .. min(hi, L - 1) -- none when it holds only position L.  Slabs are runs of whole tiles in plan order with at most `slab` rows
+// (a tile longer than that is a slab of its own); auto: 2^29 / S rows, a V slab of 4 GB -- the V pass of a slab is one sweep of
+// a tile's length whatever the number of its tiles (up to the ~3000 waves the device holds), so few tiles per slab serialise it: on the
+// 30 M-bin genome at 200 states (tiles of 7360 bins) slabs of 2^26 / S rows, 35 tiles each, made the pass 734 ms, of which the GEMM
+// needs about 160.  The GEMM's K is cut into ranges of at
+// most WC_KC rows that never cross a tile's end; split s of a slab takes an equal share of its ranges.  n_split: about 2048 waves
+// with the (S / 64)^2 blocks of C -- 64 MB of partials at every width -- and no more than the largest slab has ranges.
+struct CountsPlan {
+	std::vector<int32_t> vrow;        // [tiles] first V row of the tile in its slab
+	std::vector<KRange> kr;           // every slab's ranges, slab after slab
+	std::vector<int> slab_t0, slab_kr; // [slabs + 1] first tile / first range of every slab
+	int64_t max_rows = 0; int max_kr = 0, n_split = 1;
+};
+static constexpr int WC_KC = 256;
+
+static void plan_counts(const psmc_hip_ctx *c, int S, CountsPlan &pl)
+{
+	const int nt = (int)c->wf_chunks.size();
+	const int64_t slab = c->wide_counts_slab > 0 ? c->wide_counts_slab : std::max<int64_t>(1, ((int64_t)1 << 29) / S);
+	pl.vrow.assign(nt, 0);
+	pl.slab_t0.assign(1, 0); pl.slab_kr.assign(1, 0);
+	int64_t rows = 0;
+	for (int b = 0; b < nt; ++b) {
+		const Chunk &ch = c->wf_chunks[b];
+		const int own = std::max(0, std::min(ch.hi, ch.L - 1) - ch.lo + 1);
+		if (rows > 0 && rows + own > slab) { // the slab is full: this tile opens the next one
+			pl.slab_t0.push_back(b); pl.slab_kr.push_back((int)pl.kr.size());
+			rows = 0;
+		}
+		pl.vrow[b] = (int32_t)rows;
+		for (int r = 0; r < own; r += WC_KC) pl.kr.push_back(KRange{ch.off + ch.lo - 1 + r, (int32_t)(rows + r), std::min(WC_KC, own - r)});
+		rows += own;
+		pl.max_rows = std::max(pl.max_rows, rows);
+	}
+	pl.slab_t0.push_back(nt); pl.slab_kr.push_back((int)pl.kr.size());
+	for (size_t i = 0; i + 1 < pl.slab_kr.size(); ++i) pl.max_kr = std::max(pl.max_kr, pl.slab_kr[i + 1] - pl.slab_kr[i]);
+	pl.n_split = std::max(1, std::min(2048 / ((S / 64) * (S / 64)), pl.max_kr));
+}
+
+// One wide-counts E-step: the factored wide E-step with the full table (its bits: E, LL and the factored statistics), then per slab
+// the V pass and the GEMM, then the finish -- all on the context's stream.  Device memory the pass adds, whatever the number of
+// bins: the V slab (at most 8 S max(slab, longest tile) bytes; auto: 4 GB), the partials (n_split S^2 doubles, at most 64 MB),
+// a and A (n^2 doubles each), one slab's ranges (16 bytes per 256 rows) -- and four bytes per tile of the plan.
+int estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *A, double *sums, double *E, double *A0,
+                      double *LL, double *chk)
+{
+	int rc = ensure_fast_buffers(c);
+	if (rc) return rc;
+	c->wc_now = true;
+	rc = estep_wide_fast(c, a, e, a0, c->d_stats, c->stream);
+	c->wc_now = false;
+	if (rc) return rc;
+	c->wd_kind = WD_FAILED; // until the counts are through (an error below leaves nothing to decode, as one in the E-step)
+	const int n = c->n, S = wf_width(c);
+	char msg[320];
+	CountsPlan pl;
+	plan_counts(c, S, pl);
+	const int nt = (int)c->wf_chunks.size(), n_slabs = (int)pl.slab_t0.size() - 1;
+	auto grow = [&](auto **p, size_t &cap, size_t want, const char *what) -> int {
+		if (cap >= want && *p) return 0;
+		cap = 0;
+		if (dev_alloc(c, p, want)) {
+			snprintf(msg, sizeof msg, "estep: no device memory for %s of the wide counts pass: %lld bytes (\"wide_counts_slab\" bounds the slab)",
+			         what, (long long)(want * sizeof(**p)));
+			return fail(c, PSMC_HIP_ENOMEM, msg);
+		}
+		cap = want;
+		return 0;
+	};
+	if ((rc = grow(&c->d_wc_V, c->wc_v_cap, (size_t)std::max<int64_t>(pl.max_rows, 1) * S, "the V slab"))) return rc;
+	if ((rc = grow(&c->d_wc_P, c->wc_p_cap, (size_t)pl.n_split * S * S, "the partial matrices"))) return rc;
+	if ((rc = grow(&c->d_wc_kr, c->wc_kr_cap, (size_t)std::max(pl.max_kr, 1), "the K ranges"))) return rc;
+	if ((rc = grow(&c->d_wc_vrow, c->wc_vrow_cap, (size_t)nt, "the tiles' rows"))) return rc;
+	if (!c->d_wc_a && ((rc = dev_alloc(c, &c->d_wc_a, (size_t)n * n)) || (rc = dev_alloc(c, &c->d_wc_out, (size_t)n * n)))) return rc;
+	hipStream_t st = c->stream;
+	HIPCHK(c, hipMemcpyAsync(c->d_wc_a, a, sizeof(double) * n * n, hipMemcpyHostToDevice, st));
+	HIPCHK(c, hipMemcpyAsync(c->d_wc_vrow, pl.vrow.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, st));
+	WideCounts w;
+	memset(&w, 0, sizeof(w));
+	w.stream = st; w.ns = S; w.n_states = n; w.waves = wf_waves(c);
+	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks; w.X = c->d_wf_X; w.bentry = c->d_wf_bentry;
+	w.vrow = c->d_wc_vrow; w.V = c->d_wc_V; w.kr = c->d_wc_kr; w.n_split = pl.n_split; w.P = c->d_wc_P;
+	w.a = c->d_wc_a; w.out = c->d_wc_out; w.tiny_total = (double)c->sel.size() * HMM_TINY_H;
+	bool first = true;
+	for (int i = 0; i < n_slabs; ++i) { // (pl lives on the host until the stream is through: the synchronize below)
+		w.t0 = pl.slab_t0[i]; w.n_tiles = pl.slab_t0[i + 1] - w.t0; w.n_kr = pl.slab_kr[i + 1] - pl.slab_kr[i]; w.first = first ? 1 : 0;
+		if (w.n_kr == 0) continue; // tiles without a transition only
+		HIPCHK(c, hipMemcpyAsync(c->d_wc_kr, pl.kr.data() + pl.slab_kr[i], sizeof(KRange) * w.n_kr, hipMemcpyHostToDevice, st));
+		if (launch_wide_counts(w, WC_V) || launch_wide_counts(w, WC_GEMM)) {
+			const hipError_t err = hipGetLastError();
+			(void)hipStreamSynchronize(st); // (the copies out of pl)
+			return fail(c, PSMC_HIP_EDEVICE, "wide counts: k_wc_v / k_wc_gemm", err);
+		}
+		first = false;
+	}
+	if (first) w.n_split = 0; // no transition at all: no partial was written, and none is read
+	if (launch_wide_counts(w, WC_FINISH)) return fail(c, PSMC_HIP_EDEVICE, "k_wc_finish", hipGetLastError());
+	HIPCHK(c, hipEventRecord(c->ev[5], st));
+	std::vector<double> h((size_t)7 * n + 1), hA(A ? (size_t)n * n : 0);
+	HIPCHK(c, hipMemcpyAsync(h.data(), c->d_stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+	if (A) HIPCHK(c, hipMemcpyAsync(hA.data(), c->d_wc_out, sizeof(double) * hA.size(), hipMemcpyDeviceToHost, st));
+	HIPCHK(c, hipStreamSynchronize(st));
+	float ms = 0.0f, ms_c = 0.0f; // last_ms: [0] the whole E-step, [1] the factored part, [3] the counts pass (psmc_hip_last_timing: total, chains, expect)
+	c->timing_valid = hipEventElapsedTime(&ms, c->ev[0], c->ev[5]) == hipSuccess && hipEventElapsedTime(&ms_c, c->ev[4], c->ev[5]) == hipSuccess;
+	if (!c->timing_valid) (void)hipGetLastError();
+	for (double &v : c->last_ms) v = 0.0;
+	c->last_ms[0] = ms; c->last_ms[1] = ms - ms_c; c->last_ms[3] = ms_c;
+	unpack_factored(h.data(), n, sums, E, LL);
+	if (A) memcpy(A, hA.data(), sizeof(double) * hA.size());
+	if (A0) memset(A0, 0, sizeof(double) * n); // as every fast-mode E-step (api_fast.hip estep_fast)
+	if (chk) for (size_t i = 0; i < c->sel.size(); ++i) chk[i] = 1.0;
+	c->wc_ran = true;
+	c->wd_kind = WD_OK;
 	return PSMC_HIP_OK;
 }
 

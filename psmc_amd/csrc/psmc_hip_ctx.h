@@ -1,7 +1,7 @@
 // psmc_hip_ctx.h -- the context behind the C-ABI of include/psmc_hip.h and the helpers its translation units share:
 //   api.hip        context, options, segments, parameter staging, tables, exact mode, the table reader
 //   api_fast.hip   fast mode: tile plan, sweep items, learning, the launch of one fast E-step and its entry points
-//   api_wide_fast.hip  fast mode at 129..256 states ("wide_fast") and 257..1024 states ("wide_fast" = 2): plan, rounds and launch of the factored E-step
+//   api_wide_fast.hip  fast mode at 129..256 states ("wide_fast") and 257..1024 states ("wide_fast" = 2): plan, rounds and launch of the factored E-step; the full counts of that path ("wide_counts")
 //   api_decode.hip psmc_hip_decode / _posterior / _post_counts / _scales from the exact, the fast or the wide fast tables (one wave per tile or 2..4)
 //   api_batch.hip  psmc_hip_estep_batch (bootstrap replicates): exact launch groups, fast per-replicate plans
 //   api_probes.hip device self-test, microbenchmarks and probes (diagnostics)
@@ -20,6 +20,7 @@
 #include <vector>
 #include "psmc_hip.h"
 #include "psmc_hip_internal.h"
+#include "wide_fast.h"
 
 using namespace psmc;
 
@@ -252,6 +253,17 @@ struct psmc_hip_ctx {
 	// "wide_batch" = 1: psmc_hip_estep_batch[_cb] of such a context, asked for sums only, runs every replicate's E-step on the wide fast
 	// path -- on this context itself, one selection after the other: the path learns nothing, so no child contexts (api_batch.hip batch_wide)
 	int wide_batch = 0;
+	// "wide_counts" = 1: psmc_hip_estep of such a context (fast mode, a size "wide_fast" covers, "structured" on, a matrix of the PSMC
+	// form) runs the factored wide E-step with the full X table and then the counts pass of estep_wide_counts.hip (api_wide_fast.hip
+	// estep_counts_wide); the batch with "wide_batch" takes the wide path when A is asked for, too.  "wide_counts_slab": bins per
+	// slab of that pass, 0 = auto.  wc_now: the E-step under way is one (interval 1 whatever "wide_ckpt" says); wc_ran: the last wide
+	// fast E-step was one (fast_info).  Device memory of the pass: one slab of V, the partial matrices, a, A, the slab's ranges,
+	// and one int per tile
+	int wide_counts = 0, wide_counts_slab = 0;
+	bool wc_now = false, wc_ran = false;
+	double *d_wc_V = nullptr, *d_wc_P = nullptr, *d_wc_a = nullptr, *d_wc_out = nullptr;
+	KRange *d_wc_kr = nullptr; int32_t *d_wc_vrow = nullptr;
+	size_t wc_v_cap = 0, wc_p_cap = 0, wc_kr_cap = 0, wc_vrow_cap = 0; // rows x width | doubles | ranges | tiles
 };
 // the padded width of the wide fast path's own tables (api_wide_fast.hip writes them, api_decode.hip reads them): c->ns (192 or 256)
 // up to 256 states, beyond them the next multiple of 256 -- one wave of the tile per 256 states (c->ns stays what the wide exact
@@ -315,4 +327,6 @@ bool factor_structure(int n, int S, const double *a, double *sp);               
 void free_wide_fast(psmc_hip_ctx *c);                                                                       // api_wide_fast.hip
 int  estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *d_out, hipStream_t st); // api_wide_fast.hip
 int  estep_factored_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *sums, double *E, double *LL); // api_wide_fast.hip
+bool counts_go_wide(const psmc_hip_ctx *c, const double *a);                                                // api_wide_fast.hip
+int  estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *A, double *sums, double *E, double *A0, double *LL, double *chk); // api_wide_fast.hip
 int  estep_fast(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *A, double *E, double *A0, double *LL, double *chk); // api_fast.hip

@@ -1,6 +1,7 @@
 // wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states:
 // one wave per tile), of estep_wide_fast_mw.hip (257..1024 states: 2..4 waves per tile), of estep_wide_post.hip (decoding from
-// the tables the one-wave E-step left) and of estep_wide_post_mw.hip (decoding from the tables the multi-wave E-step left).
+// the tables the one-wave E-step left), of estep_wide_post_mw.hip (decoding from the tables the multi-wave E-step left) and of
+// estep_wide_counts.hip (the full count matrix from those tables, "wide_counts").
 #pragma once
 #include <hip/hip_runtime.h>
 #include "psmc_hip_internal.h"
@@ -51,5 +52,31 @@ struct WidePost {
 int launch_wide_post(const WidePost &w);         // estep_wide_post.hip (waves > 1: hands on to the next)
 int launch_wide_post_mw(const WidePost &w);      // estep_wide_post_mw.hip
 int launch_wide_post_cnt_add(const WidePost &w); // estep_wide_post.hip: WP_COUNTS, the tiles' partials added in tile order, at every width
+
+// the full count matrix ("wide_counts", estep_wide_counts.hip): per slab of whole tiles WC_V, then WC_GEMM; at the end WC_FINISH
+enum { WC_V, WC_GEMM, WC_FINISH };
+
+// rows of K the GEMM reads: `rows` consecutive positions of one tile, from row xrow of X and row vrow of the slab's V
+struct KRange { int64_t xrow; int32_t vrow, rows; };
+
+struct WideCounts {
+	hipStream_t stream;
+	int ns, n_states, waves;          // as WideLaunch
+	int t0, n_tiles;                  // WC_V: the slab's tiles t0 .. t0 + n_tiles - 1 of the plan
+	const double *par;                // as WideLaunch
+	const uint8_t *obs;
+	const Chunk *chunks;
+	const double *X, *bentry;         // the full table (interval 1) and the converged start vectors the E-step left
+	const int32_t *vrow;              // [tiles of the plan] the tile's first row in its slab's V
+	double *V;                        // [rows of the largest slab][ns]
+	const KRange *kr; int n_kr;       // WC_GEMM: the slab's ranges
+	int n_split, first;               // partial matrices; first: this is the call's first slab (the partials start from zero)
+	double *P;                        // [n_split][ns][ns]
+	const double *a;                  // WC_FINISH: the transition matrix [n_states][n_states]
+	double tiny_total;                // ... HMM_TINY x selected segments, added to every cell (as WideLaunch)
+	double *out;                      // ... and A, [n_states][n_states]
+};
+
+int launch_wide_counts(const WideCounts &w, int what); // estep_wide_counts.hip
 
 } // namespace psmc

@@ -24,6 +24,12 @@
       a process of its own so that a job can give each leg its time limit -- the same batch with "wide_batch" = 0: the exact
       launch groups, what such a context ran before the option existed
 
+  (f) with --counts: the full count matrix from the wide fast path ("wide_counts", estep_wide_counts.hip) -- ms per psmc_hip_estep of a
+      context with "wide_fast" + "wide_counts" (parameters moving as in (a); the first step and the later ones, and of the later ones
+      what the library's events give to the factored part and to the counts pass), ms per factored wide E-step of the same build
+      and parameters, and -- unless --exact-steps 0 -- ms per psmc_hip_estep on the wide exact kernels, what that call ran before the
+      option existed; --counts-slab sets "wide_counts_slab"
+
   --ckpt sets "wide_ckpt" = 1 on the wide contexts of (a) and (e): X at every 8th bin only, the rest recomputed in the accumulate
   sweep.  Beside every time, (a) and (e) print what psmc_hip_wide_table_info reports: the bytes of X the context holds.
   With --decode it sets "wide_ckpt" = 1 and "wide_decode_ckpt" = 1 on the wide context of (d): the decoding E-step keeps checkpoints
@@ -37,6 +43,7 @@ Library calls are synchronous.  Writes one JSON object to stdout (progress on st
     python scripts/wide_fast_timing.py --decode --stress --states 300,1024
     python scripts/wide_fast_timing.py --decode --stress --states 200,300,1024 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
+    python scripts/wide_fast_timing.py --counts [--stress] --states 200,300,1024 --steps 4 --exact-steps 1
 """
 import argparse
 import json
@@ -121,6 +128,44 @@ def library_part(hip, segs, n, steps, exact_steps, ckpt=False):
         r["exact_ms"] = float(np.min(xs)) if xs else r["exact_first_ms"]
         r["exact_over_fast"] = r["exact_ms"] / r["fast_later_ms_mean"]
         print(json.dumps({"n%d" % n: {k: r[k] for k in ("exact_first_ms", "exact_ms", "exact_over_fast")}}), file=sys.stderr, flush=True)
+    return r
+
+
+def counts_part(hip, segs, n, steps, exact_steps, slab=0):
+    """(f)"""
+    ps = params_seq(n, steps)
+    r = {"wide_counts_slab": slab}
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_counts=1, wide_counts_slab=slab)
+    es.load_segments(segs)
+    ms, dev = [], []
+    for a, e, a0 in ps:
+        t = time.perf_counter(); es.estep(a, e, a0); ms.append((time.perf_counter() - t) * 1e3)
+        tm = es.timing()
+        dev.append(dict(total=float(tm["total"]), factored=float(tm["chains"]), counts=float(tm["expect"])))
+    d = es.fast_diag()
+    assert d["back_half"] == 4, d
+    ti = table_info(es)
+    r.update(tiles=d["n_chunks"], tile_len=d["tile_len"], x_table_bytes=ti["bytes"] if ti else None, counts_ms=ms, counts_first_ms=ms[0],
+             counts_later_ms_mean=float(np.mean(ms[1:])), counts_later_ms_min=float(np.min(ms[1:])), device_ms=dev,
+             device_counts_pass_ms_mean=float(np.mean([x["counts"] for x in dev[1:]])),
+             device_factored_part_ms_mean=float(np.mean([x["factored"] for x in dev[1:]])))
+    fm = []
+    for a, e, a0 in ps:   # the factored wide E-step of the same build, on the same context (the first one sizes nothing anew)
+        t = time.perf_counter(); es.estep_factored(a, e[:2], a0); fm.append((time.perf_counter() - t) * 1e3)
+    r.update(factored_ms=fm, factored_later_ms_mean=float(np.mean(fm[1:])))
+    r["counts_over_factored"] = r["counts_later_ms_mean"] / r["factored_later_ms_mean"]
+    es.close()
+    print(json.dumps({"n%d" % n: r}), file=sys.stderr, flush=True)
+    if exact_steps > 0:
+        ex = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1)   # the same call without the option: the wide exact kernels
+        ex.load_segments(segs)
+        a, e, a0 = ps[0]
+        xs = []
+        for _ in range(exact_steps):
+            t = time.perf_counter(); ex.estep(a, e, a0); xs.append((time.perf_counter() - t) * 1e3)
+        ex.close()
+        r.update(exact_ms_all=xs, exact_ms=float(np.min(xs)), exact_over_counts=float(np.min(xs)) / r["counts_later_ms_mean"])
+        print(json.dumps({"n%d" % n: {k: r[k] for k in ("exact_ms_all", "exact_ms", "exact_over_counts")}}), file=sys.stderr, flush=True)
     return r
 
 
@@ -261,6 +306,8 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="(e): the bootstrap batch of this many replicates on the wide fast path instead of (a), (b)")
     ap.add_argument("--batch-leg", choices=["wide", "exact"], default="wide", help="with --batch: \"wide_batch\" = 1 and the single E-step, or the exact launch groups")
     ap.add_argument("--ckpt", action="store_true", help="\"wide_ckpt\" = 1 on the wide contexts of (a) and (e): X at every 8th bin only; the table's bytes are printed beside each time.  With --decode: \"wide_ckpt\" = 1 and \"wide_decode_ckpt\" = 1 on the wide context of (d), decoding from checkpoints")
+    ap.add_argument("--counts", action="store_true", help="(f): psmc_hip_estep with \"wide_counts\" = 1 against the factored wide E-step and the exact kernels instead of (a), (b)")
+    ap.add_argument("--counts-slab", type=int, default=0, help="with --counts: \"wide_counts_slab\" (0 = auto)")
     ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
     args = ap.parse_args()
     from psmc_amd import hip, sim
@@ -275,7 +322,9 @@ def main():
         segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
         out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
     for n in [int(x) for x in args.states.split(",") if x]:
-        if args.batch > 0:
+        if args.counts:
+            out["n%d" % n] = counts_part(hip, segs, n, args.steps, args.exact_steps, args.counts_slab)
+        elif args.batch > 0:
             out["n%d" % n] = batch_part(hip, segs, n, args.batch, args.batch_leg, args.ckpt)
         elif args.decode:
             out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0, args.ckpt)
