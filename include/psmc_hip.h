@@ -17,7 +17,7 @@
  * _estep_segments, _estep_batch, the table readers and the decoding entry points; the device-resident and factored fast entry
  * points return PSMC_HIP_ENOTSUP there, except that with the option "wide_fast" = 1 or 2 a fast-mode context of 129..256 states
  * runs psmc_hip_estep_factored and _estep_factored_device on the fast kernels of estep_wide_fast.hip, and with "wide_fast" = 2 one
- * of 257..1024 states runs them on the multi-wave kernels of estep_wide_fast_mw.hip (PSMC-form matrices; psmc_hip_get_tables stays
+ * of 257..1024 states runs them on the same kernels with 2..4 waves per tile (PSMC-form matrices; psmc_hip_get_tables stays
  * exact; so do the full counts of psmc_hip_estep unless "wide_counts" = 1 is set as well -- then A comes from that E-step's tables
  * through a GEMM on the FP64 matrix cores, estep_wide_counts.hip; so does the batch unless "wide_batch" = 1 is set as well -- see psmc_hip_estep_batch --
  * and so does decoding unless "wide_decode" = 1 is -- beyond 256 states together with "wide_fast" = 2: see "Decoding on a FAST context";
@@ -95,7 +95,7 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           "wide_batch": see psmc_hip_estep_batch) and the decoding entry points (without "wide_decode") stay on the
  *                           exact kernels, bit for bit.  Exact mode and <= 128 states: no effect.
  *                           2: the same at 129..256 states (the same kernels, the same bits as 1), and a fast-mode context of 257..1024
- *                           states runs them on the kernels of estep_wide_fast_mw.hip: a tile is one work-group of 2, 3 or 4 waves
+ *                           states runs them on the same kernels of estep_wide_fast.hip: a tile is one work-group of 2, 3 or 4 waves
  *                           (padded widths 512, 768, 1024: 64 lanes x 4 states per wave), the waves exchange their scan totals through
  *                           LDS once per position.  Plan, options, ENOTSUP / ECONVERGE and diagnostics as for 1; the X table is 8 x 512,
  *                           8 x 768 or 8 x 1024 bytes per bin -- 123, 184 or 246 GB at 30 M bins; with "wide_ckpt" = 1: 512, 768 or 1024
@@ -105,8 +105,8 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           Other values: PSMC_HIP_EINVAL
  *  "wide_decode"   0        1, with "wide_fast" = 1 or 2 on a fast-mode context of 129..256 states, and with "wide_fast" = 2 on one of
  *                           257..1024 states: psmc_hip_decode, _posterior, _post_counts and _scales read what the LAST single E-step
- *                           left -- after a wide fast factored E-step its X table and converged tile boundaries (estep_wide_post.hip,
- *                           beyond 256 states estep_wide_post_mw.hip; no backward table), after psmc_hip_estep the exact tables,
+ *                           left -- after a wide fast factored E-step its X table and converged tile boundaries (estep_wide_post.hip; no
+ *                           backward table), after psmc_hip_estep the exact tables,
  *                           bit for bit (see "Decoding on a FAST context").  0: the exact tables whatever E-step ran last, as before
  *                           the option existed.  Anywhere else -- exact mode, up to 128 states, beyond 256 states with "wide_fast" = 1
  *                           -- no effect.  (In the one release where "wide_fast" = 2 existed without this, the pair had no effect
@@ -131,7 +131,7 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           "wide_decode" = 1 (interval 8 in psmc_hip_wide_table_info, psmc_hip_fast_info out[5] = 1: the E-step's
  *                           table no longer depends on "wide_decode"), and psmc_hip_decode, _posterior, _post_counts and _scales after
  *                           such an E-step read its checkpoints, the tiles' last rows, 1/d and the tile boundaries: the CKPT kernels of
- *                           estep_wide_post.hip / estep_wide_post_mw.hip recompute the seven rows between two checkpoints with the
+ *                           estep_wide_post.hip recompute the seven rows between two checkpoints with the
  *                           forward sweep's own arithmetic, block by block as the E-step's accumulate sweep does, and return the bits
  *                           of decoding from the full table.  "wide_decode" may be switched on after that E-step: nothing is re-run.
  *                           The option is read by every decoding call too: back at 0, a call after a checkpointed E-step answers
@@ -457,7 +457,7 @@ int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
  * 129..256 states with "wide_fast" = 1 or 2, 257..1024 states with "wide_fast" = 2, and "wide_decode" = 1: the same rule -- the
  * last single E-step decides.
  *   - a wide fast factored E-step (psmc_hip_estep_factored / _estep_factored_device) that returned 0: one more backward sweep per
- *     tile (estep_wide_post.hip; beyond 256 states estep_wide_post_mw.hip, a tile being one work-group of 2..4 waves over X at
+ *     tile (estep_wide_post.hip; beyond 256 states a tile is one work-group of 2..4 waves over X at
  *     the padded width 512 / 768 / 1024) from the tile's converged start vector bt_{top+1}, reading X; no backward table exists
  *     or is written.  With y = a bt_{p+1}:  gamma_p(k) = X_p(k) y(k) / G_p,  G_p = sum_k X_p(k) y(k)  (the posterior the E-step's E adds
  *     up; no division by an emission);  recomb_p = 1 - sum_l X_p(l) a_ll bt_{p+1}(l) / G_p;  at p = L: gamma_L = X_L / sum X_L,

@@ -228,7 +228,7 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "batch_bins") { if (v < 0) return PSMC_HIP_EINVAL; c->batch_bins = (int64_t)v; }
 	else if (k == "overlap") c->overlap = v != 0 ? 1 : 0;
 	else if (k == "warm_tol") c->warm_tol = v;
-	else if (k == "wide_fast") { if (v != 0 && v != 1 && v != 2) return PSMC_HIP_EINVAL; c->wide_fast = (int)v; } // 2: also 257..1024 states (estep_wide_fast_mw.hip)
+	else if (k == "wide_fast") { if (v != 0 && v != 1 && v != 2) return PSMC_HIP_EINVAL; c->wide_fast = (int)v; } // 2: also 257..1024 states (2..4 waves per tile)
 	else if (k == "wide_decode") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_decode = (int)v; }
 	else if (k == "wide_decode_ckpt") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_decode_ckpt = (int)v; } // api_wide_fast.hip, api_decode.hip
 	else if (k == "wide_ckpt") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_ckpt = (int)v; c->plan_dirty = true; } // api_wide_fast.hip

@@ -3,7 +3,7 @@
 //   DEC_EXACT  f, b and s of the exact kernels (estep_exact.hip, estep_wide.hip beyond 128 states)
 //   DEC_FAST   X and bt of a fast E-step with the unfused back half, up to 128 states (estep_post_fast.hip)
 //   DEC_WIDE   X, 1/d, entry and bentry of a wide fast E-step with "wide_decode": 129..256 states (estep_wide_post.hip), and
-//              257..1024 states with "wide_fast" = 2 (estep_wide_post_mw.hip; the tables are 512, 768 or 1024 states wide).  After a
+//              257..1024 states with "wide_fast" = 2 (the same file; the tables are 512, 768 or 1024 states wide).  After a
 //              checkpointed E-step ("wide_ckpt") with "wide_decode_ckpt" = 1: its checkpoints and the tiles' last rows instead of X
 //              (the CKPT kernels of the same files; nothing of the table's size is allocated)
 // Every entry point is written once: argument check, decode_source, device scratch of its own (freed before it returns), uploads, a

@@ -1,14 +1,14 @@
 // api_wide_fast.hip -- fast mode beyond 128 states: the factored statistics of psmc_hip_estep_factored[_device] at 129..256
 // states with the option "wide_fast" = 1 or 2 (kernels: estep_wide_fast.hip, one wave per tile) and at 257..1024 states with
-// "wide_fast" = 2 (kernels: estep_wide_fast_mw.hip, 2..4 waves per tile at the padded widths 512, 768 and 1024; plan, rounds and
+// "wide_fast" = 2 (the same kernels at 2..4 waves per tile at the padded widths 512, 768 and 1024; plan, rounds and
 // options are the same, only WideLaunch knows the width and the waves).  With "wide_decode" = 1 the decoding entry points read
-// what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip up to 256 states, estep_wide_post_mw.hip beyond).  Everything else a context of that size does --
+// what such an E-step left (api_decode.hip; kernels: estep_wide_post.hip).  Everything else a context of that size does --
 // psmc_hip_estep without "wide_counts", the batch without "wide_batch" (with it: api_batch.hip batch_wide calls estep_factored_wide once per replicate),
 // psmc_hip_get_tables, decoding without "wide_decode" or after an exact E-step -- stays on the wide exact kernels, and this path does not touch their tables: it keeps its own X table (8 S bytes per bin) and scale factors.
 // "wide_ckpt" = 1: X at every 8th position only (S bytes per bin) plus every tile's last row, the accumulate sweep recomputes the rest
 // (estep_wide_fast.hip); "wide_decode" = 1 wins, because the full-table decoding kernels read every row -- unless "wide_decode_ckpt" = 1:
 // then the table does not depend on "wide_decode", and decoding recomputes the rows between the checkpoints as the accumulate sweep
-// does (the CKPT kernels of estep_wide_post.hip / estep_wide_post_mw.hip).  The table is sized anew when the interval
+// does (the CKPT kernels of estep_wide_post.hip).  The table is sized anew when the interval
 // changes between two E-steps, and what ran is recorded for fast_info, psmc_hip_wide_table_info and decode_source.
 //
 // "wide_counts" = 1: psmc_hip_estep of such a context (and, with "wide_batch", the batch asked for A) runs the factored E-step below with

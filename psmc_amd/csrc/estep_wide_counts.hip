@@ -6,11 +6,10 @@
 //   A[k][l] = a[k][l] C[k][l],   C[k][l] = sum_p X_p(k) V_p(l),   V_p(l) = mult bt_{p+1}(l) / G_p,   G_p = sum_k X_p(k) (a bt_{p+1})(k)
 // over the positions p = 1 .. L - 1 of every selected segment (position L owns no transition), so every transition adds exactly
 // mult to the sum of A.  No S x S accumulator lives inside a sweep: the pass is cut into slabs of whole tiles in plan order, and per slab
-//   k_wc_v / k_mwc_v   one more backward sweep per tile from bentry -- the steps of k_wf_acc / k_mw_acc (as k_wp_dec / k_mwp_dec of
-//                      the decoding files), so the E-step's own bt -- that writes V_p for p = lo .. min(hi, L - 1) into the slab's
-//                      V rows (8 S bytes per position; a tile that holds only position L writes nothing).  One wave per tile at
-//                      S = 192 / 256, one work-group of W = 2, 3, 4 waves at S = 256 W; the hang rule of estep_wide_post_mw.hip
-//                      holds: `top < lo` and the loop bounds come from the tile descriptor alone.
+//   k_wc_v             one more backward sweep per tile from bentry -- the backward step of the E-step (wide_prims.h bstep_parts,
+//                      as k_wp_dec of estep_wide_post.hip), so the E-step's own bt -- that writes V_p for p = lo .. min(hi, L - 1)
+//                      into the slab's V rows (8 S bytes per position; a tile that holds only position L writes nothing).  A
+//                      tile is one work-group of W waves as in the E-step: one wave at S = 192 / 256, W = 2, 3, 4 at S = 256 W.
 //   k_wc_gemm          C += X^T V on v_mfma_f64_16x16x4 (lane (t, i) supplies A[M = i][K = t] and B[K = t][N = i]; result q of the
 //                      lane is D[t + 4 q][i]: estep_fused.hip).  M = N = S, a multiple of 64: one wave owns a 64 x 64 block (4 x 4
 //                      instructions per four rows of K).  K is a list of row ranges (KRange: where the rows start in X and in the
@@ -25,10 +24,10 @@
 // The ranges, the slabs and n_split are functions of the plan and the options alone (api_wide_fast.hip plan_counts): the result
 // does not depend on the device, on timing or on earlier calls.
 //
-// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; scratch is 0 everywhere; LDS in bytes per work-group):
-//   kernel          S=192: VGPRs  LDS    S=256: VGPRs  LDS    S=512 (W=2)   S=768 (W=3)   S=1024 (W=4)
-//   k_wc_v                  100    0             124    0
-//   k_mwc_v                                                  126  192      130  288      134  384
+// Resources (hipcc -O3, gfx950, make resources; scratch is 0 everywhere).  k_wc_v per shape (NPL, W): VGPRs | LDS bytes per
+// work-group | waves per SIMD:
+//   kernel                               (3,1) S=192      (4,1) S=256      (4,2) S=512      (4,3) S=768      (4,4) S=1024
+//   k_wc_v                                   98     0 4      126     0 4      128   192 4      136   288 3      140   384 3
 //   k_wc_gemm       162 .. 164 VGPRs (of them 128 accumulators; no AGPRs) at every width, no LDS: three waves per SIMD
 //                   (amdgpu_waves_per_eu(2): without it the compiler takes 134 VGPRs + 128 AGPRs, one wave per SIMD)
 //   k_wc_finish     8 VGPRs, no LDS
@@ -38,84 +37,31 @@
 #include <hip/hip_runtime.h>
 #include "wide_fast.h"
 #include "wide_prims.h"
-#include "wide_mw_prims.h"
 
 namespace psmc {
 namespace wide {
 
 typedef double d4c_t __attribute__((ext_vector_type(4)));
 
-// Tile t0 + blockIdx.x of the plan; its V rows start at row vrow[b] of the slab (position lo first).
-template <int NPL>
-__global__ __launch_bounds__(64) void k_wc_v(const double *__restrict__ par, const uint8_t *__restrict__ obs,
-                                               const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
-                                               const double *__restrict__ bentry, const int32_t *__restrict__ vrow,
-                                               double *__restrict__ V)
+// Tile t0 + blockIdx.x of the plan; its V rows start at row vrow[b] of the slab (position lo first).  The tile is one work-group of
+// W waves (wide_prims.h).  Two exchanges per position (the step's own, and G), reached by every wave: `top < lo`, the loop bounds
+// and `p > top || p < lo` come from the tile descriptor and the loop counters.
+template <int NPL, int W>
+__global__ __launch_bounds__(64 * W) void k_wc_v(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                   const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
+                                                   const double *__restrict__ bentry, const int32_t *__restrict__ vrow,
+                                                   double *__restrict__ V)
 {
-	constexpr int S = 64 * NPL;
-	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
-	const WaveScanMasks wm = wave_scan_masks(lane);
-	const Chunk c = chunks[b];
-	const int lo = c.lo, top = min(c.hi, c.L - 1);
-	if (top < lo) return; // the tile holds position L only: no transition
-	StructParN<NPL> sc;
-	load_par<NPL>(par, k0, false, sc);
-	double e0[NPL], e1[NPL];
-	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
-	const double mult = (double)c.mult;
-	const uint8_t *o = obs + c.off;
-	const double *fo = X + c.off * S + k0;
-	double *vo = V + (int64_t)vrow[b] * S + k0;
-	double x[NPL], Xc[NPL], Xn[NPL];
-	ld<NPL>(bentry + (int64_t)b * S + k0, x);
-	ld<NPL>(fo + (int64_t)(top - 1) * S, Xc);
-	for (int g4 = (top - 1) >> 2; g4 >= 0 && 4 * g4 + 4 >= lo; --g4) {
-		const unsigned w = *reinterpret_cast<const unsigned *>(o + 4 * (int64_t)g4);
-#pragma unroll
-		for (int j = 3; j >= 0; --j) {
-			const int p = 4 * g4 + j + 1;
-			if (p > top || p < lo) continue;
-			if (p > lo) ld<NPL>(fo + (int64_t)(p - 2) * S, Xn); // X_{p-1}, for the next step
-			double ev[NPL], y[NPL], g[NPL];
-			emis<NPL>((int)((w >> (8 * j)) & 3u), e0, e1, ev);
-			if (j == 3) { // p % 4 == 0: the backward sweep's own scaling, as bstep
-				const double sb = rcp_newton(wave_total(lsum<NPL>(x)));
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) ev[i] *= sb;
-			}
-#pragma unroll
-			for (int i = 0; i < NPL; ++i) y[i] = x[i];
-			wstep<NPL>(sc, y, wm); // (a bt_{p+1})
-#pragma unroll
-			for (int i = 0; i < NPL; ++i) g[i] = Xc[i] * y[i];
-			const double s = mult * rcp_newton(wave_total(lsum<NPL>(g)));
-#pragma unroll
-			for (int i = 0; i < NPL; ++i) { g[i] = x[i] * s; x[i] = y[i] * ev[i]; }
-			st<NPL>(vo + (int64_t)(p - lo) * S, g);
-#pragma unroll
-			for (int i = 0; i < NPL; ++i) Xc[i] = Xn[i];
-		}
-	}
-}
-
-// The same at 257..1024 states: the tile is one work-group of W waves.  Two exchanges per position (the step's own, and G), reached
-// by every wave: `top < lo`, the loop bounds and `p > top || p < lo` come from the tile descriptor and the loop counters.
-template <int W>
-__global__ __launch_bounds__(64 * W) void k_mwc_v(const double *__restrict__ par, const uint8_t *__restrict__ obs,
-                                                    const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
-                                                    const double *__restrict__ bentry, const int32_t *__restrict__ vrow,
-                                                    double *__restrict__ V)
-{
-	constexpr int NPL = MW_NPL, S = 64 * NPL * W;
-	__shared__ double xs[2 * MW_SLOTS * W];
-	Xchg<W> xc = mw_xchg<W>(xs);
+	constexpr int S = 64 * NPL * W;
+	__shared__ double xs[2 * WX_SLOTS * W];
+	Xchg<W> xc = make_xchg<W>(xs);
 	const int tid = threadIdx.x, k0 = NPL * tid, b = t0 + (int)blockIdx.x;
 	const WaveScanMasks wm = wave_scan_masks(xc.lane);
 	const Chunk c = chunks[b];
 	const int lo = c.lo, top = min(c.hi, c.L - 1);
-	if (top < lo) return; // (the same in every wave)
+	if (top < lo) return; // the tile holds position L only: no transition (the same in every wave)
 	StructParN<NPL> sc;
-	mw_load_bwd<S>(par, k0, sc);
+	load_par<NPL, S>(par, k0, false, sc);
 	double e0[NPL], e1[NPL];
 	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
 	const double mult = (double)c.mult;
@@ -132,20 +78,14 @@ __global__ __launch_bounds__(64 * W) void k_mwc_v(const double *__restrict__ par
 			const int p = 4 * g4 + j + 1;
 			if (p > top || p < lo) continue; // (the same in every wave)
 			if (p > lo) ld<NPL>(fo + (int64_t)(p - 2) * S, Xn); // X_{p-1}, for the next step
-			double ev[NPL], y[NPL], g[NPL];
-			emis<NPL>((int)((w >> (8 * j)) & 3u), e0, e1, ev);
-#pragma unroll
-			for (int i = 0; i < NPL; ++i) y[i] = x[i];
-			// y <- a bt_{p+1}; p % 4 == 0: the backward sweep's own scaling 1 / sum(bt_{p+1}), as mw_bstep
-			const double tot = j == 3 ? mw_step<W, true>(sc, y, wm, xc) : mw_step<W, false>(sc, y, wm, xc);
-			if (j == 3) {
-				const double sb = rcp_newton(tot);
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) ev[i] *= sb;
-			}
+			double ev[NPL], y[NPL], g[NPL], none = 0.0;
+			// y = a bt_{p+1}; p % 4 == 0: the backward sweep's own scaling 1 / sum(bt_{p+1}) in ev
+			const int sym = (int)((w >> (8 * j)) & 3u);
+			if (j == 3) bstep_parts<NPL, W, true, false>(sc, wm, sym, e0, e1, x, y, ev, xc, none);
+			else bstep_parts<NPL, W, false, false>(sc, wm, sym, e0, e1, x, y, ev, xc, none);
 #pragma unroll
 			for (int i = 0; i < NPL; ++i) g[i] = Xc[i] * y[i];
-			const double s = mult * rcp_newton(mw_vsum<W>(xc, g)); // exchanged values only: the same bits in every wave
+			const double s = mult * rcp_newton(tile_vsum<NPL, W>(xc, g)); // exchanged values only: the same bits in every wave
 #pragma unroll
 			for (int i = 0; i < NPL; ++i) { g[i] = x[i] * s; x[i] = y[i] * ev[i]; }
 			st<NPL>(vo + (int64_t)(p - lo) * S, g);
@@ -222,11 +162,11 @@ __global__ __launch_bounds__(256) void k_wc_finish(const double *__restrict__ P,
 
 template <int S> static int launch_counts(const WideCounts &w, int what)
 {
+	constexpr int WV = S <= 256 ? 1 : S / 256; // waves per tile of k_wc_v
 	hipStream_t st = w.stream;
 	switch (what) {
 	case WC_V:
-		if constexpr (S <= 256) hipLaunchKernelGGL(k_wc_v<S / 64>, dim3(w.n_tiles), dim3(64), 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.bentry, w.vrow, w.V);
-		else hipLaunchKernelGGL(k_mwc_v<S / 256>, dim3(w.n_tiles), dim3(S / 4), 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.bentry, w.vrow, w.V);
+		hipLaunchKernelGGL((k_wc_v<S / (64 * WV), WV>), dim3(w.n_tiles), dim3(64 * WV), 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.bentry, w.vrow, w.V);
 		break;
 	case WC_GEMM:
 		hipLaunchKernelGGL(k_wc_gemm<S>, dim3((S / 64) * (S / 64), w.n_split), dim3(64), 0, st, w.X, w.V, w.kr, w.n_kr, w.n_split, w.first, w.P);

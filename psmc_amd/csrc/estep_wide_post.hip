@@ -1,42 +1,51 @@
-// estep_wide_post.hip -- decoding on the wide fast path (129..256 states, options "wide_fast" + "wide_decode"; api_decode.hip
+// estep_wide_post.hip -- decoding on the wide fast path (129..1024 states, options "wide_fast" + "wide_decode"; api_decode.hip
 // drives it): psmc_hip_decode / _posterior / _post_counts / _scales from what the last wide fast E-step left, without a backward table.
 //
 // The E-step keeps the lag-normalised forward table X (and 1/d_p at p % 4 == 0), every tile's forward start vector `entry` and its
 // backward start vector bentry = bt_{top+1}, converged to "warm_tol" by the verify / repair rounds.  One more backward sweep per
-// tile from bentry -- the steps of k_wf_acc, so the bt of the E-step -- gives at every position p, with y = a bt_{p+1} (O(N)),
+// tile from bentry -- bstep_parts of wide_prims.h, the step of k_wf_bwarm, with the scaling of k_wf_acc, so the bt of the E-step --
+// gives at every position p, with y = a bt_{p+1} (O(N)),
 //   g_p(k) = X_p(k) y(k),  G_p = sum_k g_p(k):  posterior gamma_p(k) = g_p(k) / G_p  (what E0 / E1 of the E-step add up; no division
 //            by an emission, so zero emissions and padded states are no special case),
 //   recomb_p = 1 - sum_l X_p(l) a_ll bt_{p+1}(l) / G_p  (aux.c:189-193),  and at p = L: gamma_L = X_L / sum X_L, recomb_L = 0.
-// One wave per tile, 64 lanes x NPL adjacent states as in estep_wide_fast.hip (wide_prims.h).  Nothing of 8 S bytes per bin is
-// written: only what was asked for (template flags) -- -d moves 12 bytes per bin.  Posterior rows have stride n; padded states
-// are never written, and a tile writes the positions lo .. hi it owns and nothing else.
+// A tile is one work-group of W waves, thread t holds the states NPL t .. NPL t + NPL - 1, as in estep_wide_fast.hip (wide_prims.h:
+// the exchange between the waves and the hang rule, which holds here -- see k_wp_dec).  Nothing of 8 S bytes per bin is written:
+// only what was asked for (template flags) -- -d moves 12 bytes per bin.  Posterior rows have stride n; padded states are never
+// written, and a tile writes the positions lo .. hi it owns and nothing else.
 //   k_wp_dec     the sweep: posterior rows | recombination | argmax (lowest state wins a tie) and its value | per-tile partial
-//                posterior-weighted counts, CB count columns per sweep
-//   k_wp_cnt_add the tiles' partials added in tile order (deterministic); also at the widths 512 / 768 / 1024 of estep_wide_post_mw.hip
-//   k_wp_scales  s_p = sum X_p / sum X_{p-1} / inv_p from X alone (X_{lo-1}: the tile's own `entry`), s_1 = sum_k a0_k e_k(o_1)
+//                posterior-weighted counts, CB count columns per sweep.  Two exchanges per position: the step's own, in which
+//                r = sum X a_kk bt_{p+1} rides (it does not depend on y), and one for G and, for the path, every wave's maximum
+//                and the state that holds it (an index up to 1023 is exact in a double).  iG comes from exchanged values only:
+//                the same bits in every wave.  Position L: one exchange.
+//   k_wp_cnt_add the tiles' partials added in tile order (deterministic)
+//   k_wp_scales  s_p = sum X_p / sum X_{p-1} / inv_p from X alone (X_{lo-1}: the tile's own `entry`), s_1 = sum_k a0_k e_k(o_1).
+//                ONE wave per tile at every width adds the W blocks of 64 NPL states of a row, lowest block first: no LDS, no barrier
 //
-// "wide_decode_ckpt" (compile-time variants CKPT of k_wp_dec, and k_wp_scales_ck; the full-table kernels keep their code): after a
-// "wide_ckpt" E-step X holds the rows at p % 8 == 0 only (wide_prims.h ckpt_row) and xhi[b] every tile's last row.  k_wp_dec CKPT
-// sweeps the tile in blocks of eight positions, the top block first, recomputing the block's rows forward into LDS with fstep --
-// the forward sweep's own step and its stored scale factors, as k_wf_acc CKPT of estep_wide_fast.hip -- and then runs the same
-// backward step and emit over them; k_wp_scales_ck makes one forward pass per tile.  The same bits as from the full table.
+// "wide_decode_ckpt" (compile-time variants CKPT of k_wp_dec, and k_wp_scales_ck): after a "wide_ckpt" E-step X holds the rows at
+// p % 8 == 0 only (wide_prims.h ckpt_row) and xhi[b] every tile's last row.  k_wp_dec CKPT sweeps the tile in blocks of eight
+// positions, the top block first, recomputing the block's rows forward into LDS with fstep -- the forward sweep's own step and its
+// stored scale factors, as k_wf_acc CKPT of estep_wide_fast.hip -- and then runs the same backward step and emit over them;
+// k_wp_scales_ck makes one forward pass per tile, all W waves, and sums every row through the exchange, lowest block first -- the
+// order of k_wp_scales.  The same bits as from the full table.
 //
-// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; scratch is 0 everywhere; LDS in bytes per wave):
-//   kernel                            S=192: VGPRs  LDS     S=256: VGPRs  LDS
-//   k_wp_dec  path                            98    0              122    0
-//   k_wp_dec  posterior                       96    0              122    0
-//   k_wp_dec  recombination                  106    0              134    0
-//   k_wp_dec  posterior + recomb.            106    0              136    0
-//   k_wp_dec  counts                         118    0              152    0
-//   k_wp_dec  path, CKPT                     102    10752          126    14336
-//   k_wp_dec  posterior, CKPT                 92    10752          116    14336
-//   k_wp_dec  recombination, CKPT            104    10752          132    14336
-//   k_wp_dec  posterior + recomb., CKPT      104    10752          132    14336
-//   k_wp_dec  counts, CKPT                   116    10752          148    14336
-//   k_wp_scales / k_wp_scales_ck         16 / 80    0         16 / 102    0
-//   k_wp_cnt_add                               8    0 (every width)
-// With CKPT the staged rows bound a compute unit at 15 waves (192 states) or 11 (256) of its 160 KB of LDS, where the registers alone
-// allow 16 and 12 to 16, as without CKPT.
+// Resources (hipcc -O3, gfx950, make resources; scratch is 0 everywhere).  Per shape (NPL, W): VGPRs | LDS bytes per work-group |
+// waves per SIMD.  LDS = the exchange slots, 2 x 6 x W doubles at W > 1, plus with CKPT 7 rows of S doubles in k_wp_dec.
+//   kernel                               (3,1) S=192      (4,1) S=256      (4,2) S=512      (4,3) S=768      (4,4) S=1024
+//   k_wp_dec  path                           98     0 4      122     0 4      124   192 4      128   288 4      132   384 3
+//   k_wp_dec  path, CKPT                    102 10752 4      124 14336 3      136 28864 3      132 43296 3      136 57728 2
+//   k_wp_dec  posterior                      96     0 5      122     0 4      124   192 4      128   288 4      130   384 3
+//   k_wp_dec  posterior, CKPT                92 10752 4      116 14336 3      118 28864 3      124 43296 3      128 57728 2
+//   k_wp_dec  recombination                 100     0 4      126     0 4      130   192 3      134   288 3      138   384 3
+//   k_wp_dec  recombination, CKPT           102 10752 4      128 14336 3      130 28864 3      134 43296 3      136 57728 2
+//   k_wp_dec  posterior + recomb.           102     0 4      130     0 3      132   192 3      136   288 3      138   384 3
+//   k_wp_dec  posterior + recomb., CKPT     102 10752 4      128 14336 3      130 28864 3      134 43296 3      136 57728 2
+//   k_wp_dec  counts                        118     0 4      152     0 3      156   192 3      160   288 3      162   384 3
+//   k_wp_dec  counts, CKPT                  116 10752 4      148 14336 3      150 28864 3      156 43296 3      160 57728 2
+//   k_wp_scales (64 threads)                 16     0 8       16     0 8       22     0 8       30     0 8       40     0 8
+//   k_wp_scales_ck                           80     0 6      102     0 4      106   192 4      110   288 4      112   384 4
+//   k_wp_cnt_add                         8 VGPRs at every width, no LDS
+// With CKPT the staged rows bound a compute unit at 15 tiles (S = 192), 11 (256), five (512), three (768) or two (1024) of its
+// 160 KB of LDS.
 #include <hip/hip_runtime.h>
 #include "wide_fast.h"
 #include "wide_prims.h"
@@ -44,35 +53,51 @@
 namespace psmc {
 namespace wide {
 
-constexpr int CB = 4; // count columns one sweep of k_wp_dec carries (CB x NPL accumulators per lane)
+constexpr int CB = 4; // count columns one sweep of k_wp_dec carries (CB x NPL accumulators per thread)
 
-// what one position hands out: g = unnormalised posterior of the lane's states, G = its sum over the wave, r = sum_l X a_ll bt_{p+1}
-// (last: position L, whose recombination probability is 0)
-template <int NPL, bool POST, bool REC, bool PATH, bool CNT>
-__device__ __forceinline__ void emit(int p, int lane, int n, const double (&g)[NPL], double G, double r, bool last, double *__restrict__ post,
-                                     double *__restrict__ recomb, int32_t *__restrict__ path, double *__restrict__ maxp,
-                                     const int32_t *__restrict__ cnt1, int n_cnt, int j0, int min_l, double (&acc)[CB][NPL])
+// what one position hands out: g = unnormalised posterior of the thread's states, r = sum_l X a_ll bt_{p+1} over the TILE (from the
+// step's exchange), last: position L, whose recombination probability is 0.  One exchange (G; PATH: the waves' maxima); every wave
+// of the tile calls it.  The tie rule of the path: within a wave the lowest state of the lowest lane that holds the wave's
+// maximum, across waves the lowest wave whose maximum equals the tile's -- the lowest state wins (a NaN: wave 0's, lane 0's).
+template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT>
+__device__ __forceinline__ void emit(int p, int tid, int n, const double (&g)[NPL], double r, bool last, Xchg<W> &xc,
+                                     double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
+                                     double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0, int min_l,
+                                     double (&acc)[CB][NPL])
 {
-	const int k0 = NPL * lane;
-	const double iG = rcp_newton(G);
+	const int k0 = NPL * tid;
+	xc.put(0, wave_total(lsum<NPL>(g)));
+	if (PATH) { // the wave's first maximum: the lowest i of the lane, then the lowest lane that holds the wave's maximum
+		double best = g[0]; int arg = 0;
+#pragma unroll
+		for (int i = 1; i < NPL; ++i)
+			if (g[i] > best) { best = g[i]; arg = i; }
+		const double wtop = wave_maxv(best);
+		const unsigned long long who = __ballot(best == wtop);
+		const int src = who ? __ffsll((long long)who) - 1 : 0;
+		const int k = __shfl(k0 + arg, src, 64);
+		xc.put(1, wtop); xc.put(2, (double)k);
+	}
+	xc.sync();
+	const double iG = rcp_newton(xc.sum(0));
+	double top = 0.0, ktop = 0.0;
+	if (PATH) { // the lowest wave whose maximum is the tile's
+		top = xc.vmax(1);
+		ktop = xc.get(2, 0);
+#pragma unroll
+		for (int w = W - 1; w >= 1; --w)
+			if (xc.get(1, w) == top) ktop = xc.get(2, w);
+		if (xc.get(1, 0) == top) ktop = xc.get(2, 0); // (no wave's maximum equals it -- a NaN: wave 0's)
+	}
+	xc.next();
 	if (POST) {
 		double *row = post + (int64_t)(p - 1) * n;
 #pragma unroll
 		for (int i = 0; i < NPL; ++i)
 			if (k0 + i < n) row[k0 + i] = g[i] * iG;
 	}
-	if (REC && lane == 0) recomb[p - 1] = last ? 0.0 : 1.0 - r * iG;
-	if (PATH) { // the first maximum: the lowest i of the lane, then the lowest lane that holds the wave's maximum
-		double best = g[0]; int arg = 0;
-#pragma unroll
-		for (int i = 1; i < NPL; ++i)
-			if (g[i] > best) { best = g[i]; arg = i; }
-		const double top = wave_maxv(best);
-		const unsigned long long who = __ballot(best == top);
-		const int src = who ? __ffsll((long long)who) - 1 : 0;
-		const int k = __shfl(k0 + arg, src, 64);
-		if (lane == 0) { path[p - 1] = k; maxp[p - 1] = top * iG; }
-	}
+	if (REC && tid == 0) recomb[p - 1] = last ? 0.0 : 1.0 - r * iG;
+	if (PATH && tid == 0) { path[p - 1] = (int32_t)ktop; maxp[p - 1] = top * iG; }
 	if (CNT && p <= min_l) {
 		const int32_t *c1 = cnt1 + (int64_t)(p - 1) * n_cnt + j0;
 #pragma unroll
@@ -84,30 +109,54 @@ __device__ __forceinline__ void emit(int p, int lane, int n, const double (&g)[N
 	}
 }
 
+// the backward step of one position p of the sweep: x = bt_{p+1} -> bt_p (bstep_parts: the E-step's backward step), Xc = X_p; g and
+// r for emit.  One exchange, in which r rides: a wave's share goes in and the tile's sum comes back.
+template <int NPL, int W, bool NORM, bool REC>
+__device__ __forceinline__ void dstep(const StructParN<NPL> &sc, const WaveScanMasks &wm, int sym, const double (&e0)[NPL],
+                                      const double (&e1)[NPL], const double (&akk)[NPL], const double (&Xc)[NPL], double (&x)[NPL],
+                                      double (&g)[NPL], double &r, Xchg<W> &xc)
+{
+	double y[NPL], ev[NPL];
+	r = 0.0;
+	if (REC) {
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) r = __builtin_fma(Xc[i] * akk[i], x[i], r);
+		r = wave_total(r);
+	}
+	bstep_parts<NPL, W, NORM, REC>(sc, wm, sym, e0, e1, x, y, ev, xc, r);
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) { g[i] = Xc[i] * y[i]; x[i] = y[i] * ev[i]; }
+}
+
 // Tile t0 + blockIdx.x of the plan (the tiles of one segment are consecutive).  Output pointers are the SEGMENT's (position 1 first).
 // CNT: part[(blockIdx.x * n_cnt + j) * S + k] for the columns j0 .. j0 + CB - 1 that exist.
 // CKPT ("wide_decode_ckpt" after a "wide_ckpt" E-step): X holds the rows at p % 8 == 0 only.  As k_wf_acc CKPT (estep_wide_fast.hip) the
 // tile is swept in blocks of the positions 8m .. 8m+7, the top block first: the block's rows are recomputed forward with fstep and
-// the stored scale factors -- the forward sweep's own bits -- from the checkpoint X_{8m}, or in the tile's lowest block from
-// entry[b] or from X_1 = a0 e[o_1], into LDS (7 S doubles; every lane reads back what it wrote itself, so no barrier); then the
-// backward step and emit of the full-table sweep run over them, highest position first, X_{8m} read from the table.  X_L: xhi[b].
-// With CNT every sweep of CB columns recomputes the rows again.
-template <int NPL, bool POST, bool REC, bool PATH, bool CNT, bool CKPT>
-__global__ __launch_bounds__(64) void k_wp_dec(const double *__restrict__ par, const uint8_t *__restrict__ obs,
-                                                 const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
-                                                 const double *__restrict__ inv, const double *__restrict__ entry,
-                                                 const double *__restrict__ xhi, const double *__restrict__ bentry, int n,
-                                                 double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
-                                                 double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0,
-                                                 int min_l, double *__restrict__ part)
+// the stored scale factors -- the forward sweep's own bits, every recomputed step's exchange as k_wf_fwd does it -- from the
+// checkpoint X_{8m}, or in the tile's lowest block from entry[b] or from X_1 = a0 e[o_1], into LDS (7 S doubles beside the exchange
+// slots; every thread reads back what it wrote itself, so no barrier); then dstep and emit run over them, highest position first, X_{8m}
+// read from the table.  X_L: xhi[b].  With CNT every sweep of CB columns recomputes the rows again.
+// The hang rule: the branches that enclose an exchange are `c.hi == c.L` and `top >= lo` (the tile descriptor), the bounds of the
+// loops (top, lo, the block bounds q, pb, pe), `p > top || p < lo`, `q >= lo`, `lo > 1` and `p & 3` (the loop counters) and the
+// template flags -- the same in every wave.
+template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool CKPT>
+__global__ __launch_bounds__(64 * W) void k_wp_dec(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                     const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
+                                                     const double *__restrict__ inv, const double *__restrict__ entry,
+                                                     const double *__restrict__ xhi, const double *__restrict__ bentry, int n,
+                                                     double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
+                                                     double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0,
+                                                     int min_l, double *__restrict__ part)
 {
-	constexpr int S = 64 * NPL;
-	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
-	const WaveScanMasks wm = wave_scan_masks(lane);
+	constexpr int S = 64 * NPL * W;
+	__shared__ double xs[2 * WX_SLOTS * W];
+	Xchg<W> xc = make_xchg<W>(xs);
+	const int tid = threadIdx.x, k0 = NPL * tid, b = t0 + (int)blockIdx.x;
+	const WaveScanMasks wm = wave_scan_masks(xc.lane);
 	const Chunk c = chunks[b];
 	const int lo = c.lo, top = min(c.hi, c.L - 1);
 	StructParN<NPL> sc;
-	load_par<NPL>(par, k0, false, sc);
+	load_par<NPL, S>(par, k0, false, sc);
 	double e0[NPL], e1[NPL], akk[NPL], acc[CB][NPL];
 	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
 #pragma unroll
@@ -118,10 +167,12 @@ __global__ __launch_bounds__(64) void k_wp_dec(const double *__restrict__ par, c
 		for (int i = 0; i < NPL; ++i) acc[j][i] = 0.0;
 	const uint8_t *o = obs + c.off;
 	const double *fo = X + c.off * S + k0;
+#define WP_EMIT(p, g, r, last) \
+	emit<NPL, W, POST, REC, PATH, CNT>(p, tid, n, g, r, last, xc, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc)
 	if (c.hi == c.L) { // position L: beta_L = 1
 		double g[NPL];
 		if (CKPT) ld<NPL>(xhi + (int64_t)b * S + k0, g); else ld<NPL>(fo + (int64_t)(c.L - 1) * S, g);
-		emit<NPL, POST, REC, PATH, CNT>(c.L, lane, n, g, wave_total(lsum<NPL>(g)), 0.0, true, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc);
+		WP_EMIT(c.L, g, 0.0, true);
 	}
 	if (CKPT && top >= lo) {
 		__shared__ double rows[(WCK - 1) * S];
@@ -149,31 +200,18 @@ __global__ __launch_bounds__(64) void k_wp_dec(const double *__restrict__ par, c
 				}
 				for (; p <= pe; ++p) {
 					const int sym = (int)o[p - 1] & 3;
-					if ((p & 3) == 0) fstep<NPL, true, true>(fs, wm, sym, e0, e1, xf, io[p - 1]);
-					else fstep<NPL, false, true>(fs, wm, sym, e0, e1, xf, 1.0);
+					if ((p & 3) == 0) fstep<NPL, W, true, true>(fs, wm, sym, e0, e1, xf, io[p - 1], xc);
+					else fstep<NPL, W, false, true>(fs, wm, sym, e0, e1, xf, 1.0, xc);
 					st<NPL>(my + ((p & (WCK - 1)) - 1) * S, xf);
 				}
 			}
 			for (int p = pe; p >= pb; --p) {
-				double Xc[NPL], ev[NPL], y[NPL], g[NPL];
+				double Xc[NPL], g[NPL], r;
 				if (p & (WCK - 1)) ld<NPL>(my + ((p & (WCK - 1)) - 1) * S, Xc); else ld<NPL>(X + ckpt_row(c.off, p) * S + k0, Xc);
-				emis<NPL>((int)o[p - 1] & 3, e0, e1, ev);
-				if ((p & 3) == 0) { // the backward sweep's own scaling, as bstep
-					const double sb = rcp_newton(wave_total(lsum<NPL>(x)));
-#pragma unroll
-					for (int i = 0; i < NPL; ++i) ev[i] *= sb;
-				}
-				double r = 0.0;
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) {
-					y[i] = x[i];
-					if (REC) r = __builtin_fma(Xc[i] * akk[i], x[i], r);
-				}
-				wstep<NPL>(sc, y, wm); // (a bt_{p+1})
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) { g[i] = Xc[i] * y[i]; x[i] = y[i] * ev[i]; }
-				if (REC) r = wave_total(r);
-				emit<NPL, POST, REC, PATH, CNT>(p, lane, n, g, wave_total(lsum<NPL>(g)), r, false, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc);
+				const int sym = (int)o[p - 1] & 3;
+				if ((p & 3) == 0) dstep<NPL, W, true, REC>(sc, wm, sym, e0, e1, akk, Xc, x, g, r, xc);
+				else dstep<NPL, W, false, REC>(sc, wm, sym, e0, e1, akk, Xc, x, g, r, xc);
+				WP_EMIT(p, g, r, false);
 			}
 		}
 	}
@@ -186,31 +224,19 @@ __global__ __launch_bounds__(64) void k_wp_dec(const double *__restrict__ par, c
 #pragma unroll
 			for (int j = 3; j >= 0; --j) {
 				const int p = 4 * g4 + j + 1;
-				if (p > top || p < lo) continue;
+				if (p > top || p < lo) continue; // (the same in every wave: both exchanges below are reached by all or none)
 				if (p > lo) ld<NPL>(fo + (int64_t)(p - 2) * S, Xn); // X_{p-1}, for the next step
-				double ev[NPL], y[NPL], g[NPL];
-				emis<NPL>((int)((w >> (8 * j)) & 3u), e0, e1, ev);
-				if (j == 3) { // p % 4 == 0: the backward sweep's own scaling, as bstep
-					const double sb = rcp_newton(wave_total(lsum<NPL>(x)));
-#pragma unroll
-					for (int i = 0; i < NPL; ++i) ev[i] *= sb;
-				}
-				double r = 0.0;
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) {
-					y[i] = x[i];
-					if (REC) r = __builtin_fma(Xc[i] * akk[i], x[i], r);
-				}
-				wstep<NPL>(sc, y, wm); // (a bt_{p+1})
-#pragma unroll
-				for (int i = 0; i < NPL; ++i) { g[i] = Xc[i] * y[i]; x[i] = y[i] * ev[i]; }
-				if (REC) r = wave_total(r);
-				emit<NPL, POST, REC, PATH, CNT>(p, lane, n, g, wave_total(lsum<NPL>(g)), r, false, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc);
+				double g[NPL], r;
+				const int sym = (int)((w >> (8 * j)) & 3u);
+				if (j == 3) dstep<NPL, W, true, REC>(sc, wm, sym, e0, e1, akk, Xc, x, g, r, xc);
+				else dstep<NPL, W, false, REC>(sc, wm, sym, e0, e1, akk, Xc, x, g, r, xc);
+				WP_EMIT(p, g, r, false);
 #pragma unroll
 				for (int i = 0; i < NPL; ++i) Xc[i] = Xn[i];
 			}
 		}
 	}
+#undef WP_EMIT
 	if (CNT) {
 #pragma unroll
 		for (int j = 0; j < CB; ++j)
@@ -229,19 +255,31 @@ __global__ __launch_bounds__(256) void k_wp_cnt_add(const double *__restrict__ p
 	cnt[i] += t;
 }
 
-template <int NPL>
+// one wave per tile; the sum of a row: the W blocks of 64 NPL states, lowest first (every lane holds the same bits)
+template <int NPL, int W> __device__ __forceinline__ double rowsum(const double *__restrict__ row)
+{
+	double u[NPL];
+	ld<NPL>(row, u);
+	double t = wave_total(lsum<NPL>(u));
+#pragma unroll
+	for (int w = 1; w < W; ++w) {
+		ld<NPL>(row + 64 * NPL * w, u);
+		t += wave_total(lsum<NPL>(u));
+	}
+	return t;
+}
+template <int NPL, int W>
 __global__ __launch_bounds__(64) void k_wp_scales(const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
                                                     const double *__restrict__ inv, const double *__restrict__ entry, double *__restrict__ s)
 {
-	constexpr int S = 64 * NPL;
+	constexpr int S = 64 * NPL * W;
 	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
 	const Chunk c = chunks[b];
 	const double *fo = X + c.off * S + k0, *io = inv + c.off;
-	double u[NPL], prev = 1.0;
-	if (c.lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, u); prev = wave_total(lsum<NPL>(u)); }
+	double prev = 1.0;
+	if (c.lo > 1) prev = rowsum<NPL, W>(entry + (int64_t)b * S + k0);
 	for (int p = c.lo; p <= c.hi; ++p) {
-		ld<NPL>(fo + (int64_t)(p - 1) * S, u);
-		const double cur = wave_total(lsum<NPL>(u));
+		const double cur = rowsum<NPL, W>(fo + (int64_t)(p - 1) * S);
 		double v = p == 1 ? cur : cur / prev; // X_1 = a0 e[o_1] as it stands
 		if (p > 1 && (p & (NORM_EVERY - 1)) == 0) v /= io[p - 1];
 		if (lane == 0) s[p - 1] = v;
@@ -249,54 +287,58 @@ __global__ __launch_bounds__(64) void k_wp_scales(const Chunk *__restrict__ chun
 	}
 }
 
-// CKPT: the scales without the table -- one forward pass over the tile from entry[b] (or X_1 = a0 e[o_1], stored as it stands) through
-// fstep with the stored factors: the forward sweep's rows, so the row sums (one wave_total each) and the quotients of k_wp_scales
-template <int NPL>
-__global__ __launch_bounds__(64) void k_wp_scales_ck(const double *__restrict__ par, const uint8_t *__restrict__ obs,
-                                                       const Chunk *__restrict__ chunks, int t0, const double *__restrict__ inv,
-                                                       const double *__restrict__ entry, double *__restrict__ s)
+// CKPT: the scales without the table -- the tile's W waves step forward from entry[b] (or X_1 = a0 e[o_1], stored as it stands) with
+// fstep and the stored factors: the forward sweep's rows.  A row's sum goes through the exchange, which adds the waves' blocks
+// lowest block first -- the order of rowsum.  Two exchanges per position, reached by every wave: the loop bounds come from the
+// tile descriptor alone, and `c.lo > 1` is the same in every wave.
+template <int NPL, int W>
+__global__ __launch_bounds__(64 * W) void k_wp_scales_ck(const double *__restrict__ par, const uint8_t *__restrict__ obs,
+                                                           const Chunk *__restrict__ chunks, int t0, const double *__restrict__ inv,
+                                                           const double *__restrict__ entry, double *__restrict__ s)
 {
-	constexpr int S = 64 * NPL;
-	const int lane = threadIdx.x, k0 = NPL * lane, b = t0 + (int)blockIdx.x;
-	const WaveScanMasks wm = wave_scan_masks(lane);
+	constexpr int S = 64 * NPL * W;
+	__shared__ double xs[2 * WX_SLOTS * W];
+	Xchg<W> xc = make_xchg<W>(xs);
+	const int tid = threadIdx.x, k0 = NPL * tid, b = t0 + (int)blockIdx.x;
+	const WaveScanMasks wm = wave_scan_masks(xc.lane);
 	const Chunk c = chunks[b];
 	StructParN<NPL> fs;
-	load_par<NPL>(par, k0, true, fs);
+	load_par<NPL, S>(par, k0, true, fs);
 	double e0[NPL], e1[NPL], x[NPL], prev;
 	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
 	const uint8_t *o = obs + c.off;
 	const double *io = inv + c.off;
 	int p = c.lo;
-	if (c.lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, x); prev = wave_total(lsum<NPL>(x)); }
+	if (c.lo > 1) { ld<NPL>(entry + (int64_t)b * S + k0, x); prev = tile_vsum<NPL, W>(xc, x); }
 	else {
 		double ev[NPL];
 		ld<NPL>(par + WP_A0 * S + k0, x);
 		emis<NPL>((int)o[0] & 3, e0, e1, ev);
 #pragma unroll
 		for (int i = 0; i < NPL; ++i) x[i] *= ev[i];
-		prev = wave_total(lsum<NPL>(x));
-		if (lane == 0) s[0] = prev;
+		prev = tile_vsum<NPL, W>(xc, x);
+		if (tid == 0) s[0] = prev;
 		p = 2;
 	}
 	for (; p <= c.hi; ++p) {
 		const int sym = (int)o[p - 1] & 3;
 		const bool norm = (p & (NORM_EVERY - 1)) == 0;
-		if (norm) fstep<NPL, true, true>(fs, wm, sym, e0, e1, x, io[p - 1]);
-		else fstep<NPL, false, true>(fs, wm, sym, e0, e1, x, 1.0);
-		const double cur = wave_total(lsum<NPL>(x));
+		if (norm) fstep<NPL, W, true, true>(fs, wm, sym, e0, e1, x, io[p - 1], xc);
+		else fstep<NPL, W, false, true>(fs, wm, sym, e0, e1, x, 1.0, xc);
+		const double cur = tile_vsum<NPL, W>(xc, x);
 		double v = cur / prev;
 		if (norm) v /= io[p - 1];
-		if (lane == 0) s[p - 1] = v;
+		if (tid == 0) s[p - 1] = v;
 		prev = cur;
 	}
 }
 
-template <int NPL, bool CKPT> static int launch_post(const WidePost &w)
+template <int NPL, int W, bool CKPT> static int launch_post(const WidePost &w)
 {
-	const dim3 grid(w.n_tiles), blk(64);
+	const dim3 grid(w.n_tiles), blk(64 * W);
 	hipStream_t st = w.stream;
 #define WP_DEC(POST, REC, PATH, CNT, j0) \
-	hipLaunchKernelGGL((k_wp_dec<NPL, POST, REC, PATH, CNT, CKPT>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.inv, w.entry, w.xhi, \
+	hipLaunchKernelGGL((k_wp_dec<NPL, W, POST, REC, PATH, CNT, CKPT>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.inv, w.entry, w.xhi, \
 	                   w.bentry, w.n_states, w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part)
 	switch (w.what) {
 	case WP_PATH: WP_DEC(false, false, true, false, 0); break;
@@ -308,14 +350,15 @@ template <int NPL, bool CKPT> static int launch_post(const WidePost &w)
 		if (hipGetLastError() != hipSuccess) return -1;
 		return launch_wide_post_cnt_add(w);
 	case WP_SCALES:
-		if (CKPT) hipLaunchKernelGGL(k_wp_scales_ck<NPL>, grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.inv, w.entry, w.s);
-		else hipLaunchKernelGGL(k_wp_scales<NPL>, grid, blk, 0, st, w.chunks, w.t0, w.X, w.inv, w.entry, w.s);
+		if (CKPT) hipLaunchKernelGGL((k_wp_scales_ck<NPL, W>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.inv, w.entry, w.s);
+		else hipLaunchKernelGGL((k_wp_scales<NPL, W>), grid, dim3(64), 0, st, w.chunks, w.t0, w.X, w.inv, w.entry, w.s);
 		break;
 	default: return -1;
 	}
 #undef WP_DEC
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+template <int NPL, int W> static int launch_post(const WidePost &w, bool ck) { return ck ? launch_post<NPL, W, true>(w) : launch_post<NPL, W, false>(w); }
 
 template <int S> static int launch_cnt_add(const WidePost &w)
 {
@@ -341,9 +384,14 @@ int launch_wide_post(const WidePost &w)
 {
 	const bool ck = w.ckpt == wide::WCK; // the E-step kept checkpoints ("wide_ckpt"): X at every 8th position, the tiles' last rows in w.xhi
 	if (w.ckpt != 1 && !(ck && w.xhi)) return -1;
-	if (w.waves > 1) return launch_wide_post_mw(w); // 257..1024 states: estep_wide_post_mw.hip
-	if (w.ns == 192) return ck ? wide::launch_post<3, true>(w) : wide::launch_post<3, false>(w);
-	if (w.ns == 256) return ck ? wide::launch_post<4, true>(w) : wide::launch_post<4, false>(w);
+	if (w.waves > 1 ? w.ns != 256 * w.waves : (w.ns != 192 && w.ns != 256)) return -1;
+	switch (w.ns) {
+	case 192: return wide::launch_post<3, 1>(w, ck);
+	case 256: return wide::launch_post<4, 1>(w, ck);
+	case 512: return wide::launch_post<4, 2>(w, ck);
+	case 768: return wide::launch_post<4, 3>(w, ck);
+	case 1024: return wide::launch_post<4, 4>(w, ck);
+	}
 	return -1;
 }
 

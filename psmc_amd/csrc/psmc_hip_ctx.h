@@ -32,7 +32,7 @@ constexpr int DEC_FAST = 1;   // the fast tables X and bt (dense sweeps, or the 
 constexpr int DEC_EXACT = 2;  // the exact tables (65..128 states, a matrix without the PSMC form: fast mode ran the exact kernels)
 constexpr int DEC_NO_BT = 3;  // the fused or factored back half: no backward table
 constexpr int DEC_MERGED = 4; // the forward fix pass ("merge"): its X carries per-tile factors
-constexpr int DEC_WIDE = 5;   // never stored, decode_source returns it: the tables of the wide fast path ("wide_decode"; 129..256 states: estep_wide_post.hip, 257..1024 with "wide_fast" = 2: estep_wide_post_mw.hip)
+constexpr int DEC_WIDE = 5;   // never stored, decode_source returns it: the tables of the wide fast path ("wide_decode"; estep_wide_post.hip: 129..256 states, 257..1024 with "wide_fast" = 2)
 // psmc_hip_ctx::wd_kind: what the last wide fast E-step of the context left (set in api_wide_fast.hip, read by api_decode.hip decode_source)
 constexpr int WD_NONE = 0;    // there was none, or a batch came after it
 constexpr int WD_OK = 1;      // X, 1/d, entry and a converged bentry of every tile of its plan
@@ -223,7 +223,7 @@ struct psmc_hip_ctx {
 	double dbg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	// fast mode beyond 128 states (api_wide_fast.hip): "wide_fast" = 1 runs psmc_hip_estep_factored[_device] of a fast context with 129..256
 	// states on the kernels of estep_wide_fast.hip, in tables of its own (the exact tables stay what the last exact E-step left);
-	// "wide_fast" = 2: the same, and 257..1024 states on the multi-wave kernels of estep_wide_fast_mw.hip
+	// "wide_fast" = 2: the same, and 257..1024 states on the same kernels with 2..4 waves per tile
 	int wide_fast = 0;
 	bool wf_ran = false;                 // the last fast E-step of this context was one of the wide path (fast_info, fast_diag)
 	std::vector<Chunk> wf_chunks;        // its plan; rebuilt when plan_dirty
@@ -246,7 +246,7 @@ struct psmc_hip_ctx {
 	// and the exact tables are the newer ones; wd_sel: the selection serial it ran with (psmc_hip_select moves sel_serial on)
 	int wide_decode = 0;
 	// "wide_decode_ckpt" = 1: a "wide_ckpt" E-step keeps checkpoints whatever "wide_decode" says, and the decoding entry points read
-	// them (wf_last_iv == 8: the CKPT kernels of estep_wide_post.hip / estep_wide_post_mw.hip recompute the rows between them).  Read
+	// them (wf_last_iv == 8: the CKPT kernels of estep_wide_post.hip recompute the rows between them).  Read
 	// by the E-step (the interval) and again by decode_source at every decoding call
 	int wide_decode_ckpt = 0;
 	int wd_kind = 0; unsigned long long wd_serial = 0, wd_sel = 0, sel_serial = 0;

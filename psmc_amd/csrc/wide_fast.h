@@ -1,7 +1,6 @@
-// wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics, 129..256 states:
-// one wave per tile), of estep_wide_fast_mw.hip (257..1024 states: 2..4 waves per tile), of estep_wide_post.hip (decoding from
-// the tables the one-wave E-step left), of estep_wide_post_mw.hip (decoding from the tables the multi-wave E-step left) and of
-// estep_wide_counts.hip (the full count matrix from those tables, "wide_counts").
+// wide_fast.h -- what api_wide_fast.hip hands the kernels of estep_wide_fast.hip (fast mode, factored statistics: 129..256 states
+// as one wave per tile, 257..1024 states as 2..4 waves per tile), of estep_wide_post.hip (decoding from the tables that E-step
+// left) and of estep_wide_counts.hip (the full count matrix from those tables, "wide_counts").
 #pragma once
 #include <hip/hip_runtime.h>
 #include "psmc_hip_internal.h"
@@ -26,8 +25,7 @@ struct WideLaunch {
 	double *xhi;                      // ckpt == 8: [n_tiles][ns] every tile's last row X_hi (what its neighbour's verify / repair and the LL read)
 };
 
-int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip (waves > 1: hands on to the next)
-int launch_wide_fast_mw(const WideLaunch &w, int what, int n_list);  // estep_wide_fast_mw.hip
+int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip; -1: ns and waves do not go together, or ckpt is not 1 or 8 with xhi
 
 // decoding of ONE segment: its tiles are t0 .. t0 + n_tiles - 1 of the plan; every output pointer is the segment's own buffer
 enum { WP_PATH, WP_POST, WP_REC, WP_POST_REC, WP_COUNTS, WP_SCALES };
@@ -49,8 +47,7 @@ struct WidePost {
 	double *part, *cnt;               // [n_tiles][n_cnt][ns] per-tile partials; [n_states][n_cnt] running totals (in / out)
 };
 
-int launch_wide_post(const WidePost &w);         // estep_wide_post.hip (waves > 1: hands on to the next)
-int launch_wide_post_mw(const WidePost &w);      // estep_wide_post_mw.hip
+int launch_wide_post(const WidePost &w);         // estep_wide_post.hip; refuses as launch_wide_fast
 int launch_wide_post_cnt_add(const WidePost &w); // estep_wide_post.hip: WP_COUNTS, the tiles' partials added in tile order, at every width
 
 // the full count matrix ("wide_counts", estep_wide_counts.hip): per slab of whole tiles WC_V, then WC_GEMM; at the end WC_FINISH

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the factored E-step of the wide fast path ("wide_fast", estep_wide_fast.hip) costs against the wide exact kernels, on the
 30 M-bin genome bench.py builds (psmc_amd/sim.py), at 149, 200 and 256 states (patterns "1+74*2", "100*2", "128*2"), and
--- beyond 256 states with "wide_fast" = 2, the multi-wave kernels of estep_wide_fast_mw.hip -- at 300, 512, 768 and 1024 states
+-- beyond 256 states with "wide_fast" = 2, the same kernels at 2..4 waves per tile -- at 300, 512, 768 and 1024 states
 ("150*2", "128*4", "128*6", "128*8"); --stress takes the stress fixture (tests/golden/stress, 2.2 M bins) instead of the genome:
 
   (a) ms per factored E-step on the wide fast path, parameters moving every step (the host model of psmc_amd.hostlib with
@@ -10,8 +10,8 @@
   (b) ms per E-step of the wide exact kernels (psmc_hip_estep) on the same input and the first parameters (one step after a
       warm-up of the allocations)
   (c) with --cli: wall clock of `psmc -N5 -p "100*2"` on the genome in exact mode and with PSMC_HIP_MODE=fast PSMC_HIP_WIDE=fast
-  (d) with --decode: decoding from the wide fast tables ("wide_decode", estep_wide_post.hip; beyond 256 states "wide_fast" = 2 and
-      the multi-wave kernels of estep_wide_post_mw.hip) -- after a warm-up pass, --repeats
+  (d) with --decode: decoding from the wide fast tables ("wide_decode", estep_wide_post.hip; beyond 256 states "wide_fast" = 2: the
+      same kernels at 2..4 waves per tile) -- after a warm-up pass, --repeats
       passes of each decoding call over ALL segments (decode = -d, recombination only and posterior rows + recombination = -D,
       post_counts with three columns = -c, scales = -s; the posterior rows of the longest segment only unless --full-post: all
       of them are 8 n bytes per bin to the host), min | median | max in ms; and what the same request costs without the option:
@@ -58,7 +58,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PATTERNS = {149: ("1+74*2", 75), 200: ("100*2", 100), 256: ("128*2", 128),
+PATTERNS = {149: ("1+74*2", 75), 150: ("75*2", 75), 200: ("100*2", 100), 256: ("128*2", 128),
             300: ("150*2", 150), 512: ("128*4", 128), 768: ("128*6", 128), 1024: ("128*8", 128)}
 
 

@@ -1,6 +1,6 @@
 """The option "wide_ckpt" = 1: the wide fast E-step (129..1024 states, "wide_fast") keeps its forward table X at every 8th position
 only, plus every tile's last row, and the accumulate sweep recomputes the seven rows between two checkpoints into LDS with the
-forward sweep's own step (fstep / mw_fstep of psmc_amd/csrc/wide_prims.h, wide_mw_prims.h) and its stored scale factors.  The claim
+forward sweep's own step (fstep of psmc_amd/csrc/wide_prims.h) and its stored scale factors.  The claim
 is bit identity with the full-table E-step -- statistics, LL and the repair counters -- so everything the suite establishes about
 the wide path's accuracy carries over; the exact kernels are compared directly as well, at the library's own tolerances (check()
 of tests/test_gpu_wide_fast.py).  Data: short_segs of tests/test_gpu_wide_fast_mw.py, 1661 bins in segments of 1 .. 1000 bins.

@@ -1,8 +1,7 @@
 """The option "wide_decode_ckpt" = 1: decoding from the checkpoints of a "wide_ckpt" wide fast E-step (129..1024 states).  Such an
 E-step keeps X at every 8th position plus every tile's last row even while "wide_decode" is on, and psmc_hip_decode / _posterior /
 _post_counts / _scales recompute the seven rows between two checkpoints into LDS with the forward sweep's own step and its stored
-scale factors (the CKPT variants of k_wp_dec / k_mwp_dec and of the scales kernels: psmc_amd/csrc/estep_wide_post.hip,
-estep_wide_post_mw.hip).  The recomputed rows are the forward sweep's bits (tests/test_gpu_wide_fast_ckpt.py), so the claim is bit
+scale factors (the CKPT variants of k_wp_dec and of the scales kernels: psmc_amd/csrc/estep_wide_post.hip).  The recomputed rows are the forward sweep's bits (tests/test_gpu_wide_fast_ckpt.py), so the claim is bit
 identity with decoding from the full table: context C ("wide_ckpt" + "wide_decode_ckpt") against context F (neither), same tiling.
 The exact kernels are compared directly as well, with compare() of tests/test_gpu_wide_fast_decode.py (the library's tolerances
 for wide decoding, include/psmc_hip.h).  Data: short_segs of tests/test_gpu_wide_fast_mw.py, 1661 bins in 17 segments of 1 .. 1000

@@ -232,7 +232,7 @@ def test_wide_fast_one_bin_segment_alone(hip, golden, wide, key):
     and ended one unit in the last place of the sum (0.93292 / 0.93328) away from the exact sum: LL -0.06943605406361747 against
     -0.06943605406361758 (1.60e-15 relative) at 149 states, -0.06904683892951673 against -0.06904683892951662 (1.61e-15) at 200,
     in either tiling -- log at 0.933 magnifies a relative error 14.4 times; the reference's own sequential sum (khmm.c, the oracle)
-    is off by the same unit.  For a segment of one bin k_wf_ll now adds the products up without rounding (two-sum, wave_total_comp);
+    is off by the same unit.  For a segment of one bin k_wf_ll now adds the products up without rounding (two-sum, tile_total_comp);
     every longer segment keeps the plain sum, and every result of tests/test_gpu_wide_fast.py its bits."""
     a, e, a0 = wide[key + ".a"], wide[key + ".e"], wide[key + ".a0"]
     n = a.shape[0]

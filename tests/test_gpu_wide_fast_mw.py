@@ -1,5 +1,5 @@
-"""Fast mode at 257 .. 1024 hidden states: psmc_hip_estep_factored with the option "wide_fast" = 2 (the multi-wave kernels of
-psmc_amd/csrc/estep_wide_fast_mw.hip: a tile is one work-group of 2, 3 or 4 waves at the padded widths 512, 768 and 1024; the
+"""Fast mode at 257 .. 1024 hidden states: psmc_hip_estep_factored with the option "wide_fast" = 2 (the kernels of
+psmc_amd/csrc/estep_wide_fast.hip at W > 1: a tile is one work-group of 2, 3 or 4 waves at the padded widths 512, 768 and 1024; the
 waves exchange their scan totals through LDS once per position).  References: the exact wide kernels on the same device (which
 the suite pins bit for bit against the reference up to 1024 states), the CPU oracle at 300 states, and a fresh context for the
 bit-for-bit claims.  Gates and tolerances: the ones of tests/test_gpu_wide_fast.py (fast mode's own, tests/test_gpu_estep.py):

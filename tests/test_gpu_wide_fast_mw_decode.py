@@ -1,6 +1,6 @@
 """Decoding on the multi-wave wide fast path: a fast-mode context of 257..1024 states with "wide_fast" = 2 and "wide_decode" = 1
 answers psmc_hip_decode / _posterior / _post_counts / _scales from what its last wide fast factored E-step left (X at the padded
-width 512 / 768 / 1024, 1/d, the tiles' start vectors; no backward table -- psmc_amd/csrc/estep_wide_post_mw.hip).  Every
+width 512 / 768 / 1024, 1/d, the tiles' start vectors; no backward table -- psmc_amd/csrc/estep_wide_post.hip).  Every
 comparison is against an EXACT context given the same parameters and segments, with compare() of
 tests/test_gpu_wide_fast_decode.py: compare_decoding's tolerances, the library's own for fast decoding (include/psmc_hip.h) --
 posterior rows, maxp, recomb 1e-9 absolute; scales 1e-11 relative; post_counts 1e-9 relative on cells >= 1e-6 of the largest;

@@ -1,5 +1,5 @@
 """The `psmc` binary with PSMC_HIP_MODE=fast PSMC_HIP_WIDE=fast-all at 300 states (-p "150*2"): factored E-steps on the multi-wave
-wide fast path (psmc_amd/csrc/estep_wide_fast_mw.hip) against runs of the same binary on the exact kernels, under the bounds of
+wide fast path (psmc_amd/csrc/estep_wide_fast.hip) against runs of the same binary on the exact kernels, under the bounds of
 tests/test_host_cli_wide_fast.py; PSMC_HIP_WIDE=fast and decoding runs of that size stay what they were."""
 import os
 import pytest

@@ -1,6 +1,6 @@
 """`psmc` with PSMC_HIP_MODE=fast PSMC_HIP_WIDE=fast-all PSMC_HIP_DECODE=fast-all at 300 hidden states (-p "150*2"): the EM rounds
 stay on the multi-wave wide fast path and -d / -D / -c / -s decode from its tables (options "wide_fast" = 2 + "wide_decode",
-include/psmc_hip.h; kernels: psmc_amd/csrc/estep_wide_post_mw.hip).  -N0 decodes the starting parameters, so the fast and the
+include/psmc_hip.h; kernels: psmc_amd/csrc/estep_wide_post.hip).  -N0 decodes the starting parameters, so the fast and the
 exact run decode the same model: same lines, numbers within the library's tolerances (to the last printed digit), DC runs
 identical except at near-ties which the exact run's own -D output shows to be ties (compare() of
 tests/test_host_cli_fast_decode.py).  PSMC_HIP_DECODE=fast keeps what it meant beyond 256 states: a fast-mode run on the exact
