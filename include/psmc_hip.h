@@ -121,7 +121,8 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           sized anew when the interval changes between two E-steps of a context (psmc_hip_wide_table_info reports it;
  *                           psmc_hip_fast_info out[5] is 1 after a checkpointed E-step).  "wide_decode" = 1 wins: the decoding kernels
  *                           read full rows, so while it is set a wide fast E-step keeps the full table whatever "wide_ckpt" says
- *                           (PSMC_HIP_ENOMEM as under "wide_fast" when that does not fit) -- set "wide_decode" before the one E-step
+ *                           (PSMC_HIP_ENOMEM as under "wide_fast" when that does not fit; so does a wide-counts E-step -- "wide_counts" --
+ *                           unless "wide_counts_ckpt" = 1) -- set "wide_decode" before the one E-step
  *                           that is decoded, and the EM rounds before it run checkpointed -- or set "wide_decode_ckpt" = 1 as well,
  *                           and that E-step keeps checkpoints too.  Without "wide_decode_ckpt", psmc_hip_decode, _posterior,
  *                           _post_counts and _scales after a checkpointed E-step ("wide_decode" set afterwards, no new E-step) answer
@@ -152,7 +153,7 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           chk = 1.0 as after every fast-mode E-step; PSMC_HIP_ECONVERGE as the factored wide E-step answers it.  The
  *                           result depends on the call's inputs and the options alone -- not on the device, on timing or on earlier
  *                           calls: bit-reproducible.  That E-step keeps the full X table (interval 1) whatever "wide_ckpt" says, as
- *                           "wide_decode" without "wide_decode_ckpt" does: counts from checkpoints are not built.  Device memory the
+ *                           "wide_decode" without "wide_decode_ckpt" does -- unless "wide_counts_ckpt" = 1: counts from checkpoints.  Device memory the
  *                           counts pass adds, whatever the number of bins: one slab of V (8 S bytes per slab bin, S = the padded width;
  *                           auto: at most 4 GB, or one tile if that is longer), the partial matrices (at most 64 MB), a and A (8 n^2 bytes each)
  *                           and one slab's row ranges -- plus four bytes per tile of the plan; PSMC_HIP_ENOMEM with the size in the
@@ -165,9 +166,25 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           covered (PSMC_HIP_ENOTSUP as before); psmc_hip_group_estep reaches the path through its per-shard
  *                           psmc_hip_estep.  With "wide_batch" = 1 the batch returns A this way too (psmc_hip_estep_batch).
  *                           Other values: PSMC_HIP_EINVAL
+ *  "wide_counts_ckpt" 0     1: counts from checkpoints.  A wide-counts E-step ("wide_counts": psmc_hip_estep, the wide fast batch asked for A,
+ *                           every shard of a psmc_hip_group) with "wide_ckpt" = 1 keeps checkpoints -- X at every 8th position plus every
+ *                           tile's last row; interval 8 in psmc_hip_wide_table_info, psmc_hip_fast_info out[5] = 1 -- and the V pass of the
+ *                           counts recomputes the seven rows between two checkpoints with the forward sweep's own arithmetic, block by
+ *                           block as the accumulate sweep does, and writes the slab's X rows beside its V rows; the GEMM reads them
+ *                           through the same row ranges in the same order.  A, E, LL (and the batch's factored sums) are the bits of the
+ *                           full-table wide-counts E-step with the same inputs and options; A0 = zeros, chk = 1.0.  A context that
+ *                           alternates psmc_hip_estep and psmc_hip_estep_factored then keeps one table: nothing is sized anew.  The
+ *                           counts pass follows the interval the E-step kept: "wide_decode" = 1 without "wide_decode_ckpt" still forces
+ *                           the full table, and the counts then read it; with "wide_decode_ckpt" = 1 the E-step keeps checkpoints and a
+ *                           decoding call after it reads them.  Device memory the checkpoint path adds: one X slab of the V slab's size
+ *                           (8 S bytes per slab bin; auto: at most 4 GB, or one tile if that is longer; "wide_counts_slab" bounds both),
+ *                           allocated at the first such E-step; PSMC_HIP_ENOMEM names the buffer and its size.  At 30 M bins and 1024
+ *                           states: 31 GB of X plus up to 8 GB of slabs instead of 246 GB; at 256: 7.7 GB plus up to 8 GB instead of 61 GB.
+ *                           Exact mode, up to 128 states, "wide_fast" = 0, without "wide_ckpt" or without "wide_counts": accepted, no
+ *                           effect.  psmc_hip_estep_device beyond 128 states stays PSMC_HIP_ENOTSUP.  Other values: PSMC_HIP_EINVAL
  *  "wide_counts_slab" 0     bins per slab of that counts pass (whole tiles in plan order; a tile longer than the slab is a slab of its
  *                           own); 0 = auto: 2^29 / S bins (fewer tiles per slab serialise the V pass).  Slabs, row ranges and the split factor are functions of the tile plan and
- *                           this option alone.  Negative: PSMC_HIP_EINVAL
+ *                           this option alone ("wide_counts_ckpt" changes none of them; it adds an X slab of the same rows).  Negative: PSMC_HIP_EINVAL
  *  "merge"         0        1: a forward FIX pass between the forward sweep and the back half (64 states, fused back half): every tile's start
  *                           vector is checked there, and a tile that fails is rewritten from the true vector until its trajectory has the
  *                           direction of the stored one again (the factor between the two parts is kept for the counts and the likelihood) --

@@ -234,6 +234,7 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "wide_ckpt") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_ckpt = (int)v; c->plan_dirty = true; } // api_wide_fast.hip
 	else if (k == "wide_batch") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_batch = (int)v; }
 	else if (k == "wide_counts") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_counts = (int)v; } // api_wide_fast.hip estep_counts_wide
+	else if (k == "wide_counts_ckpt") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_counts_ckpt = (int)v; } // api_wide_fast.hip estep_wide_fast, estep_counts_wide
 	else if (k == "wide_counts_slab") { if (v < 0 || v > 2147483647.0) return PSMC_HIP_EINVAL; c->wide_counts_slab = (int)v; }
 	else if (k == "rep_impl") c->rep_impl = v < 0 ? -1 : (v != 0 ? 1 : 0);
 	else return PSMC_HIP_EINVAL;

@@ -14,6 +14,9 @@
 // "wide_counts" = 1: psmc_hip_estep of such a context (and, with "wide_batch", the batch asked for A) runs the factored E-step below with
 // the full table (it wins over "wide_ckpt" for that E-step, as "wide_decode" does) and then the counts pass of estep_wide_counts.hip
 // -- per slab of whole tiles a V pass and a split-K GEMM on the f64 matrix cores, at the end A = a . C (estep_counts_wide, below).
+// "wide_counts_ckpt" = 1 lifts that as "wide_decode_ckpt" does for decoding: the counts E-step keeps checkpoints when "wide_ckpt" says
+// so (and "wide_decode" does not forbid it), and the V pass recomputes the rows between them and writes the slab's X rows beside its V
+// rows for the GEMM -- the same ranges, the same operands, the same bits.  The counts pass follows the interval the E-step kept.
 //
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
 // of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,
@@ -30,15 +33,15 @@ static constexpr int WF_NACC = 7; // SL SU DG CL CU E0 E1 per tile
 void free_wide_fast(psmc_hip_ctx *c)
 {
 	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
-	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi, c->d_wc_V, c->d_wc_P, c->d_wc_a, c->d_wc_out, c->d_wc_kr, c->d_wc_vrow};
+	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi, c->d_wc_V, c->d_wc_Xs, c->d_wc_P, c->d_wc_a, c->d_wc_out, c->d_wc_kr, c->d_wc_vrow};
 	for (void *q : p) if (q) (void)hipFree(q);
 	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
 	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
 	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
 	c->d_wf_xhi = nullptr; c->wf_xhi_cap = 0; c->wf_rows = 0; c->wf_tab_iv = c->wf_last_iv = 0;
 	c->wf_cap = 0; c->wf_bins = 0;
-	c->d_wc_V = c->d_wc_P = c->d_wc_a = c->d_wc_out = nullptr; c->d_wc_kr = nullptr; c->d_wc_vrow = nullptr;
-	c->wc_v_cap = c->wc_p_cap = c->wc_kr_cap = c->wc_vrow_cap = 0;
+	c->d_wc_V = c->d_wc_Xs = c->d_wc_P = c->d_wc_a = c->d_wc_out = nullptr; c->d_wc_kr = nullptr; c->d_wc_vrow = nullptr;
+	c->wc_v_cap = c->wc_xs_cap = c->wc_p_cap = c->wc_kr_cap = c->wc_vrow_cap = 0;
 }
 
 // rows of the X table over `bins` positions at one row per `iv` positions (iv = 8: the rows at p % 8 == 0, by absolute position)
@@ -149,8 +152,9 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	if ((c->plan_dirty || c->wf_chunks.empty()) && (rc = plan_wide(c))) return rc;
 	const int64_t bins = c->total + 128;
 	// "wide_ckpt": one X row per 8 positions -- unless "wide_decode" is on without "wide_decode_ckpt": the full-table decoding kernels
-	// read every row, so that E-step keeps them; and so does a wide-counts E-step ("wide_counts": the GEMM reads every row)
-	const int iv = c->wide_ckpt && !c->wc_now && (!c->wide_decode || c->wide_decode_ckpt) ? 8 : 1;
+	// read every row, so that E-step keeps them; and so does a wide-counts E-step ("wide_counts": the GEMM reads every row of the
+	// table) -- unless "wide_counts_ckpt" is on: then the counts pass recomputes the rows between the checkpoints slab by slab
+	const int iv = c->wide_ckpt && (!c->wc_now || c->wide_counts_ckpt) && (!c->wide_decode || c->wide_decode_ckpt) ? 8 : 1;
 	const int nt = (int)c->wf_chunks.size();
 	c->wf_last_iv = 0;
 	if (c->wf_bins < bins || c->wf_tab_iv != iv) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins; 8 KB per bin at S = 1024), with "wide_ckpt" S bytes per bin; sized anew when the interval changes, whether it grows or shrinks
@@ -236,7 +240,8 @@ bool counts_go_wide(const psmc_hip_ctx *c, const double *a)
 	return factor_structure(c->n, c->n, a, sp.data());
 }
 
-// The plan of the counts pass, from the tile plan and "wide_counts_slab" alone.  A tile owns the transitions of its positions
+// The plan of the counts pass, from the tile plan and "wide_counts_slab" alone -- `xs`: the GEMM reads X from the slab's own X rows
+// ("wide_counts_ckpt" after a checkpointed E-step), so a range's xrow is its vrow; slabs, ranges, their order and n_split do not depend on it.  A tile owns the transitions of its positions
 // lo .. min(hi, L - 1) -- none when it holds only position L.  Slabs are runs of whole tiles in plan order with at most `slab` rows
 // (a tile longer than that is a slab of its own); auto: 2^29 / S rows, a V slab of 4 GB -- the V pass of a slab is one sweep of
 // a tile's length whatever the number of its tiles (up to the ~3000 waves the device holds), so few tiles per slab serialise it: on the
@@ -252,7 +257,7 @@ struct CountsPlan {
 };
 static constexpr int WC_KC = 256;
 
-static void plan_counts(const psmc_hip_ctx *c, int S, CountsPlan &pl)
+static void plan_counts(const psmc_hip_ctx *c, int S, bool xs, CountsPlan &pl)
 {
 	const int nt = (int)c->wf_chunks.size();
 	const int64_t slab = c->wide_counts_slab > 0 ? c->wide_counts_slab : std::max<int64_t>(1, ((int64_t)1 << 29) / S);
@@ -267,7 +272,7 @@ static void plan_counts(const psmc_hip_ctx *c, int S, CountsPlan &pl)
 			rows = 0;
 		}
 		pl.vrow[b] = (int32_t)rows;
-		for (int r = 0; r < own; r += WC_KC) pl.kr.push_back(KRange{ch.off + ch.lo - 1 + r, (int32_t)(rows + r), std::min(WC_KC, own - r)});
+		for (int r = 0; r < own; r += WC_KC) pl.kr.push_back(KRange{xs ? rows + r : ch.off + ch.lo - 1 + r, (int32_t)(rows + r), std::min(WC_KC, own - r)});
 		rows += own;
 		pl.max_rows = std::max(pl.max_rows, rows);
 	}
@@ -276,10 +281,11 @@ static void plan_counts(const psmc_hip_ctx *c, int S, CountsPlan &pl)
 	pl.n_split = std::max(1, std::min(2048 / ((S / 64) * (S / 64)), pl.max_kr));
 }
 
-// One wide-counts E-step: the factored wide E-step with the full table (its bits: E, LL and the factored statistics), then per slab
+// One wide-counts E-step: the factored wide E-step with the full table, or with checkpoints ("wide_ckpt" + "wide_counts_ckpt") (its bits: E, LL and the factored statistics), then per slab
 // the V pass and the GEMM, then the finish -- all on the context's stream.  Device memory the pass adds, whatever the number of
 // bins: the V slab (at most 8 S max(slab, longest tile) bytes; auto: 4 GB), the partials (n_split S^2 doubles, at most 64 MB),
-// a and A (n^2 doubles each), one slab's ranges (16 bytes per 256 rows) -- and four bytes per tile of the plan.
+// a and A (n^2 doubles each), one slab's ranges (16 bytes per 256 rows) -- and four bytes per tile of the plan.  After a checkpointed
+// E-step (wf_last_iv == 8) one X slab of the V slab's size beside it, allocated at the first such pass.
 int estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, double *A, double *sums, double *E, double *A0,
                       double *LL, double *chk)
 {
@@ -293,7 +299,8 @@ int estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const d
 	const int n = c->n, S = wf_width(c);
 	char msg[320];
 	CountsPlan pl;
-	plan_counts(c, S, pl);
+	const bool ck = c->wf_last_iv == 8; // the interval the E-step above actually kept
+	plan_counts(c, S, ck, pl);
 	const int nt = (int)c->wf_chunks.size(), n_slabs = (int)pl.slab_t0.size() - 1;
 	auto grow = [&](auto **p, size_t &cap, size_t want, const char *what) -> int {
 		if (cap >= want && *p) return 0;
@@ -307,6 +314,7 @@ int estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const d
 		return 0;
 	};
 	if ((rc = grow(&c->d_wc_V, c->wc_v_cap, (size_t)std::max<int64_t>(pl.max_rows, 1) * S, "the V slab"))) return rc;
+	if (ck && (rc = grow(&c->d_wc_Xs, c->wc_xs_cap, (size_t)std::max<int64_t>(pl.max_rows, 1) * S, "the X slab (\"wide_counts_ckpt\")"))) return rc;
 	if ((rc = grow(&c->d_wc_P, c->wc_p_cap, (size_t)pl.n_split * S * S, "the partial matrices"))) return rc;
 	if ((rc = grow(&c->d_wc_kr, c->wc_kr_cap, (size_t)std::max(pl.max_kr, 1), "the K ranges"))) return rc;
 	if ((rc = grow(&c->d_wc_vrow, c->wc_vrow_cap, (size_t)nt, "the tiles' rows"))) return rc;
@@ -318,6 +326,7 @@ int estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const d
 	memset(&w, 0, sizeof(w));
 	w.stream = st; w.ns = S; w.n_states = n; w.waves = wf_waves(c);
 	w.par = c->d_wf_par; w.obs = c->d_obs; w.chunks = c->d_wf_chunks; w.X = c->d_wf_X; w.bentry = c->d_wf_bentry;
+	w.ckpt = ck ? 8 : 1; w.inv = c->d_wf_inv; w.entry = c->d_wf_entry; w.Xs = ck ? c->d_wc_Xs : nullptr;
 	w.vrow = c->d_wc_vrow; w.V = c->d_wc_V; w.kr = c->d_wc_kr; w.n_split = pl.n_split; w.P = c->d_wc_P;
 	w.a = c->d_wc_a; w.out = c->d_wc_out; w.tiny_total = (double)c->sel.size() * HMM_TINY_H;
 	bool first = true;

@@ -256,10 +256,14 @@ struct psmc_hip_ctx {
 	// "wide_counts" = 1: psmc_hip_estep of such a context (fast mode, a size "wide_fast" covers, "structured" on, a matrix of the PSMC
 	// form) runs the factored wide E-step with the full X table and then the counts pass of estep_wide_counts.hip (api_wide_fast.hip
 	// estep_counts_wide); the batch with "wide_batch" takes the wide path when A is asked for, too.  "wide_counts_slab": bins per
-	// slab of that pass, 0 = auto.  wc_now: the E-step under way is one (interval 1 whatever "wide_ckpt" says); wc_ran: the last wide
-	// fast E-step was one (fast_info).  Device memory of the pass: one slab of V, the partial matrices, a, A, the slab's ranges,
-	// and one int per tile
-	int wide_counts = 0, wide_counts_slab = 0;
+	// slab of that pass, 0 = auto.  wc_now: the E-step under way is one (interval 1 whatever "wide_ckpt" says, unless
+	// "wide_counts_ckpt"); wc_ran: the last wide fast E-step was one (fast_info).  Device memory of the pass: one slab of V, the partial
+	// matrices, a, A, the slab's ranges, and one int per tile.
+	// "wide_counts_ckpt" = 1: a wide-counts E-step keeps checkpoints when "wide_ckpt" says so (and "wide_decode" without "wide_decode_ckpt"
+	// does not forbid it); the counts pass follows wf_last_iv: at 8 k_wc_v CKPT recomputes the rows between the checkpoints and
+	// writes the slab's X rows into d_wc_Xs (the V slab's size, allocated at the first such pass), which the GEMM reads
+	int wide_counts = 0, wide_counts_slab = 0, wide_counts_ckpt = 0;
+	double *d_wc_Xs = nullptr; size_t wc_xs_cap = 0;
 	bool wc_now = false, wc_ran = false;
 	double *d_wc_V = nullptr, *d_wc_P = nullptr, *d_wc_a = nullptr, *d_wc_out = nullptr;
 	KRange *d_wc_kr = nullptr; int32_t *d_wc_vrow = nullptr;

@@ -54,7 +54,7 @@ int launch_wide_post_cnt_add(const WidePost &w); // estep_wide_post.hip: WP_COUN
 enum { WC_V, WC_GEMM, WC_FINISH };
 
 // rows of K the GEMM reads: `rows` consecutive positions of one tile, from row xrow of X and row vrow of the slab's V
-struct KRange { int64_t xrow; int32_t vrow, rows; };
+struct KRange { int64_t xrow; int32_t vrow, rows; }; // (ckpt == 8: xrow is the row of the slab's Xs, and equals vrow)
 
 struct WideCounts {
 	hipStream_t stream;
@@ -63,7 +63,10 @@ struct WideCounts {
 	const double *par;                // as WideLaunch
 	const uint8_t *obs;
 	const Chunk *chunks;
-	const double *X, *bentry;         // the full table (interval 1) and the converged start vectors the E-step left
+	int ckpt;                         // as WideLaunch: 1 (X holds every row), or 8 (the E-step kept checkpoints; "wide_counts_ckpt": k_wc_v CKPT recomputes the rows between them)
+	const double *X, *bentry;         // the table the E-step left (ckpt == 1: every row) and its converged start vectors
+	const double *inv, *entry;        // ckpt == 8: the stored scale factors [bins] and every tile's forward start vector [tiles][ns]
+	double *Xs;                       // ckpt == 8: [rows of the largest slab][ns] the slab's X rows, row for row beside V (WC_V writes, WC_GEMM reads them)
 	const int32_t *vrow;              // [tiles of the plan] the tile's first row in its slab's V
 	double *V;                        // [rows of the largest slab][ns]
 	const KRange *kr; int n_kr;       // WC_GEMM: the slab's ranges
@@ -74,6 +77,6 @@ struct WideCounts {
 	double *out;                      // ... and A, [n_states][n_states]
 };
 
-int launch_wide_counts(const WideCounts &w, int what); // estep_wide_counts.hip
+int launch_wide_counts(const WideCounts &w, int what); // estep_wide_counts.hip; -1: ns and waves do not go together, or ckpt is not 1 or 8 with inv, entry and Xs
 
 } // namespace psmc

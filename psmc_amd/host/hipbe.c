@@ -16,6 +16,8 @@ typedef struct {
 	int decoding, on_twin; double *pa, *pe, *pa0;
 	/* the wide fast path is on ("wide_fast" went through psmc_hipbe_set_option) / its tables are what the decoding reads ("wide_decode") */
 	int wide, wide_decode;
+	/* the note about the full-count E-steps on the wide fast path, until the first E-step has run (psmc_hipbe_note_counts) */
+	char *note;
 } hip_be;
 
 /* the per-segment readers go to the context that holds the segment's tables: the exact twin's after a fallback */
@@ -79,6 +81,16 @@ static int exact_once(hip_be *h, const double *a, const double *e, const double 
 	return rc;
 }
 
+/* after the first E-step: the held-back note, and what that E-step kept when it was a counts E-step of the wide fast path */
+static void say_note(hip_be *h, int counts_ok)
+{
+	if (!h->note) return;
+	psmc_hip_ctx *c = h->ctx; int l; int64_t ti[4] = {0, 0, 0, 0};
+	const int ck = counts_ok && (!h->grp || psmc_hip_group_route(h->grp, 0, &c, &l) == 0) && psmc_hip_wide_table_info(c, ti) == 0 && ti[2] == 8;
+	fprintf(stderr, "%s%s\n", h->note, ck ? ", X at every 8th bin" : "");
+	free(h->note); h->note = 0;
+}
+
 static void tri_sums(int n, const double *A, double *sums)
 {
 	memset(sums, 0, sizeof(double) * 5 * (size_t)n);
@@ -110,6 +122,7 @@ static int hb_estep(void *self, const double *a, const double *e, const double *
 		memset(A, 0, sizeof(double) * n * n);
 		rc = h->grp ? psmc_hip_group_estep_factored(h->grp, a, e, a0, sums, E, LL) : psmc_hip_estep_factored(h->ctx, a, e, a0, sums, E, LL);
 		free(sums);
+		say_note(h, 0);
 		for (int i = 0; i < h->n_seg; ++i) h->chk[i] = 1.0; /* (fast mode has no underflow self-check) */
 		if (rc == PSMC_HIP_ENOTSUP) { /* "structured" = 0, a matrix without the PSMC form (-C): nothing of the wide path to decode */
 			fprintf(stderr, "psmc: the wide fast E-step cannot run (%s); repeating the decoding E-step with the exact kernels\n", hb_error(h));
@@ -119,7 +132,10 @@ static int hb_estep(void *self, const double *a, const double *e, const double *
 			if ((!h->grp || psmc_hip_group_route(h->grp, 0, &c, &l) == 0) && psmc_hip_wide_table_info(c, ti) == 0 && ti[2] == 8)
 				fprintf(stderr, "psmc: the decoding reads the wide fast tables (checkpoints: X at every 8th bin)\n");
 		}
-	} else rc = h->grp ? psmc_hip_group_estep(h->grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->ctx, a, e, a0, A, E, 0, LL, h->chk);
+	} else {
+		rc = h->grp ? psmc_hip_group_estep(h->grp, a, e, a0, A, E, 0, LL, h->chk) : psmc_hip_estep(h->ctx, a, e, a0, A, E, 0, LL, h->chk);
+		say_note(h, rc == 0);
+	}
 	if (rc == PSMC_HIP_ECONVERGE && h->mode == PSMC_HIP_MODE_FAST) rc = exact_once(h, a, e, a0, A, E, LL, 0);
 	if (rc) return rc;
 	for (int i = 0; i < h->n_seg; ++i) { /* the diagnostic of khmm.c:239-240 */
@@ -193,6 +209,7 @@ static int hb_scales(void *self, int seg, double *s) { HB_DECODE_CALL(psmc_hip_s
 static void hb_destroy(void *self)
 {
 	hip_be *h = (hip_be *)self;
+	say_note(h, 0); /* (no E-step ran) */
 	if (h->x_ctx) psmc_hip_destroy(h->x_ctx);
 	if (h->x_grp) psmc_hip_group_destroy(h->x_grp);
 	if (h->grp) psmc_hip_group_destroy(h->grp); else psmc_hip_destroy(h->ctx);
@@ -242,6 +259,13 @@ int psmc_hipbe_set_option(psmc_estep_backend *be, const char *key, double value)
 	hip_be *h = (hip_be *)be->self;
 	if (strcmp(key, "wide_fast") == 0) h->wide = value != 0;
 	return h->grp ? psmc_hip_group_set_option(h->grp, key, value) : psmc_hip_set_option(h->ctx, key, value);
+}
+
+void psmc_hipbe_note_counts(psmc_estep_backend *be, const char *line)
+{
+	hip_be *h = (hip_be *)be->self;
+	free(h->note);
+	h->note = strdup(line);
 }
 
 psmc_hip_ctx *psmc_hipbe_ctx(psmc_estep_backend *be) { return be && be->self ? ((hip_be *)be->self)->ctx : 0; }

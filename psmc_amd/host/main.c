@@ -16,7 +16,9 @@
  *                                    tables ("wide_fast" = 2 + "wide_decode")
  *   PSMC_HIP_WIDE_COUNTS=1           with PSMC_HIP_WIDE covering the run's size and a run that asks for full counts (PSMC_FACTORED=0 or
  *                                    PSMC_FAST_MSTEP=0): the full-count E-steps run on the wide fast path too (options "wide_fast" +
- *                                    "wide_counts"); without it they use the exact kernels
+ *                                    "wide_counts"); without it they use the exact kernels.  With
+ *                                    PSMC_HIP_OPTIONS=wide_ckpt=1,wide_counts_ckpt=1 these E-steps keep X at every 8th bin only and
+ *                                    the counts pass recomputes the rest ("wide_counts_ckpt"): the same output bytes
  *   PSMC_HIP_DEVICE=<index>          one GPU
  *   PSMC_HIP_DEVICES=<i>,<j>,...     the segments of every E-step sharded over these GPUs (psmc_hip_group_*: LPT
  *                                    partition, one RCCL all-reduce of the statistics per EM iteration in fast mode,
@@ -85,13 +87,14 @@ int main(int argc, char *argv[])
 	/* (PSMC_FACTORED=0 or PSMC_FAST_MSTEP=0 ask for full counts, which beyond 128 states only the exact kernels compute) */
 	/* PSMC_HIP_WIDE_COUNTS=1: a run of a size PSMC_HIP_WIDE covers that asks for full counts gets them from the wide fast path as well */
 	const char *wc_s = getenv("PSMC_HIP_WIDE_COUNTS");
+	char note[256] = "";
 	const int wide_counts = wide_fast && !use_factored && mode == PSMC_HIP_MODE_FAST && wc_s && atoi(wc_s) == 1;
 	if (wide_fast && use_factored && (plan & PSMC_PLAN_WIDE_DECODE))
 		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s PSMC_HIP_DECODE=%s: factored E-steps on the wide fast kernels; the decoding reads the wide fast tables\n", n_states, wide_s, dec_s);
 	else if (wide_fast && use_factored)
 		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s: factored E-steps on the wide fast kernels (full counts and decoding stay exact)\n", n_states, wide_s);
-	else if (wide_counts)
-		fprintf(stderr, "psmc: %d hidden states: PSMC_HIP_WIDE=%s PSMC_HIP_WIDE_COUNTS=1: full-count E-steps on the wide fast kernels\n", n_states, wide_s);
+	else if (wide_counts) /* said once the first E-step has run: with what it kept (psmc_hipbe_note_counts) */
+		snprintf(note, sizeof note, "psmc: %d hidden states: PSMC_HIP_WIDE=%s PSMC_HIP_WIDE_COUNTS=1: full-count E-steps on the wide fast kernels", n_states, wide_s);
 	else if (n_states > 128 && mode_is_fast())
 		fprintf(stderr, "psmc: %d hidden states: the fast kernels stop at 128, every E-step of this run uses the exact ones\n", n_states);
 	/* The input is read on a thread of its own while the device comes up: 0.35 s for a 30 M-bin genome beside 0.4 s of HIP start-up, of a
@@ -106,6 +109,8 @@ int main(int argc, char *argv[])
 	if (rc == 0 && wide_counts) rc = psmc_hipbe_set_option(&be, "wide_counts", 1);
 	if (rd_started) { pthread_join(rd_tid, 0); o.prefetched = pj.in; o.prefetch_rc = pj.rc; }
 	else free(pj.in);
+	if (note[0] && rc) fprintf(stderr, "%s\n", note);
+	else if (note[0]) psmc_hipbe_note_counts(&be, note);
 	if (rc) {
 		fprintf(stderr, "psmc: cannot start the MI355X E-step (%s); this build has no CPU path\n", psmc_hip_strerror(rc));
 		psmc_options_free(&o);

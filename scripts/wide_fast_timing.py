@@ -28,7 +28,10 @@
       context with "wide_fast" + "wide_counts" (parameters moving as in (a); the first step and the later ones, and of the later ones
       what the library's events give to the factored part and to the counts pass), ms per factored wide E-step of the same build
       and parameters, and -- unless --exact-steps 0 -- ms per psmc_hip_estep on the wide exact kernels, what that call ran before the
-      option existed; --counts-slab sets "wide_counts_slab"
+      option existed; --counts-slab sets "wide_counts_slab".  With --ckpt it sets "wide_ckpt" = 1 and "wide_counts_ckpt" = 1 on that
+      context: the counts E-steps keep checkpoints and the counts pass recomputes the rows between them.  Either way it prints the X
+      table's bytes and interval beside each time, and the device memory in use before the context exists and after its E-steps
+      (hipMemGetInfo: the context keeps every buffer, so the difference is what the run needs)
 
   --ckpt sets "wide_ckpt" = 1 on the wide contexts of (a) and (e): X at every 8th bin only, the rest recomputed in the accumulate
   sweep.  Beside every time, (a) and (e) print what psmc_hip_wide_table_info reports: the bytes of X the context holds.
@@ -44,6 +47,7 @@ Library calls are synchronous.  Writes one JSON object to stdout (progress on st
     python scripts/wide_fast_timing.py --decode --stress --states 200,300,1024 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
     python scripts/wide_fast_timing.py --counts [--stress] --states 200,300,1024 --steps 4 --exact-steps 1
+    python scripts/wide_fast_timing.py --counts --stress --states 200,300,1024 --steps 4 --exact-steps 0 [--ckpt]
 """
 import argparse
 import json
@@ -131,20 +135,45 @@ def library_part(hip, segs, n, steps, exact_steps, ckpt=False):
     return r
 
 
-def counts_part(hip, segs, n, steps, exact_steps, slab=0):
+def device_bytes_in_use(hip):
+    """total - free of hipMemGetInfo on the current device -- the runtime the library is linked against, found through the library's
+    own handle; None when it cannot be asked"""
+    import ctypes as C
+    try:
+        fn = hip.load_library().hipMemGetInfo
+    except AttributeError:
+        return None
+    fn.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    fn.restype = C.c_int
+    free, total = C.c_size_t(0), C.c_size_t(0)
+    return int(total.value - free.value) if fn(C.byref(free), C.byref(total)) == 0 else None
+
+
+def counts_part(hip, segs, n, steps, exact_steps, slab=0, ckpt=False):
     """(f)"""
     ps = params_seq(n, steps)
-    r = {"wide_counts_slab": slab}
+    r = {"wide_counts_slab": slab, "wide_counts_ckpt": int(ckpt)}
+    hip.load_library().psmc_hip_device_count()   # (the runtime is up before the first reading)
+    before = device_bytes_in_use(hip)
     es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_counts=1, wide_counts_slab=slab)
+    if ckpt:
+        es.set_option("wide_ckpt", 1)
+        es.set_option("wide_counts_ckpt", 1)
     es.load_segments(segs)
-    ms, dev = [], []
+    ms, dev, tabs = [], [], []
     for a, e, a0 in ps:
         t = time.perf_counter(); es.estep(a, e, a0); ms.append((time.perf_counter() - t) * 1e3)
         tm = es.timing()
         dev.append(dict(total=float(tm["total"]), factored=float(tm["chains"]), counts=float(tm["expect"])))
+        ti = table_info(es)
+        tabs.append(dict(bytes=ti["bytes"], interval=ti["interval"]) if ti else None)
+    after = device_bytes_in_use(hip)
     d = es.fast_diag()
     assert d["back_half"] == 4, d
     ti = table_info(es)
+    assert ti is None or ti["interval"] == (8 if ckpt else 1), ti
+    r.update(x_table=tabs, device_bytes_before=before, device_bytes_after_counts_esteps=after,
+             device_bytes_of_the_context=after - before if before is not None and after is not None else None)
     r.update(tiles=d["n_chunks"], tile_len=d["tile_len"], x_table_bytes=ti["bytes"] if ti else None, counts_ms=ms, counts_first_ms=ms[0],
              counts_later_ms_mean=float(np.mean(ms[1:])), counts_later_ms_min=float(np.min(ms[1:])), device_ms=dev,
              device_counts_pass_ms_mean=float(np.mean([x["counts"] for x in dev[1:]])),
@@ -305,7 +334,7 @@ def main():
     ap.add_argument("--full-post", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="(e): the bootstrap batch of this many replicates on the wide fast path instead of (a), (b)")
     ap.add_argument("--batch-leg", choices=["wide", "exact"], default="wide", help="with --batch: \"wide_batch\" = 1 and the single E-step, or the exact launch groups")
-    ap.add_argument("--ckpt", action="store_true", help="\"wide_ckpt\" = 1 on the wide contexts of (a) and (e): X at every 8th bin only; the table's bytes are printed beside each time.  With --decode: \"wide_ckpt\" = 1 and \"wide_decode_ckpt\" = 1 on the wide context of (d), decoding from checkpoints")
+    ap.add_argument("--ckpt", action="store_true", help="\"wide_ckpt\" = 1 on the wide contexts of (a) and (e): X at every 8th bin only; the table's bytes are printed beside each time.  With --decode: \"wide_ckpt\" = 1 and \"wide_decode_ckpt\" = 1 on the wide context of (d), decoding from checkpoints.  With --counts: \"wide_ckpt\" = 1 and \"wide_counts_ckpt\" = 1 on the wide-counts context of (f), counts from checkpoints")
     ap.add_argument("--counts", action="store_true", help="(f): psmc_hip_estep with \"wide_counts\" = 1 against the factored wide E-step and the exact kernels instead of (a), (b)")
     ap.add_argument("--counts-slab", type=int, default=0, help="with --counts: \"wide_counts_slab\" (0 = auto)")
     ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
@@ -323,7 +352,7 @@ def main():
         out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
     for n in [int(x) for x in args.states.split(",") if x]:
         if args.counts:
-            out["n%d" % n] = counts_part(hip, segs, n, args.steps, args.exact_steps, args.counts_slab)
+            out["n%d" % n] = counts_part(hip, segs, n, args.steps, args.exact_steps, args.counts_slab, args.ckpt)
         elif args.batch > 0:
             out["n%d" % n] = batch_part(hip, segs, n, args.batch, args.batch_leg, args.ckpt)
         elif args.decode:
