@@ -203,6 +203,20 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           when the plan is made -- inside such a run the chain forgets at the rate of the matrix's second eigenvalue alone,
  *                           ~5e5 bins, so no warm-up works -- do not count against "group_cap" / "kc_div", and share ONE transfer matrix per
  *                           direction (a^T to the tile length).  0: as rounds 1-4 (a 2e5-bin gap then costs ~50 repair rounds per E-step)
+ *  "hom_tiles"     0        1: runs of homozygosity are found when the plan is made, as "gap_tiles" finds runs of missing data (structured sweeps,
+ *                           up to 128 states).  A hom tile is a full tile without a heterozygous bin -- all homozygous, or homozygous and missing
+ *                           bins -- that is neither the first nor the last tile of its segment; a qualifying run is a maximal sequence of
+ *                           consecutive hom tiles and gap tiles of one segment that holds at least one hom tile and "hom_min" bins of hom tiles.
+ *                           Every tile whose warm-up window overlaps a tile of a qualifying run -- the run's own tiles behind its head, and the
+ *                           tiles up to one warm-up past its end, in either direction -- is glued to its neighbour at once instead of being
+ *                           learned one repair round at a time (a 45 k-bin run at 256-bin tiles: ~290 rounds in a context's first E-step).  The
+ *                           all-homozygous tiles of qualifying runs share ONE transfer matrix per direction when the tile length is a multiple
+ *                           of four and then do not count against "group_cap" / "kc_div"; the others keep a matrix each and count in full.
+ *                           0: the plan is bit for bit what it was without the option.  Accepted and ignored in exact mode, by the dense
+ *                           sweeps ("structured" = 0, a matrix without the PSMC form) and beyond 128 states.  Other values: PSMC_HIP_EINVAL
+ *  "hom_min"       auto     bins of hom tiles a run needs to qualify; 0 = auto = "warmup" / 4.  The default comes from a CPU measurement on two
+ *                           parameter sets (~512 het-free bins inside a 3072-bin warm-up are harmless, ~1024 are not),
+ *                           not from a GPU sweep.  Negative: PSMC_HIP_EINVAL
  *  "two_phase"     auto     2: the fused back half runs as two launches, odd tiles of the second list start from the exit
  *                           vector of the tile above instead of speculating backward; 0: every tile speculates, one
  *                           launch when the tiles fit one round.  auto: 2 with two rounds, 0 with one

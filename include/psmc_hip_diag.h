@@ -89,6 +89,14 @@ int psmc_hip_last_timing(psmc_hip_ctx *ctx, double ms[7]);
  * batch's way like this (psmc_amd/host/boot.c). */
 int psmc_hip_cumask_probe(int device, int n_cus_a, int n_waves_a, int n_waves_b, int steps, double *out, double *ms_out);
 
+/* Diagnostic: the tiles of the current fast plan (up to 128 states), as the planner classified them ("gap_tiles", "hom_tiles" of
+ * psmc_hip.h).  Returns the number of tiles of the plan -- PSMC_HIP_ESTATE when there is none, as psmc_hip_fast_plan -- and fills the
+ * first `cap` entries: cls[b] = 0, 1 = gap tile (a full tile of missing data inside its segment), 2 = hom tile (a full het-free tile
+ * inside its segment) outside a qualifying run, 3 = hom tile of a qualifying run; glue[b] = bit 0: tile b continues the forward item
+ * of tile b - 1, bit 1: it continues the backward item of tile b + 1 -- what the plan rules set and what the context has learned
+ * since. */
+int psmc_hip_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap);
+
 #ifdef __cplusplus
 }
 #endif

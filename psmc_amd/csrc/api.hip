@@ -212,6 +212,8 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "tail") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->tail = (int)v; }
 	else if (k == "lanes8") { if (v < -1 || v > 1) return PSMC_HIP_EINVAL; c->lanes8 = (int)v; }
 	else if (k == "gap_tiles") { c->gap_tiles = v != 0 ? 1 : 0; c->plan_dirty = true; c->items_dirty = true; }
+	else if (k == "hom_tiles") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->hom_tiles = (int)v; c->plan_dirty = true; c->items_dirty = true; } // api_fast.hip plan_fast
+	else if (k == "hom_min") { if (!(v >= 0 && v <= 2147483647.0)) return PSMC_HIP_EINVAL; c->hom_min = (int)v; c->plan_dirty = true; c->items_dirty = true; }
 	else if (k == "coarse") { if (v < -1 || v > 16) return PSMC_HIP_EINVAL; c->coarse = (int)v; c->plan_dirty = true; c->items_dirty = true; }
 	else if (k == "kc_sub") { if (v < 1 || v > 16) return PSMC_HIP_EINVAL; c->kc_sub = (int)v; c->kc_sub_set = true; c->plan_dirty = true; c->items_dirty = true; }
 	else if (k == "two_phase") { if (v != -1 && v != 0 && v != 2) return PSMC_HIP_EINVAL; c->two_phase = (int)v; c->plan_dirty = true; c->items_dirty = true; }

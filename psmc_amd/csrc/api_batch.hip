@@ -488,7 +488,7 @@ static psmc_hip_ctx *batch_child(psmc_hip_ctx *c, int r)
 		k->struct_tiles_set = c->struct_tiles_set; k->struct_tiles = c->struct_tiles;
 		k->two_phase = c->two_phase; k->kc_div = c->kc_div; k->kc_min = c->kc_min; k->ckpt = c->ckpt; k->fuse = c->fuse;
 		k->learn = c->learn; k->group_cap = c->group_cap; k->warm_shift = c->warm_shift; k->kc_sub = c->kc_sub; k->kcol_prio = c->kcol_prio;
-		k->fuse128 = c->fuse128; k->coarse = c->coarse; k->gate = c->gate; k->lanes8 = c->lanes8; k->gap_tiles = c->gap_tiles; k->exact_refwd = c->exact_refwd;
+		k->fuse128 = c->fuse128; k->coarse = c->coarse; k->gate = c->gate; k->lanes8 = c->lanes8; k->gap_tiles = c->gap_tiles; k->hom_tiles = c->hom_tiles; k->hom_min = c->hom_min; k->exact_refwd = c->exact_refwd;
 		k->merge = c->merge; k->adapt = c->adapt; k->prev_start = c->prev_start;
 		k->tail = 0; // (the replicates of a batch keep the plain tail)
 		k->merge1 = c->merge1; k->merge_order = c->merge_order; k->runs_late = c->runs_late; k->warm_shift_set = c->warm_shift_set; k->kc_sub_set = c->kc_sub_set;

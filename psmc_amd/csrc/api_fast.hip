@@ -141,24 +141,55 @@ static int plan_fast(psmc_hip_ctx *c)
 	if ((rc = dev_alloc(c, &c->d_Epart, (size_t)nc * c->n_sub_used * 3 * c->ns))) return rc;
 	if ((rc = ensure_fast_buffers(c))) return rc;
 	HIPCHK(c, hipMemcpy(c->d_chunks, c->chunks.data(), sizeof(Chunk) * nc, hipMemcpyHostToDevice));
-	if (st && c->gap_tiles) {
-		// Tiles of missing data (round 5; estep_struct.hip k_tile_allmiss).  A FULL tile inside its segment (not the first, not the last: position 1
-		// and position L are special) that is all `N` is a "gap tile": glued to its neighbours now, in both directions, together with the first
-		// tile after the gap in either direction -- their start vectors hang on what entered the gap however long it is.
-		std::vector<int> fl(nc, 0);
-		if (launch_tile_allmiss(c->stream, c->d_obs, c->d_chunks, nc, c->d_dirty) != 0) return fail(c, PSMC_HIP_EDEVICE, "k_tile_allmiss", hipGetLastError());
-		HIPCHK(c, hipMemcpyAsync(fl.data(), c->d_dirty, sizeof(int) * nc, hipMemcpyDeviceToHost, c->stream));
+	c->hom.assign(nc, 0);
+	if (st && (c->gap_tiles || c->hom_tiles)) {
+		// What every tile holds (estep_struct.hip k_tile_class): 0 a het bin, 1 missing data only, 2 homozygous bins only, 3 het-free, both kinds.
+		std::vector<int> cls(nc, 0);
+		if (launch_tile_class(c->stream, c->d_obs, c->d_chunks, nc, c->d_dirty) != 0) return fail(c, PSMC_HIP_EDEVICE, "k_tile_class", hipGetLastError());
+		HIPCHK(c, hipMemcpyAsync(cls.data(), c->d_dirty, sizeof(int) * nc, hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(c, hipMemsetAsync(c->d_dirty, 0, sizeof(int) * nc, c->stream)); // (borrowed as scratch: back to what an allocation holds)
 		HIPCHK(c, hipStreamSynchronize(c->stream));
-		for (int b = 0; b < nc; ++b) {
-			const Chunk &ch = c->chunks[b];
-			c->gap[b] = fl[b] && ch.lo > 1 && ch.hi < ch.L && ch.hi - ch.lo + 1 == T;
-		}
 		auto same = [&](int x, int y) { return x >= 0 && y < nc && c->chunks[x].off == c->chunks[y].off; };
-		for (int b = 0; b < nc; ++b) {
-			if (c->gap[b]) { if (same(b - 1, b)) c->glue_f[b] = 1; if (same(b, b + 1)) c->glue_b[b] = 1; }
-			if (b > 0 && c->gap[b - 1] && same(b - 1, b)) c->glue_f[b] = 1;      // the first tile after a gap, forward
-			if (b + 1 < nc && c->gap[b + 1] && same(b, b + 1)) c->glue_b[b] = 1;  // ... and backward
+		auto inner = [&](const Chunk &ch) { return ch.lo > 1 && ch.hi < ch.L && ch.hi - ch.lo + 1 == T; }; // a FULL tile, not the first, not the last
+		if (c->gap_tiles) {
+			// Tiles of missing data (round 5).  A FULL tile inside its segment (not the first, not the last: position 1
+			// and position L are special) that is all `N` is a "gap tile": glued to its neighbours now, in both directions, together with the first
+			// tile after the gap in either direction -- their start vectors hang on what entered the gap however long it is.
+			for (int b = 0; b < nc; ++b) c->gap[b] = cls[b] == 1 && inner(c->chunks[b]);
+			for (int b = 0; b < nc; ++b) {
+				if (c->gap[b]) { if (same(b - 1, b)) c->glue_f[b] = 1; if (same(b, b + 1)) c->glue_b[b] = 1; }
+				if (b > 0 && c->gap[b - 1] && same(b - 1, b)) c->glue_f[b] = 1;      // the first tile after a gap, forward
+				if (b + 1 < nc && c->gap[b + 1] && same(b, b + 1)) c->glue_b[b] = 1;  // ... and backward
+			}
+		}
+		if (c->hom_tiles) {
+			// Runs of homozygosity ("hom_tiles"; the rule: psmc_hip_ctx.h, its evidence: DESIGN.md section 9 (5)).  A warm-up that lies in such a run
+			// has not forgotten its start, INSIDE the run and for a warm-up's length behind it -- "the first tile after", which is what a gap needs,
+			// is not enough at small tiles.  Every tile whose warm-up window touches a tile of a qualifying run is glued to its neighbour now.
+			const int64_t need = c->hom_min > 0 ? c->hom_min : c->warmup / 4;
+			for (int b = 0; b < nc; ++b) c->hom[b] = (cls[b] == 2 || cls[b] == 3) && inner(c->chunks[b]);
+			std::vector<int> inq(nc + 1, 0); // inq[b + 1] - inq[b]: tile b belongs to a qualifying run (prefix sums)
+			for (int b = 0; b < nc;) {
+				if (!c->hom[b] && !c->gap[b]) { ++b; continue; }
+				int e = b; int64_t bins = 0;
+				for (; e < nc && same(b, e) && (c->hom[e] || c->gap[e]); ++e) if (c->hom[e]) bins += T;
+				if (bins > 0 && bins >= need)
+					for (int t = b; t < e; ++t) { inq[t + 1] = 1; if (c->hom[t]) c->hom[t] = cls[t] == 2 ? 3 : 2; }
+				b = e;
+			}
+			for (int b = 0; b < nc; ++b) inq[b + 1] += inq[b];
+			for (int b = 0; b < nc; ++b) {
+				const Chunk &ch = c->chunks[b];
+				const int first = b - c->chunk_idx[b]; // the segment's first tile; the tile that holds position p is first + (p - 1) / T
+				if (same(b - 1, b)) { // forward: positions lo - wf .. lo - 1
+					const int t0 = first + (int)((std::max<int64_t>(1, (int64_t)ch.lo - ch.wf) - 1) / T);
+					if (ch.wf > 0 && inq[b] - inq[t0] > 0) c->glue_f[b] = 1; // tiles t0 .. b - 1
+				}
+				if (same(b, b + 1)) { // backward: positions hi + 1 .. hi + wb
+					const int t1 = first + (int)((std::min<int64_t>(ch.L, (int64_t)ch.hi + ch.wb) - 1) / T);
+					if (ch.wb > 0 && inq[t1 + 1] - inq[b + 1] > 0) c->glue_b[b] = 1; // tiles b + 1 .. t1
+				}
+			}
 		}
 	}
 	c->plan_dirty = false; c->chunks_dirty = false; c->prev_ok = false;
@@ -193,8 +224,11 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 	auto same_seg = [&](int x, int y) { return c->chunks[x].off == c->chunks[y].off; };
 	// "group_cap" bounds the bins of a run that carry DATA: a run of missing data costs its tiles one shared transfer matrix, however long it is
 	const bool gaps = c->gap_tiles && (int)c->gap.size() == nc;
+	// ("hom_tiles": so does a run of homozygosity -- the all-homozygous tiles of a qualifying run that share one matrix, see push_kc; a het-free mix counts in full)
+	const bool homs = c->hom_tiles && (int)c->hom.size() == nc && c->chunk_used % 4 == 0;
+	auto hom_shared = [&](int t) { return homs && c->hom[t] == 3; };
 	std::vector<int64_t> eff(nc + 1, 0);
-	for (int b = 0; b < nc; ++b) eff[b + 1] = eff[b] + ((gaps && c->gap[b]) ? 0 : c->chunks[b].hi - c->chunks[b].lo + 1);
+	for (int b = 0; b < nc; ++b) eff[b + 1] = eff[b] + (((gaps && c->gap[b]) || hom_shared(b)) ? 0 : c->chunks[b].hi - c->chunks[b].lo + 1);
 	auto span_ok = [&](int b, int e) { return eff[e + 1] - eff[b] <= (int64_t)c->group_cap; }; // tiles b .. e
 	for (int b = 0; b < nc;) { // forward: head b, members b+1.. while glued
 		int e = b + 1;
@@ -364,6 +398,7 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 	//   d_items + 12nc: wl_f (2nc) | wl_b (2nc) | kc tiles (4nc: KcTile) | runs (4nc + : KcRun)
 	std::vector<int> wl((size_t)4 * nc, 0), kc, runs_f, runs_b, kslot, kuniq; // kslot[j]: matrix slot of KcTile j; kuniq[u]: the KcTile that computes slot u
 	int gap_slot[2] = {-1, -1}; // the slot every gap tile of a direction shares
+	int hom_slot[2] = {-1, -1}; // ... and the one the all-homozygous tiles of qualifying runs share ("hom_tiles")
 	auto push_kc = [&](int t, int dir) {
 		const int j = (int)kc.size() / 2;
 		kc.push_back(t); kc.push_back(dir);
@@ -373,6 +408,9 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 		if (gaps && c->gap[t] && c->chunk_used % 4 == 0) {
 			if (gap_slot[dir] < 0) { gap_slot[dir] = (int)kuniq.size(); kuniq.push_back(j); }
 			kslot.push_back(gap_slot[dir]);
+		} else if (hom_shared(t)) { // (the same condition: hom_shared holds only where T % 4 == 0)
+			if (hom_slot[dir] < 0) { hom_slot[dir] = (int)kuniq.size(); kuniq.push_back(j); }
+			kslot.push_back(hom_slot[dir]);
 		} else { kslot.push_back((int)kuniq.size()); kuniq.push_back(j); }
 	};
 	c->n_wl_f = c->n_wl_b = 0;
@@ -389,9 +427,10 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 		int budget = std::max(64, nc / c->kc_div);
 		for (int i = 0; i < n_long; ++i) {
 			int first = k[i].second.first, count = k[i].second.second;
-			// what a run's matrices cost: one column kernel per tile that carries data (gap tiles share a matrix computed once per direction)
+			// what a run's matrices cost: one column kernel per tile that carries data (gap tiles share a matrix computed once per direction, and so do
+			// the all-homozygous tiles of "hom_tiles")
 			int cost = 0;
-			for (int tt = first; tt < first + count; ++tt) cost += (gaps && c->gap[tt] && c->chunk_used % 4 == 0) ? 0 : 1;
+			for (int tt = first; tt < first + count; ++tt) cost += ((gaps && c->gap[tt] && c->chunk_used % 4 == 0) || hom_shared(tt)) ? 0 : 1;
 			cost = std::max(cost - 1, 1);
 			const bool chain = chains && count >= kc_min && cost <= budget;
 			if (chain) budget -= cost;

@@ -279,3 +279,17 @@ extern "C" int psmc_hip_last_timing(psmc_hip_ctx *c, double ms[7])
 	for (int i = 0; i < 7; ++i) ms[i] = c->last_ms[i];
 	return PSMC_HIP_OK;
 }
+
+extern "C" int psmc_hip_plan_tiles(psmc_hip_ctx *c, int32_t *cls, int32_t *glue, int cap)
+{
+	if (!c || cap < 0 || (cap > 0 && (!cls || !glue))) return PSMC_HIP_EINVAL;
+	// (as psmc_hip_fast_plan: the plan is made by the first fast E-step after load / select / an option that changes it)
+	if (c->plan_dirty || c->chunks.empty()) return fail(c, PSMC_HIP_ESTATE, "plan_tiles: no current plan (run a fast E-step first)");
+	const int nc = (int)c->chunks.size();
+	for (int b = 0; b < nc && b < cap; ++b) {
+		const int hom = b < (int)c->hom.size() ? c->hom[b] : 0;
+		cls[b] = (b < (int)c->gap.size() && c->gap[b]) ? 1 : (hom >= 2 ? 3 : (hom == 1 ? 2 : 0));
+		glue[b] = (c->glue_f[b] ? 1 : 0) | (c->glue_b[b] ? 2 : 0);
+	}
+	return nc;
+}

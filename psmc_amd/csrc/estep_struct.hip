@@ -1202,24 +1202,49 @@ void launch_gather_prev(const EstepLaunch &p, hipStream_t st, int first, int n_i
 	hipLaunchKernelGGL(k_gather_prev, dim3(n_items), dim3(64), 0, st, p.d_chunks, (const SweepItem *)p.d_items_f + first, p.ns, p.d_f, p.d_a0, prevx, p.ckpt);
 }
 
-// Plan time: which tiles consist of missing data only (symbol 2 at every position lo..hi)?  Real .psmcfa files carry runs of 1e4 .. 3e5 `N`
-// bins (centromeres, assembly gaps: utils/fq2psmcfa.c:114-127); inside such a run the chain forgets at the rate of the transition matrix's
-// second eigenvalue alone -- 0.99995 for a human-like model: 5e5 bins to 1e-12 -- so no speculative warm-up ever works there and every tile
-// of the run hangs on the vector at its start.  The planner glues them at once, and their transfer matrix (a^T to the tile length,
-// whatever the tile) is computed ONCE per direction (api_fast.hip build_items).
-__global__ __launch_bounds__(64) void k_tile_allmiss(const uint8_t *__restrict__ obs, const Chunk *__restrict__ chunks, int *__restrict__ flags)
+// Plan time: what kind of observations does every tile hold?  Two kinds of tiles defeat a speculative warm-up, and the planner glues both
+// before the first E-step instead of learning them one repair round at a time (api_fast.hip plan_fast).
+//   Missing data ("gap_tiles", round 5).  Real .psmcfa files carry runs of 1e4 .. 3e5 `N` bins (centromeres, assembly gaps:
+//   utils/fq2psmcfa.c:114-127); inside such a run the chain forgets at the rate of the transition matrix's second eigenvalue alone --
+//   0.99995 for a human-like model: 5e5 bins to 1e-12 -- so every tile of the run hangs on the vector at its start.  Their transfer matrix
+//   (a^T to the tile length, whatever the tile) is computed ONCE per direction (build_items).
+//   No heterozygous bin ("hom_tiles").  A homozygous bin tells the chain about a sixteenth of what an ordinary bin does (DESIGN.md
+//   section 9 (5)): a warm-up that lies in a run of homozygosity has not forgotten its start when it reaches the tile.
+// One wave per tile reads the tile's bytes once, 16 per lane and load where they are aligned; the ragged bytes before the first and behind
+// the last aligned 16 are read one per lane (the segment base is 64-byte aligned, lo is anything), so no byte outside lo..hi is looked at.
+// Three wave-wide predicates over byte & 3 -- some bin is not 2, some bin is 1, some bin is 2 -- give the code:
+//   0 = a het bin, 1 = all missing (what k_tile_allmiss answered until round 6), 2 = all homozygous, 3 = het-free, both 0 and 2.
+// (A symbol 3, which no loader lets through, counts as het: the tile is left alone.)
+__global__ __launch_bounds__(64) void k_tile_class(const uint8_t *__restrict__ obs, const Chunk *__restrict__ chunks, int *__restrict__ cls)
 {
 	const Chunk c = chunks[blockIdx.x];
-	const uint8_t *o = obs + c.off;
-	int bad = 0;
-	for (int p = c.lo + (int)threadIdx.x; p <= c.hi; p += 64) bad |= ((int)o[p - 1] & 3) != 2;
-	const int any_bad = __any(bad);
-	if (threadIdx.x == 0) flags[blockIdx.x] = any_bad ? 0 : 1;
+	const int lane = threadIdx.x;
+	const uint8_t *t = obs + c.off + c.lo - 1; // the tile's bytes: t[0 .. n - 1]
+	const int n = c.hi - c.lo + 1;
+	const int head = min((int)((16 - ((uintptr_t)t & 15)) & 15), n); // bytes before the first aligned 16 (a tile inside one aligned 16: all of it)
+	const int n16 = (n - head) >> 4, tail = head + 16 * n16;          // aligned 16s; where the bytes behind the last one start
+	uint32_t not2 = 0, het = 0, two = 0; // bit 0 of every byte: that symbol is not 2 / is odd / has bit 1
+	auto word = [&](uint32_t w, uint32_t m) { // m: bit 0 of the bytes that hold a symbol
+		const uint32_t v = w & 0x03030303u;
+		const uint32_t x = v ^ 0x02020202u;
+		not2 |= (x | (x >> 1)) & m; het |= v & m; two |= (v >> 1) & m;
+	};
+	// head t[0 .. head - 1] and tail t[tail .. n - 1]: fewer than 16 bytes each, one per lane
+	if (lane < head) word((uint32_t)t[lane], 1u);
+	if (tail + lane < n) word((uint32_t)t[tail + lane], 1u);
+	const uint4 *t4 = (const uint4 *)(t + head);
+#pragma unroll 4
+	for (int i = lane; i < n16; i += 64) {
+		const uint4 w = t4[i];
+		word(w.x, 0x01010101u); word(w.y, 0x01010101u); word(w.z, 0x01010101u); word(w.w, 0x01010101u);
+	}
+	const int any_not2 = __any((int)not2), any_het = __any((int)het), any_two = __any((int)two);
+	if (lane == 0) cls[blockIdx.x] = any_het ? 0 : (!any_not2 ? 1 : (!any_two ? 2 : 3));
 }
-int launch_tile_allmiss(hipStream_t st, const uint8_t *d_obs, const Chunk *d_chunks, int n_chunks, int *d_flags)
+int launch_tile_class(hipStream_t st, const uint8_t *d_obs, const Chunk *d_chunks, int n_chunks, int *d_cls)
 {
 	if (n_chunks <= 0) return 0;
-	hipLaunchKernelGGL(k_tile_allmiss, dim3(n_chunks), dim3(64), 0, st, d_obs, d_chunks, d_flags);
+	hipLaunchKernelGGL(k_tile_class, dim3(n_chunks), dim3(64), 0, st, d_obs, d_chunks, d_cls);
 	return (int)hipGetLastError();
 }
 

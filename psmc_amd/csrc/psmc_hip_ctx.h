@@ -113,9 +113,19 @@ struct psmc_hip_ctx {
 	int *h_ritems = nullptr;   // pinned + device-mapped, 2 * 2*n_chunks ints
 	int *m_ritems = nullptr, *m_cnt = nullptr; // device views of h_ritems / h_cnt
 	std::vector<uint8_t> glue_f, glue_b; // glue_f[b]: tile b continues the forward item of b-1; glue_b[b]: b continues b+1's backward item
-	std::vector<uint8_t> gap;            // gap[b]: tile b is a FULL tile of missing data inside its segment (plan_fast: k_tile_allmiss): glued at once,
+	std::vector<uint8_t> gap;            // gap[b]: tile b is a FULL tile of missing data inside its segment (plan_fast: k_tile_class): glued at once,
 	                                     // free of "group_cap", one shared transfer matrix per direction (build_items)
 	int gap_tiles = 1;                   // "gap_tiles": 0 = treat tiles of missing data like any other (rounds 1-4)
+	// "hom_tiles": runs without a heterozygous bin.  A HOM TILE is a full tile of k_tile_class 2 (all homozygous) or 3 (het-free: homozygous and
+	// missing bins) that is neither the first nor the last tile of its segment -- what a gap tile is for missing data.  A QUALIFYING RUN is a
+	// maximal sequence of consecutive tiles of one segment, each a hom tile or a gap tile, at least one of them a hom tile, whose hom tiles total at
+	// least "hom_min" bins.  plan_fast glues every tile whose warm-up window overlaps a tile of a qualifying run (forward: [lo - wf, lo - 1];
+	// backward: [hi + 1, hi + wb]) after the gap-tile rule, the flags OR-ed.  build_items: the all-homozygous tiles of qualifying runs share one
+	// transfer matrix per direction as gap tiles do (a slot of their own, under the same T % 4 == 0), and those that share one cost nothing
+	// towards the chain budget and count no bins towards "group_cap"; het-free mixes keep a matrix each and count in full.
+	std::vector<uint8_t> hom;            // hom[b]: 0 = no hom tile, 1 = hom tile outside a qualifying run, 2 = het-free mix in a qualifying run, 3 = all homozygous in one
+	int hom_tiles = 0;                   // "hom_tiles": 1 = on
+	int hom_min = 0;                     // "hom_min": bins; 0 = auto = warmup / 4
 	int n_kuniq = 0;                     // transfer-matrix slots of the current item lists
 	std::vector<int> flagged_f, flagged_b;
 	bool items_dirty = true;

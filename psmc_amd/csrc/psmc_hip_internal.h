@@ -220,7 +220,7 @@ void launch_fwd_struct(const EstepLaunch &p, hipStream_t st, int which, int firs
 void launch_bwd_struct(const EstepLaunch &p, hipStream_t st, int which, int first, int n_items);
 void launch_compact(const EstepLaunch &p, hipStream_t st, bool bwd, bool counted = false); // counted: d_cnt already holds the number of flags (an all-clear round writes only that)
 void launch_gather_prev(const EstepLaunch &p, hipStream_t st, int first, int n_items, double *prevx); // estep_struct.hip
-int launch_tile_allmiss(hipStream_t st, const uint8_t *d_obs, const Chunk *d_chunks, int n_chunks, int *d_flags); // estep_struct.hip
+int launch_tile_class(hipStream_t st, const uint8_t *d_obs, const Chunk *d_chunks, int n_chunks, int *d_cls); // estep_struct.hip: 0 het, 1 all missing, 2 all homozygous, 3 het-free mix
 void launch_walks(const EstepLaunch &p, hipStream_t st);
 void launch_gate(hipStream_t st, const int *ctr, int want);
 int walk_blocks(const EstepLaunch &p);

@@ -39,7 +39,7 @@ EXPORTS = [
 DIAG_EXPORTS = [
     "psmc_hip_selftest", "psmc_hip_last_timing", "psmc_hip_microbench", "psmc_hip_stream_probe", "psmc_hip_hbm_probe",
     "psmc_hip_load_probe", "psmc_hip_load_probe_st", "psmc_hip_pipe_probe", "psmc_hip_pipe_probe2", "psmc_hip_place_probe",
-    "psmc_hip_cumask_probe",
+    "psmc_hip_cumask_probe", "psmc_hip_plan_tiles",
 ]
 
 
@@ -325,6 +325,21 @@ class HipEStep:
         self._chk(self.lib.psmc_hip_fast_plan(self.h, _p(o)), "fast_plan")
         return dict(tiles=int(o[0]), tile_len=int(o[1]), warm_fwd_mean=o[2], warm_bwd_mean=o[3], warm_fwd_max=int(o[4]), warm_bwd_max=int(o[5]),
                     glued_fwd=int(o[6]), glued_bwd=int(o[7]))
+
+    def plan_tiles(self):
+        """Per tile of the current fast plan (psmc_hip_plan_tiles, the diagnostic library): dict(cls, glue) of int32 arrays -- cls 0,
+        1 = gap tile, 2 = hom tile outside a qualifying run, 3 = hom tile of a qualifying run ("hom_tiles"); glue bit 0 = glued forward,
+        bit 1 = glued backward."""
+        d = load_diag()
+        d.psmc_hip_plan_tiles.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int]
+        n = d.psmc_hip_plan_tiles(self.h, None, None, 0)
+        if n < 0:
+            self._chk(n, "plan_tiles")
+        cls = np.zeros(n, dtype=np.int32); glue = np.zeros(n, dtype=np.int32)
+        n2 = d.psmc_hip_plan_tiles(self.h, cls.ctypes.data_as(_i32p), glue.ctypes.data_as(_i32p), n)
+        if n2 < 0:
+            self._chk(n2, "plan_tiles")
+        return dict(cls=cls, glue=glue)
 
     def tables(self, seg, want_b=True):
         L = int(self.lens[seg])

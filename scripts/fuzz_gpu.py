@@ -4,7 +4,7 @@ campaign to run on a lease (`python scripts/fuzz_gpu.py SECONDS [SEED0]`), its s
 
 Every case: 1-12 segments with lengths log-uniform in [1, 300 k], simulated under a parameter set of the committed EM trajectory
 (64 or 128 states), with planted runs of missing data (up to 60 k bins) and of homozygous bins; a random plan (chunk, warmup,
-fused or not, gap tiles, the round-6 options merge / adapt / prev_start); four E-steps with DIFFERENT parameter sets on the same
+fused or not, gap tiles, hom tiles, the round-6 options merge / adapt / prev_start); four E-steps with DIFFERENT parameter sets on the same
 context (the plan learns across them), full counts and factored sums, each compared with exact mode at the bounds the suite uses
 (tests/test_gpu_estep.py check_fast).  PSMC_HIP_ECONVERGE is an allowed answer for plans that cannot converge (it is counted).
 FUZZ_DEFAULT=1: every case with the default plan (what a caller without options gets).  FUZZ_BIG=1: segments of 20 k..1 M bins and
@@ -69,6 +69,7 @@ def main():
         if rng.random() < 0.5: opts["warmup"] = int(rng.choice([128, 512, 1024, 3072]))
         if rng.random() < 0.2: opts["fuse"] = 0
         if rng.random() < 0.2: opts["gap_tiles"] = 0
+        if rng.random() < 0.5: opts["hom_tiles"] = 1   # (drawn since "hom_tiles" exists: the seeds of profiles/r06_fuzz.txt then name other plans)
         if n == 64 and rng.random() < 0.4:
             opts["merge"] = 1
             if rng.random() < 0.5: opts["adapt"] = 1
