@@ -217,6 +217,26 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *  "hom_min"       auto     bins of hom tiles a run needs to qualify; 0 = auto = "warmup" / 4.  The default comes from a CPU measurement on two
  *                           parameter sets (~512 het-free bins inside a 3072-bin warm-up are harmless, ~1024 are not),
  *                           not from a GPU sweep.  Negative: PSMC_HIP_EINVAL
+ *  "wide_gap_tiles" 0       1: the wide fast path ("wide_fast", 129..1024 states) finds runs of missing data when its plan is made and crosses
+ *                           them with a transfer matrix instead of speculating into them and repairing them position by position.  A gap tile
+ *                           is a full tile of missing data only that is neither the first nor the last tile of its segment; a qualifying run
+ *                           is a maximal sequence of consecutive gap tiles of one segment that holds at least "wide_gap_min" bins.  Glued
+ *                           forward: every gap tile of a qualifying run and every later tile of the segment whose warm-up window (the
+ *                           "warmup" bins before it) overlaps a tile of the run; glued backward: the mirror.  A tile whose speculation
+ *                           starts at the true segment end in a direction is never glued in it.  Glued tiles do not speculate: once per
+ *                           E-step the matrix M of one full tile of missing data is built (n unit vectors swept through the forward
+ *                           sweep's own step), one chain per run and direction applies it tile by tile from the exit vector of the run's
+ *                           neighbour, the run's tiles are swept from the chain's vectors, and one walk per run goes on through the tiles
+ *                           glued behind it.  Every boundary is verified as any other, a failing one is repaired as before -- a failing
+ *                           run by chaining it again, which fast_diag counts as one head tile.  Results stay bit-reproducible and within
+ *                           the fast-mode tolerances; with "wide_ckpt", "wide_decode[_ckpt]", "wide_counts[_ckpt]", "wide_batch" and in
+ *                           group shards as without.  Device memory: n x (padded states) doubles for M, 8 MB at 1024 states.  Measured
+ *                           on the stress fixture (2.2 M bins, planted runs of 2e5 missing bins): profiles/wide_fast_timing.txt.
+ *                           0: plan and E-step are bit for bit what they are without the option, and nothing new is launched.  Accepted
+ *                           and ignored where the wide fast path does not run.  Other values: PSMC_HIP_EINVAL
+ *  "wide_gap_min"  auto     bins of missing data a run of gap tiles needs to qualify; 0 = auto = a quarter of the wide plan's warm-up (4096
+ *                           at the default 16384): a shorter run leaves at least 12288 data bins in a warm-up window, which
+ *                           profiles/wide_fast_timing.txt measured as sufficient.  Negative: PSMC_HIP_EINVAL
  *  "two_phase"     auto     2: the fused back half runs as two launches, odd tiles of the second list start from the exit
  *                           vector of the tile above instead of speculating backward; 0: every tile speculates, one
  *                           launch when the tiles fit one round.  auto: 2 with two rounds, 0 with one

@@ -94,8 +94,16 @@ int psmc_hip_cumask_probe(int device, int n_cus_a, int n_waves_a, int n_waves_b,
  * first `cap` entries: cls[b] = 0, 1 = gap tile (a full tile of missing data inside its segment), 2 = hom tile (a full het-free tile
  * inside its segment) outside a qualifying run, 3 = hom tile of a qualifying run; glue[b] = bit 0: tile b continues the forward item
  * of tile b - 1, bit 1: it continues the backward item of tile b + 1 -- what the plan rules set and what the context has learned
- * since. */
+ * since.  The plan of the wide fast path (129..1024 states, "wide_fast") is a different one: psmc_hip_wide_plan_tiles below. */
 int psmc_hip_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap);
+
+/* Diagnostic: the tiles of the current plan of the wide fast path ("wide_fast", 129..1024 states), as "wide_gap_tiles" of psmc_hip.h
+ * classified them.  Returns the number of tiles of the plan -- PSMC_HIP_ESTATE when there is none (no wide fast E-step since load /
+ * select / an option that changes the plan) -- and fills the first `cap` entries: cls[b] = 0, 1 = gap tile (a full tile of missing
+ * data, neither first nor last in its segment) outside a qualifying run, 2 = gap tile of a qualifying run; glue[b] = bit 0: glued
+ * forward (the tile does not speculate: its start vector comes from the transfer-matrix chain across the run, or from the walk
+ * behind it), bit 1: glued backward.  All zero with "wide_gap_tiles" = 0. */
+int psmc_hip_wide_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap);
 
 #ifdef __cplusplus
 }

@@ -293,3 +293,17 @@ extern "C" int psmc_hip_plan_tiles(psmc_hip_ctx *c, int32_t *cls, int32_t *glue,
 	}
 	return nc;
 }
+
+extern "C" int psmc_hip_wide_plan_tiles(psmc_hip_ctx *c, int32_t *cls, int32_t *glue, int cap)
+{
+	if (!c || cap < 0 || (cap > 0 && (!cls || !glue))) return PSMC_HIP_EINVAL;
+	// (the wide plan is made by the first wide fast E-step after load / select / an option that changes it: api_wide_fast.hip plan_wide)
+	if (c->plan_dirty || c->wf_chunks.empty()) return fail(c, PSMC_HIP_ESTATE, "wide_plan_tiles: no current wide plan (run a wide fast E-step first)");
+	const int nc = (int)c->wf_chunks.size();
+	const bool have = (int)c->wg_cls.size() == nc; // ("wide_gap_tiles" = 0: nothing was classified)
+	for (int b = 0; b < nc && b < cap; ++b) {
+		cls[b] = have ? c->wg_cls[b] : 0;
+		glue[b] = have ? c->wg_glue[b] & 3 : 0;
+	}
+	return nc;
+}

@@ -18,6 +18,15 @@
 // so (and "wide_decode" does not forbid it), and the V pass recomputes the rows between them and writes the slab's X rows beside its V
 // rows for the GEMM -- the same ranges, the same operands, the same bits.  The counts pass follows the interval the E-step kept.
 //
+// "wide_gap_tiles" = 1: runs of missing data are found when the plan is made (plan_wide_gaps; the rule: psmc_hip_ctx.h) and crossed by a
+// transfer-matrix chain (estep_wide_gap.hip) instead of speculation and position-by-position repair.  With a qualifying run in the plan
+// an E-step is, per direction: the speculative sweeps of the tiles that are not glued; the matrix of one full tile of missing data
+// (once, forward); then level by level -- a run whose chain starts from what the walk of the run before it computes is one level
+// later -- the chains of the level and ONE launch with the sweeps of the runs' tiles from the chain's vectors and one walk per run
+// through the tiles glued behind it; then the verify / repair rounds as below.  A repair walk stops in front of a run's first
+// chained tile; a run whose first chained tile heads a failing run is chained again for that round (one head tile in fast_diag).
+// Off, or without a qualifying run: the plan and the launches below, nothing else.
+//
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
 // of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,
 // which launches one wave per HEAD of a failing run (a failing tile whose predecessor in the sweep direction passed).  With "learn"
@@ -35,6 +44,10 @@ void free_wide_fast(psmc_hip_ctx *c)
 	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
 	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi, c->d_wc_V, c->d_wc_Xs, c->d_wc_P, c->d_wc_a, c->d_wc_out, c->d_wc_kr, c->d_wc_vrow};
 	for (void *q : p) if (q) (void)hipFree(q);
+	void *gp[] = {c->d_wg_glue, c->d_wg_list[0], c->d_wg_list[1], c->d_wg_spec[0], c->d_wg_spec[1], c->d_wg_runs[0], c->d_wg_runs[1], c->d_wg_again, c->d_wg_M};
+	for (void *q : gp) if (q) (void)hipFree(q);
+	c->d_wg_glue = c->d_wg_list[0] = c->d_wg_list[1] = c->d_wg_spec[0] = c->d_wg_spec[1] = nullptr;
+	c->d_wg_runs[0] = c->d_wg_runs[1] = c->d_wg_again = nullptr; c->d_wg_M = nullptr; c->wg_cap = 0; c->wg_m_cap = 0;
 	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
 	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
 	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
@@ -46,6 +59,104 @@ void free_wide_fast(psmc_hip_ctx *c)
 
 // rows of the X table over `bins` positions at one row per `iv` positions (iv = 8: the rows at p % 8 == 0, by absolute position)
 static inline int64_t wide_table_rows(int64_t bins, int iv) { return (bins + iv - 1) / iv; }
+
+// "wide_gap_tiles": runs of missing data in the wide plan (the rule: psmc_hip_ctx.h).  One launch of k_tile_class (estep_struct.hip; 1 =
+// missing data only) over the plan's tiles, with d_wf_dirty borrowed as scratch; everything else is host work.  The result is a function
+// of the selection, the data and the options, and lives with the plan.  Without a qualifying run nothing but wg_cls / wg_glue (for
+// psmc_hip_wide_plan_tiles) is left, and the E-step is the one without the option.
+static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
+{
+	const std::vector<Chunk> &ch = c->wf_chunks;
+	const int nc = (int)ch.size();
+	std::vector<int> cls(nc, 0);
+	if (launch_tile_class(c->stream, c->d_obs, c->d_wf_chunks, nc, c->d_wf_dirty) != 0) return fail(c, PSMC_HIP_EDEVICE, "k_tile_class", hipGetLastError());
+	HIPCHK(c, hipMemcpyAsync(cls.data(), c->d_wf_dirty, sizeof(int) * nc, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemsetAsync(c->d_wf_dirty, 0, sizeof(int) * nc, c->stream)); // (borrowed as scratch: back to what an allocation holds)
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	std::vector<int32_t> &gc = c->wg_cls, &glue = c->wg_glue;
+	gc.assign(nc, 0); glue.assign(nc, 0);
+	auto same = [&](int x, int y) { return x >= 0 && y >= 0 && x < nc && y < nc && ch[x].off == ch[y].off; };
+	for (int b = 0; b < nc; ++b) gc[b] = cls[b] == 1 && ch[b].lo > 1 && ch[b].hi < ch[b].L && ch[b].hi - ch[b].lo + 1 == T; // a FULL tile, not the first, not the last
+	const int64_t need = c->wide_gap_min > 0 ? c->wide_gap_min : W / 4;
+	std::vector<std::pair<int, int>> runs; // first and last tile of every qualifying run
+	for (int b = 0; b < nc;) {
+		if (!gc[b]) { ++b; continue; }
+		int e = b;
+		while (e < nc && same(b, e) && gc[e]) ++e;
+		if ((int64_t)(e - b) * T >= need) { runs.push_back({b, e - 1}); for (int t = b; t < e; ++t) gc[t] = 2; }
+		b = e;
+	}
+	if (runs.empty()) return 0;
+	std::vector<int> inq(nc + 1, 0), first(nc, 0); // prefix sums of "tile of a qualifying run"; the segment's first tile
+	for (int b = 0; b < nc; ++b) { inq[b + 1] = inq[b] + (gc[b] == 2); first[b] = same(b - 1, b) ? first[b - 1] : b; }
+	for (int b = 0; b < nc; ++b) { // the tile that holds position p of the segment is first + (p - 1) / T
+		const Chunk &k = ch[b];
+		if (!(k.flags & CHUNK_ANCHOR_F) && same(b - 1, b)) { // forward: positions lo - wf .. lo - 1, the tiles t0 .. b - 1
+			const int t0 = first[b] + (int)((std::max<int64_t>(1, (int64_t)k.lo - k.wf) - 1) / T);
+			if (gc[b] == 2 || (k.wf > 0 && inq[b] - inq[t0] > 0)) glue[b] |= 1;
+		}
+		if (!(k.flags & CHUNK_ANCHOR_B) && same(b, b + 1)) { // backward: positions hi + 1 .. hi + wb, the tiles b + 1 .. t1
+			const int t1 = first[b] + (int)((std::min<int64_t>(k.L, (int64_t)k.hi + k.wb) - 1) / T);
+			if (gc[b] == 2 || (k.wb > 0 && inq[t1 + 1] - inq[b + 1] > 0)) glue[b] |= 2;
+		}
+	}
+	// the chains, one direction at a time, in sweep order
+	struct Tmp { GapRun g; int walk, lev; };
+	for (int d = 0; d < 2; ++d) {
+		const int step = d ? -1 : 1, anchor = d ? CHUNK_ANCHOR_B : CHUNK_ANCHOR_F, bit = d ? 2 : 1;
+		std::vector<char> late(nc, 0); // swept behind a chain: does not speculate
+		std::vector<Tmp> tmp;
+		int last_lev = 0;
+		for (size_t i = 0; i < runs.size(); ++i) {
+			const std::pair<int, int> &R = runs[d ? runs.size() - 1 - i : i];
+			const int in = d ? R.second : R.first, out = d ? R.first : R.second; // the run's first and last tile in sweep order
+			int f = in; // the first tile from `in` on that is not anchored in this direction: there the chain starts
+			while (same(in, f) && (ch[f].flags & anchor)) f += step;
+			if (!same(in, f)) continue; // anchored through to the segment's end: every speculation behind the run is exact
+			Tmp t;
+			const bool inside = d ? f >= out : f <= out;
+			if (inside) { t.g = GapRun{f, std::abs(out - f) + 1}; t.walk = out + step; glue[f] |= d ? WG_FIRST_B : WG_FIRST_F; }
+			else { // the whole run is anchored: no tile to cross, but the tiles glued behind it still hang on one walk from the last anchored tile's exit
+				if (!(glue[f] & bit) || gc[f] == 2 || late[f]) continue; // (a later run's tile: that run's chain starts there)
+				t.g = GapRun{f, 0}; t.walk = f;
+			}
+			t.lev = late[f - step] ? last_lev + 1 : 0; // its first vector comes out of the walk before it
+			last_lev = t.lev;
+			for (int b = f; b != t.walk + step; b += step) late[b] = 1;
+			for (int b = t.walk + step; same(f, b) && (glue[b] & bit) && gc[b] != 2; b += step) late[b] = 1; // what the walk goes through at once
+			tmp.push_back(t);
+		}
+		std::stable_sort(tmp.begin(), tmp.end(), [](const Tmp &x, const Tmp &y) { return x.lev < y.lev; });
+		psmc_hip_ctx::WgDir &D = c->wg[d];
+		for (size_t i = 0; i < tmp.size(); ++i) {
+			const Tmp &t = tmp[i];
+			if (i == 0 || t.lev != tmp[i - 1].lev) { D.run_off.push_back((int32_t)D.runs.size()); D.list_off.push_back((int32_t)D.list.size()); }
+			D.runs.push_back(t.g); D.walk.push_back(t.walk);
+			for (int j = 0; j < t.g.count; ++j) D.list.push_back((t.g.first + step * j) | WG_OWN | WG_SINGLE);
+			D.list.push_back(t.walk | WG_OWN);
+		}
+		D.run_off.push_back((int32_t)D.runs.size()); D.list_off.push_back((int32_t)D.list.size());
+		for (int b = 0; b < nc; ++b) if (!late[b]) D.spec.push_back(b);
+	}
+	if (c->wg[0].runs.empty() && c->wg[1].runs.empty()) return 0;
+	int rc;
+	if (nc > c->wg_cap) {
+		c->wg_cap = 0;
+		if ((rc = dev_alloc(c, &c->d_wg_glue, (size_t)nc))) return rc;
+		for (int d = 0; d < 2; ++d) // (a run has at least one tile, a walk one more: no list is longer than the plan)
+			if ((rc = dev_alloc(c, &c->d_wg_list[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_spec[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_runs[d], (size_t)nc))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wg_again, (size_t)nc))) return rc;
+		c->wg_cap = nc;
+	}
+	HIPCHK(c, hipMemcpy(c->d_wg_glue, glue.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice));
+	for (int d = 0; d < 2; ++d) {
+		const psmc_hip_ctx::WgDir &D = c->wg[d];
+		if (!D.list.empty()) HIPCHK(c, hipMemcpy(c->d_wg_list[d], D.list.data(), sizeof(int32_t) * D.list.size(), hipMemcpyHostToDevice));
+		if (!D.spec.empty()) HIPCHK(c, hipMemcpy(c->d_wg_spec[d], D.spec.data(), sizeof(int32_t) * D.spec.size(), hipMemcpyHostToDevice));
+		if (!D.runs.empty()) HIPCHK(c, hipMemcpy(c->d_wg_runs[d], D.runs.data(), sizeof(GapRun) * D.runs.size(), hipMemcpyHostToDevice));
+	}
+	return 0;
+}
 
 // Tiles of T bins (option "chunk", else about WF_TILES tiles: four waves per SIMD of an MI355X -- the forward sweep fits four at
 // up to 110 VGPRs; the accumulate sweep, at 154 / 206 VGPRs, fits three (192 states) or two (256) and runs the tiles in two generations), every one speculating "warmup" bins in both directions -- by default WF_WARMUP, not the 3072 of
@@ -89,15 +200,22 @@ static int plan_wide(psmc_hip_ctx *c)
 	}
 	HIPCHK(c, hipMemcpy(c->d_wf_chunks, c->wf_chunks.data(), sizeof(Chunk) * nc, hipMemcpyHostToDevice));
 	c->wf_T = T; c->wf_W = W;
+	c->wg_cls.clear(); c->wg_glue.clear();
+	for (auto &d : c->wg) { d.runs.clear(); d.walk.clear(); d.list.clear(); d.run_off.clear(); d.list_off.clear(); d.spec.clear(); }
+	if (c->wide_gap_tiles && nc > 0 && (rc = plan_wide_gaps(c, T, W))) return rc;
 	c->plan_dirty = false;
 	return 0;
 }
 
 // verify / repair rounds of one direction; returns 0, or PSMC_HIP_ECONVERGE after max_rounds repair rounds
-static int wide_rounds(psmc_hip_ctx *c, WideLaunch &w, bool bwd, int &rounds, int &tiles)
+// (g: the plan has qualifying runs of missing data, "wide_gap_tiles" -- what their chains are launched with; else null)
+static int wide_rounds(psmc_hip_ctx *c, WideLaunch &w, bool bwd, int &rounds, int &tiles, WideGap *g = nullptr)
 {
 	const int nc = w.n_tiles;
-	std::vector<int> dirty(nc), heads;
+	std::vector<int> dirty(nc), heads, again;
+	std::vector<char> own;
+	std::vector<GapRun> chains;
+	int n_again = 0;
 	rounds = tiles = 0;
 	for (;;) {
 		HIPCHK(c, hipMemsetAsync(w.cnt + (bwd ? 1 : 0), 0, sizeof(int), w.stream));
@@ -110,12 +228,48 @@ static int wide_rounds(psmc_hip_ctx *c, WideLaunch &w, bool bwd, int &rounds, in
 		if (bad == 0) return 0;
 		if (rounds >= c->max_rounds) return PSMC_HIP_ECONVERGE;
 		heads.clear();
-		for (int b = 0; b < nc; ++b) {
-			if (!dirty[b]) continue;
+		auto follows = [&](int b) {
 			const int nb = bwd ? b + 1 : b - 1; // the neighbour it starts from
-			const bool follows = nb >= 0 && nb < nc && c->wf_chunks[nb].off == c->wf_chunks[b].off && dirty[nb];
-			if (!follows) heads.push_back(b);
+			return nb >= 0 && nb < nc && c->wf_chunks[nb].off == c->wf_chunks[b].off && dirty[nb];
+		};
+		if (g) {
+			// "wide_gap_tiles": a qualifying run whose first chained tile heads a failing run is chained again from the exit vector its
+			// neighbour holds now -- the chain, then its tiles' sweeps and its walk in the repair launch below (WG_OWN) -- instead of being walked
+			// position by position.  Its tiles count as failing for everybody else (no walk enters them, no head starts from them); the run is one head.
+			const psmc_hip_ctx::WgDir &D = c->wg[bwd ? 1 : 0];
+			const int step = bwd ? -1 : 1;
+			again.clear(); own.assign(nc, 0);
+			for (size_t i = 0; i < D.runs.size(); ++i) if (dirty[D.runs[i].first] && !follows(D.runs[i].first)) again.push_back((int)i);
+			for (int i : again) {
+				for (int j = 0; j < D.runs[i].count; ++j) own[D.runs[i].first + step * j] = 1;
+				own[D.walk[i]] = 2;
+			}
+			for (int b = 0; b < nc; ++b) if (own[b]) dirty[b] = 1;
+			n_again = 0;
+			if (!again.empty()) {
+				chains.clear();
+				for (int i : again) chains.push_back(D.runs[i]);
+				HIPCHK(c, hipMemcpyAsync(w.dirty, dirty.data(), sizeof(int) * nc, hipMemcpyHostToDevice, w.stream));
+				HIPCHK(c, hipMemcpyAsync(c->d_wg_again, chains.data(), sizeof(GapRun) * chains.size(), hipMemcpyHostToDevice, w.stream));
+				g->runs = c->d_wg_again; g->n_runs = (int)chains.size();
+				if (launch_wide_gap(*g, bwd ? WG_CHAIN_B : WG_CHAIN_F)) return fail(c, PSMC_HIP_EDEVICE, "k_wf_gapchain", hipGetLastError());
+				n_again = (int)again.size();
+			}
+			for (int b = 0; b < nc; ++b) {
+				if (own[b]) heads.push_back(b | WG_OWN | (own[b] == 1 ? WG_SINGLE : 0));
+				else if (dirty[b] && !follows(b)) heads.push_back(b);
+			}
+			int n_own = 0;
+			for (int b = 0; b < nc; ++b) n_own += own[b] != 0;
+			HIPCHK(c, hipMemcpyAsync(c->d_wf_list, heads.data(), sizeof(int) * heads.size(), hipMemcpyHostToDevice, w.stream));
+			w.list = c->d_wf_list; w.init = 0;
+			if (launch_wide_fast(w, bwd ? WF_ACC_GAP : WF_FWD_GAP, (int)heads.size()))
+				return fail(c, PSMC_HIP_EDEVICE, "wide repair", hipGetLastError());
+			HIPCHK(c, hipStreamSynchronize(w.stream)); // (heads, dirty and chains live on the host)
+			++rounds; tiles += (int)heads.size() - n_own + n_again;
+			continue;
 		}
+		for (int b = 0; b < nc; ++b) if (dirty[b] && !follows(b)) heads.push_back(b);
 		HIPCHK(c, hipMemcpyAsync(c->d_wf_list, heads.data(), sizeof(int) * heads.size(), hipMemcpyHostToDevice, w.stream));
 		w.list = c->d_wf_list;
 		if (launch_wide_fast(w, bwd ? WF_ACC_REPAIR : WF_FWD_REPAIR, (int)heads.size()))
@@ -194,14 +348,54 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	w.part = c->d_wf_part; w.LLpart = c->d_wf_ll; w.stage = c->d_stage; w.out = d_out;
 	c->report = FastReport{0, 0, 0, 0, 0, 0, 2};
 	c->wf_ran = true; c->wc_ran = false; c->last_fused = 3; c->wf_last_iv = iv;
-	if (launch_wide_fast(w, WF_FWD) || launch_wide_fast(w, WF_BWARM)) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
+	// "wide_gap_tiles" with a qualifying run in the plan: the tiles glued at plan time do not speculate.  Per direction: the sweeps of
+	// the others; the transfer matrix (once); then level by level the chains across the runs and ONE launch with the sweeps of the runs'
+	// tiles from the chain's vectors and the walks behind the runs (no work-group of it reads what another one of it writes).
+	const bool gaps = !c->wg[0].runs.empty() || !c->wg[1].runs.empty();
+	WideGap g;
+	memset(&g, 0, sizeof(g));
+	if (gaps) {
+		if (c->wg_m_cap < (size_t)n * S) {
+			c->wg_m_cap = 0;
+			if ((rc = dev_alloc(c, &c->d_wg_M, (size_t)n * S))) return rc;
+			c->wg_m_cap = (size_t)n * S;
+		}
+		g.stream = st; g.ns = S; g.n_states = n; g.waves = w.waves; g.ckpt = iv; g.T = c->wf_T; g.par = c->d_wf_par; g.chunks = c->d_wf_chunks;
+		g.M = c->d_wg_M; g.X = c->d_wf_X; g.xhi = w.xhi; g.bexit = c->d_wf_bexit; g.entry = c->d_wf_entry; g.bentry = c->d_wf_bentry;
+		w.glue = c->d_wg_glue;
+	}
+	auto gap_levels = [&](int d) -> int { // the chains of direction d and what hangs on them
+		const psmc_hip_ctx::WgDir &D = c->wg[d];
+		for (size_t l = 0; l + 1 < D.run_off.size(); ++l) {
+			g.runs = c->d_wg_runs[d] + D.run_off[l]; g.n_runs = D.run_off[l + 1] - D.run_off[l];
+			if (launch_wide_gap(g, d ? WG_CHAIN_B : WG_CHAIN_F)) return -1;
+			w.list = c->d_wg_list[d] + D.list_off[l]; w.init = 1;
+			if (launch_wide_fast(w, d ? WF_ACC_GAP : WF_FWD_GAP, D.list_off[l + 1] - D.list_off[l])) return -1;
+		}
+		w.list = c->d_wf_list; w.init = 0;
+		return 0;
+	};
+	if (!gaps) {
+		if (launch_wide_fast(w, WF_FWD) || launch_wide_fast(w, WF_BWARM)) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
+	} else {
+		w.list = c->d_wg_spec[0];
+		if (launch_wide_fast(w, WF_FWD_LIST, (int)c->wg[0].spec.size())) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
+		w.list = c->d_wg_spec[1];
+		if (launch_wide_fast(w, WF_BWARM_LIST, (int)c->wg[1].spec.size())) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
+		if (launch_wide_gap(g, WG_MAT) || gap_levels(0)) return fail(c, PSMC_HIP_EDEVICE, "wide gap chains (forward)", hipGetLastError());
+	}
 	int r = 0, t = 0;
-	rc = wide_rounds(c, w, false, r, t);
+	rc = wide_rounds(c, w, false, r, t, gaps ? &g : nullptr);
 	c->report.fwd_rounds = r; c->report.fwd_tiles = t;
 	if (rc == PSMC_HIP_ECONVERGE) return fail(c, rc, "fast mode (wide_fast): forward tile boundaries did not converge within max_rounds");
 	if (rc) return rc;
-	if (launch_wide_fast(w, WF_ACC)) return fail(c, PSMC_HIP_EDEVICE, "k_wf_acc", hipGetLastError());
-	rc = wide_rounds(c, w, true, r, t);
+	if (!gaps) {
+		if (launch_wide_fast(w, WF_ACC)) return fail(c, PSMC_HIP_EDEVICE, "k_wf_acc", hipGetLastError());
+	} else {
+		w.list = c->d_wg_spec[1];
+		if (launch_wide_fast(w, WF_ACC_LIST, (int)c->wg[1].spec.size()) || gap_levels(1)) return fail(c, PSMC_HIP_EDEVICE, "wide gap chains (backward)", hipGetLastError());
+	}
+	rc = wide_rounds(c, w, true, r, t, gaps ? &g : nullptr);
 	c->report.bwd_rounds = r; c->report.bwd_tiles = t;
 	if (rc == PSMC_HIP_ECONVERGE) return fail(c, rc, "fast mode (wide_fast): backward tile boundaries did not converge within max_rounds");
 	if (rc) return rc;

@@ -49,6 +49,14 @@
 //   k_wf_verify backward                     36     0 8       39     0 8       40   192 8       40   288 8       40   384 8
 //   k_wf_ll                                  37     0 8       38     0 8       38   192 8       38   288 8       38   384 8
 //   k_wf_reduce1 / 2                     8 / 42 VGPRs at every width, no LDS
+// "wide_gap_tiles" (GAP = 1: the listed tiles only, the registers of the plain kernels; GAP = 2: sweeps from a tile's own start
+// vector and the repairs of a plan with qualifying runs, the registers of the repairs; LDS as the kernel above them):
+//   k_wf_fwd    GAP 1 | CKPT, GAP 1     86  |  88   5      108  | 110  4      114  | 116  4      118  | 120  4      126  | 128  4
+//   k_wf_fwd    GAP 2 | CKPT, GAP 2     90  |  92   5      112  | 114  4      120  | 122  4      124  | 126  4      130  | 134  3
+//   k_wf_bwarm  LIST                         80     6           102    4           106    4           108    4           112    4
+//   k_wf_acc    GAP 1 | CKPT, GAP 1    154 3 | 196 2       206 2 | 256 2       216 2 | 220 2       220 2 | 224 2       226 2 | 226 2
+//   k_wf_acc    GAP 2 | CKPT, GAP 2    178 2 | 220 2       228 2 | 256+24 1    234 2 | 248 2       238 2 | 252 2       244 2 | 252 2
+// The kernels of the transfer-matrix chain itself: estep_wide_gap.hip.
 // The CKPT accumulate sweep at (4, 1) sits on the register edge (256 VGPRs; its repair takes 24 AGPRs and one wave per SIMD): the
 // one-wave order of astep and of the scaled steps of wide_prims.h is what keeps it there.  With CKPT the staged rows are at most
 // 115 KB of a compute unit's 160 KB of LDS (eight tiles of S = 256; four, two and two work-groups at W = 2, 3, 4).
@@ -65,11 +73,18 @@ namespace wide {
 // ------------------------------------------------------------------ forward
 // CKPT ("wide_ckpt"): X keeps the rows at p % 8 == 0 only (ckpt_row), and the tile's last row X_hi goes to xhi[b] -- what the
 // neighbour's verify and repair and k_wf_ll read; the accumulate sweep recomputes the rest.
-template <int NPL, int W, bool REPAIR, bool CKPT>
+// GAP ("wide_gap_tiles"; 0: the kernels as they were, the two last arguments unused): 1 = the speculative sweep over the listed tiles only
+// (the unglued tiles of the plan); 2 = the repair of a plan with qualifying runs -- a list entry is a tile and two flags, WG_OWN: start from
+// the tile's own entry[b] (what the transfer-matrix chain of estep_wide_gap.hip left there) instead of the neighbour's last row, WG_SINGLE:
+// do not walk on (a gap tile of a run: the chain has given every one its own start).  The walk never enters the first chained tile of a
+// run (glue & WG_FIRST_F): the chain crosses the run, not the walk.  `init`: the launch behind the chain at the start of an E-step -- no
+// verify has run, so there are no heads to respect, and a tile glued forward (glue & 1) has no start vector to compare with: walk on.
+template <int NPL, int W, bool REPAIR, bool CKPT, int GAP = 0>
 __global__ __launch_bounds__(64 * W) void k_wf_fwd(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                      const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
                                                      const int *__restrict__ dirty, int chain, double tol, double *__restrict__ X,
-                                                     double *__restrict__ inv, double *__restrict__ entry, double *__restrict__ xhi)
+                                                     double *__restrict__ inv, double *__restrict__ entry, double *__restrict__ xhi,
+                                                     const int *__restrict__ glue, int init)
 {
 	constexpr int S = 64 * NPL * W;
 	__shared__ double xs[2 * WX_SLOTS * W];
@@ -81,12 +96,15 @@ __global__ __launch_bounds__(64 * W) void k_wf_fwd(const double *__restrict__ pa
 	double e0[NPL], e1[NPL];
 	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
 	if (REPAIR) __builtin_amdgcn_s_setprio(3);
-	int b = REPAIR ? list[blockIdx.x] : (int)blockIdx.x;
+	int b = REPAIR || GAP ? list[blockIdx.x] : (int)blockIdx.x;
+	int own = 0, single = 0; // (GAP == 2; from the list: the same in every wave)
+	if (GAP == 2) { own = b & WG_OWN; single = b & WG_SINGLE; b &= WG_TILE; }
 	Chunk c = chunks[b];
 	double x[NPL];
 	int p0;
 	if (REPAIR) { // from the neighbour's X_{lo-1} (a repaired tile is never a segment's first)
-		if (CKPT) ld<NPL>(xhi + (int64_t)(b - 1) * S + k0, x); else ld<NPL>(X + (c.off + c.lo - 2) * S + k0, x);
+		if (GAP == 2 && own) ld<NPL>(entry + (int64_t)b * S + k0, x);
+		else if (CKPT) ld<NPL>(xhi + (int64_t)(b - 1) * S + k0, x); else ld<NPL>(X + (c.off + c.lo - 2) * S + k0, x);
 		p0 = c.lo;
 	} else {
 		const int ws = max(1, c.lo - c.wf);
@@ -125,10 +143,26 @@ __global__ __launch_bounds__(64 * W) void k_wf_fwd(const double *__restrict__ pa
 				}
 			}
 		}
-		if (!REPAIR || !chain) break;
+		if (!REPAIR || (GAP != 2 && !chain)) break;
 		// glued run: go on into the next tile while its start vector disagrees with this exit vector -- but not into a head of this
 		// launch, nor into the tile before one (that head reads the tile's last X row as its start vector)
 		const int nb = b + 1;
+		if (GAP == 2) { // (every condition from the list, the plan or the verify flags: the same in every wave)
+			if (single || nb >= n || !same_seg(chunks, b, nb) || (chunks[nb].flags & CHUNK_ANCHOR_F) || (glue[nb] & WG_FIRST_F)) break;
+			const bool through = init && (glue[nb] & 1); // glued at plan time and not swept yet: nothing to compare with
+			if (!through && !chain) break;
+			if (!init) {
+				if (head_f(chunks, dirty, nb)) break;
+				if (nb + 1 < n && same_seg(chunks, nb, nb + 1) && head_f(chunks, dirty, nb + 1)) break;
+			}
+			if (!through) {
+				double u[NPL];
+				ld<NPL>(entry + (int64_t)nb * S + k0, u);
+				if (tile_mismatch<NPL, W>(u, x, xc) <= tol) break;
+			}
+			b = nb; c = chunks[b]; p0 = c.lo;
+			continue;
+		}
 		if (nb >= n || !same_seg(chunks, b, nb) || (chunks[nb].flags & CHUNK_ANCHOR_F) || head_f(chunks, dirty, nb)) break;
 		if (nb + 1 < n && same_seg(chunks, nb, nb + 1) && head_f(chunks, dirty, nb + 1)) break;
 		double u[NPL];
@@ -139,14 +173,15 @@ __global__ __launch_bounds__(64 * W) void k_wf_fwd(const double *__restrict__ pa
 }
 
 // ------------------------------------------------------------------ backward
-template <int NPL, int W>
+// LIST ("wide_gap_tiles"): the listed tiles only (those not glued backward; the chain of estep_wide_gap.hip gives the others their start vectors)
+template <int NPL, int W, bool LIST = false>
 __global__ __launch_bounds__(64 * W) void k_wf_bwarm(const double *__restrict__ par, const uint8_t *__restrict__ obs,
-                                                       const Chunk *__restrict__ chunks, double *__restrict__ bentry)
+                                                       const Chunk *__restrict__ chunks, double *__restrict__ bentry, const int *__restrict__ list)
 {
 	constexpr int S = 64 * NPL * W;
 	__shared__ double xs[2 * WX_SLOTS * W];
 	Xchg<W> xc = make_xchg<W>(xs);
-	const int tid = threadIdx.x, k0 = NPL * tid, b = blockIdx.x;
+	const int tid = threadIdx.x, k0 = NPL * tid, b = LIST ? list[blockIdx.x] : (int)blockIdx.x;
 	const WaveScanMasks wm = wave_scan_masks(xc.lane);
 	const Chunk c = chunks[b];
 	const int top = min(c.hi, c.L - 1);
@@ -245,12 +280,14 @@ __device__ __forceinline__ void astep(const StructParN<NPL> &sc, const WaveScanM
 // entry[b] (the X_{lo-1} the tile was built on) or from X_1 = a0 e[o_1], into LDS (rows 8m+1 .. 8m+7: 7 S doubles, 56 KB at
 // W = 4, beside the exchange slots; every thread reads back what it wrote itself, so no barrier); then astep runs over them,
 // highest position first, X_{8m} read from the table.  The block bounds come from the tile descriptor alone.
-template <int NPL, int W, bool REPAIR, bool CKPT>
+// GAP: as k_wf_fwd, mirrored -- WG_OWN starts from the tile's own bentry[b], the walk goes down, never into the first chained tile
+// of a run from above (glue & WG_FIRST_B), and with `init` through the tiles glued backward (glue & 2).
+template <int NPL, int W, bool REPAIR, bool CKPT, int GAP = 0>
 __global__ __launch_bounds__(64 * W) void k_wf_acc(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                      const Chunk *__restrict__ chunks, int n, const int *__restrict__ list,
                                                      const int *__restrict__ dirty, int chain, double tol, const double *__restrict__ X,
                                                      const double *__restrict__ inv, const double *__restrict__ entry, double *__restrict__ bentry,
-                                                     double *__restrict__ bexit, double *__restrict__ part)
+                                                     double *__restrict__ bexit, double *__restrict__ part, const int *__restrict__ glue, int init)
 {
 	constexpr int S = 64 * NPL * W;
 	__shared__ double xs[2 * WX_SLOTS * W];
@@ -262,9 +299,11 @@ __global__ __launch_bounds__(64 * W) void k_wf_acc(const double *__restrict__ pa
 	double e0[NPL], e1[NPL];
 	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
 	if (REPAIR) __builtin_amdgcn_s_setprio(3);
-	int b = REPAIR ? list[blockIdx.x] : (int)blockIdx.x;
+	int b = REPAIR || GAP ? list[blockIdx.x] : (int)blockIdx.x;
+	int own = 0, single = 0; // (GAP == 2; from the list: the same in every wave)
+	if (GAP == 2) { own = b & WG_OWN; single = b & WG_SINGLE; b &= WG_TILE; }
 	double x[NPL];
-	if (REPAIR) { ld<NPL>(bexit + (int64_t)(b + 1) * S + k0, x); st<NPL>(bentry + (int64_t)b * S + k0, x); }
+	if (REPAIR && !(GAP == 2 && own)) { ld<NPL>(bexit + (int64_t)(b + 1) * S + k0, x); st<NPL>(bentry + (int64_t)b * S + k0, x); }
 	else ld<NPL>(bentry + (int64_t)b * S + k0, x);
 	for (;;) {
 		const Chunk c = chunks[b];
@@ -343,10 +382,27 @@ __global__ __launch_bounds__(64 * W) void k_wf_acc(const double *__restrict__ pa
 		}
 #pragma unroll
 		for (int q = 0; q < WACC; ++q) st<NPL>(out + q * S, acc[q]);
-		if (!REPAIR || !chain || top < lo) break;
+		if (!REPAIR || (GAP != 2 && !chain) || top < lo) break;
 		// glued run: go on into the tile below while its start vector disagrees with this exit vector -- but not into a head of this
 		// launch, nor into the tile above one (that head reads the tile's bexit as its start vector)
 		const int nb = b - 1;
+		if (GAP == 2) { // (every condition from the list, the plan or the verify flags: the same in every wave)
+			if (single || nb < 0 || !same_seg(chunks, nb, b) || (chunks[nb].flags & CHUNK_ANCHOR_B) || (glue[nb] & WG_FIRST_B)) break;
+			const bool through = init && (glue[nb] & 2); // glued at plan time and not swept yet: nothing to compare with
+			if (!through && !chain) break;
+			if (!init) {
+				if (head_b(chunks, dirty, n, nb)) break;
+				if (nb - 1 >= 0 && same_seg(chunks, nb - 1, nb) && head_b(chunks, dirty, n, nb - 1)) break;
+			}
+			if (!through) {
+				double u[NPL];
+				ld<NPL>(bentry + (int64_t)nb * S + k0, u);
+				if (tile_mismatch<NPL, W>(u, x, xc) <= tol) break;
+			}
+			b = nb;
+			st<NPL>(bentry + (int64_t)b * S + k0, x);
+			continue;
+		}
 		if (nb < 0 || !same_seg(chunks, nb, b) || (chunks[nb].flags & CHUNK_ANCHOR_B) || head_b(chunks, dirty, n, nb)) break;
 		if (nb - 1 >= 0 && same_seg(chunks, nb - 1, nb) && head_b(chunks, dirty, n, nb - 1)) break;
 		double u[NPL];
@@ -468,23 +524,42 @@ template <int NPL, int W> static int launch_all(const WideLaunch &w, int what, i
 	const bool ck = w.ckpt == WCK;                      // "wide_ckpt": X at every 8th position, the tiles' last rows in w.xhi
 	const double *xhi = ck ? w.xhi : nullptr;
 	if (w.ckpt != 1 && !(ck && w.xhi)) return -1;
+	if (what >= WF_FWD_LIST && (n_list <= 0 || !w.list || !w.glue)) return n_list == 0 ? 0 : -1; // (an empty list: nothing to launch)
 	switch (what) {
 	case WF_FWD:
-		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, W, false, true>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi);
-		else hipLaunchKernelGGL((k_wf_fwd<NPL, W, false, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi);
+		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, W, false, true>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi, nullptr, 0);
+		else hipLaunchKernelGGL((k_wf_fwd<NPL, W, false, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi, nullptr, 0);
 		break;
 	case WF_FWD_REPAIR:
-		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, W, true, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi);
-		else hipLaunchKernelGGL((k_wf_fwd<NPL, W, true, false>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi);
+		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, W, true, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi, nullptr, 0);
+		else hipLaunchKernelGGL((k_wf_fwd<NPL, W, true, false>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi, nullptr, 0);
 		break;
-	case WF_BWARM: hipLaunchKernelGGL((k_wf_bwarm<NPL, W>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, w.bentry); break;
+	case WF_BWARM: hipLaunchKernelGGL((k_wf_bwarm<NPL, W>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, w.bentry, nullptr); break;
 	case WF_ACC:
-		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, W, false, true>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
-		else hipLaunchKernelGGL((k_wf_acc<NPL, W, false, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, W, false, true>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, nullptr, 0);
+		else hipLaunchKernelGGL((k_wf_acc<NPL, W, false, false>), dim3(nc), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, nullptr, 0);
 		break;
 	case WF_ACC_REPAIR:
-		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, W, true, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
-		else hipLaunchKernelGGL((k_wf_acc<NPL, W, true, false>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part);
+		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, W, true, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, nullptr, 0);
+		else hipLaunchKernelGGL((k_wf_acc<NPL, W, true, false>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, nullptr, 0);
+		break;
+	// "wide_gap_tiles": the listed speculative sweeps (w.list, n_list tiles) and the sweeps / repairs of a plan with qualifying runs
+	case WF_FWD_LIST:
+		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, W, false, true, 1>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi, w.glue, 0);
+		else hipLaunchKernelGGL((k_wf_fwd<NPL, W, false, false, 1>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.xhi, w.glue, 0);
+		break;
+	case WF_FWD_GAP:
+		if (ck) hipLaunchKernelGGL((k_wf_fwd<NPL, W, true, true, 2>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi, w.glue, w.init);
+		else hipLaunchKernelGGL((k_wf_fwd<NPL, W, true, false, 2>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.xhi, w.glue, w.init);
+		break;
+	case WF_BWARM_LIST: hipLaunchKernelGGL((k_wf_bwarm<NPL, W, true>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, w.bentry, w.list); break;
+	case WF_ACC_LIST:
+		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, W, false, true, 1>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, w.glue, 0);
+		else hipLaunchKernelGGL((k_wf_acc<NPL, W, false, false, 1>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, 0, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, w.glue, 0);
+		break;
+	case WF_ACC_GAP:
+		if (ck) hipLaunchKernelGGL((k_wf_acc<NPL, W, true, true, 2>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, w.glue, w.init);
+		else hipLaunchKernelGGL((k_wf_acc<NPL, W, true, false, 2>), dim3(n_list), dim3(T), 0, st, w.par, w.obs, w.chunks, nc, w.list, w.dirty, w.chain, w.tol, w.X, w.inv, w.entry, w.bentry, w.bexit, w.part, w.glue, w.init);
 		break;
 	case WF_VERIFY_F: hipLaunchKernelGGL((k_wf_verify<NPL, W, false>), dim3(nc), dim3(T), 0, st, w.chunks, nc, w.tol, w.X, xhi, w.entry, w.bexit, w.dirty, w.cnt, w.warm); break;
 	case WF_VERIFY_B: hipLaunchKernelGGL((k_wf_verify<NPL, W, true>), dim3(nc), dim3(T), 0, st, w.chunks, nc, w.tol, w.X, xhi, w.bentry, w.bexit, w.dirty, w.cnt + 1, w.warm + 1); break;

@@ -1,0 +1,158 @@
+// estep_wide_gap.hip -- the wide fast path (estep_wide_fast.hip, 129..1024 states) across runs of missing data: option
+// "wide_gap_tiles" (api_wide_fast.hip plans and drives it).
+//
+// Inside a run of `N` bins the emission is 1 for every state, so a full tile of T missing bins maps its start vector by one fixed
+// matrix, M = a^T to the power T, whatever the tile: forward X_{hi} = X_{lo-1} M, backward bt_{lo} = M bt_{hi+1}, both up to the
+// positive factors the sweeps scale by.  A speculative warm-up cannot cross such a run (the chain forgets at the matrix's second
+// eigenvalue alone), and a repair walks it position by position.  Here the run is crossed tile by tile:
+//   k_wf_gapmat    once per E-step (the parameters move): row k of M is the unit vector of state k swept T bins through fstep
+//                  (wide_prims.h), the forward sweep's own step, under the missing symbol; one work-group per row, in the layout of
+//                  the sweeps.  The steps are the UNSCALED ones: what the sweep does at p % 4 == 0 on top is a multiplication of every
+//                  state by one power of two, which is exact -- so a row here is the sweep's row with those factors undone, and all
+//                  rows are on one scale (the matrix is stochastic under the missing symbol: a row's sum stays 1 up to rounding).
+//   k_wf_gapchain  one work-group of 1024 threads per qualifying run and direction: reads the vector the run is entered with,
+//                  applies M once per tile and writes every tile's start vector (wide_fast.h GapRun).  Forward x <- x M: one thread
+//                  per column, the rows split into 1024 / S contiguous ranges whose partial sums are added lowest range first.
+//                  Backward y <- M y: one wave per row (rows wave, wave + 16, ...), every lane the columns lane, lane + 64, ...
+//                  in ascending order, then wave_total's fixed order.  The vector is normalised to sum 1 after every application
+//                  (every consumer of entry / bentry is invariant to a positive factor).  No atomics, every sum in a fixed order:
+//                  the same bits at every call.
+// Correctness does not rest on the chain: k_wf_verify tests the boundaries of the chained tiles like any other, and the structured
+// sweep of a gap tile from the chain's vector is what fills X, inv and the statistics.
+//
+// Resources (hipcc -O3, gfx950, make resources; scratch is 0 everywhere): VGPRs | LDS bytes | waves per SIMD
+//   kernel                               (3,1) S=192      (4,1) S=256      (4,2) S=512      (4,3) S=768      (4,4) S=1024
+//   k_wf_gapmat                              62     0 8       78     0 6       82   192 5       85   288 5       89   384 5
+//   k_wf_gapchain forward                    68  9224 7       68 10248 7       68 12296 7       48 12296 8       46 16392 8
+//   k_wf_gapchain backward                   28  9224 8       30 10248 8       46 12296 8       64 12296 8       82 16392 5
+// (the chain is one work-group of 16 waves whatever the width: four waves per SIMD of one compute unit)
+#include <hip/hip_runtime.h>
+#include "wave_prims.h"
+#include "struct_prims.h"
+#include "psmc_hip_internal.h"
+#include "wide_fast.h"
+#include "wide_prims.h"
+
+namespace psmc {
+namespace wide {
+
+template <int NPL, int W>
+__global__ __launch_bounds__(64 * W) void k_wf_gapmat(const double *__restrict__ par, int T, double *__restrict__ M)
+{
+	constexpr int S = 64 * NPL * W;
+	__shared__ double xs[2 * WX_SLOTS * W];
+	Xchg<W> xc = make_xchg<W>(xs);
+	const int tid = threadIdx.x, k0 = NPL * tid, k = blockIdx.x;
+	const WaveScanMasks wm = wave_scan_masks(xc.lane);
+	StructParN<NPL> sc;
+	load_par<NPL, S>(par, k0, true, sc);
+	double e0[NPL], e1[NPL]; // (the missing symbol reads neither)
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+	double x[NPL];
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) x[i] = k0 + i == k ? 1.0 : 0.0;
+	for (int p = 0; p < T; ++p) fstep<NPL, W, false, false>(sc, wm, 2, e0, e1, x, 1.0, xc); // (T: the same in every wave)
+	st<NPL>(M + (int64_t)k * S + k0, x);
+}
+
+constexpr int WG_THREADS = 1024;
+
+template <int S, bool BWD>
+__global__ __launch_bounds__(WG_THREADS) void k_wf_gapchain(const double *__restrict__ M, int n, const Chunk *__restrict__ chunks,
+                                                              const GapRun *__restrict__ runs, const double *__restrict__ X,
+                                                              const double *__restrict__ xhi, const double *__restrict__ bexit,
+                                                              double *__restrict__ dst)
+{
+	constexpr int KS = WG_THREADS / S; // forward: ranges of rows (5 at S = 192, 4, 2, 1, 1)
+	__shared__ double v[S], y[KS * S], tot;
+	const GapRun r = runs[blockIdx.x];
+	const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+	const double *src;
+	if (BWD) src = bexit + (int64_t)(r.first + 1) * S;
+	else if (xhi) src = xhi + (int64_t)(r.first - 1) * S;
+	else { const Chunk c = chunks[r.first - 1]; src = X + (c.off + c.hi - 1) * S; }
+	if (t < S) {
+		const double a = src[t];
+		v[t] = a; y[t] = 0.0; // (backward: rows n .. S - 1 of M do not exist, those states stay 0)
+		dst[(int64_t)r.first * S + t] = a;
+	}
+	__syncthreads();
+	for (int i = 1; i <= r.count; ++i) { // (r, n: the same in every thread -- every barrier below is reached by all)
+		if (!BWD) {
+			const int g = t / S, col = t - g * S, kc = (n + KS - 1) / KS;
+			if (g < KS) {
+				const int k1 = min(n, (g + 1) * kc);
+				double acc = 0.0;
+#pragma unroll 8
+				for (int k = g * kc; k < k1; ++k) acc = __builtin_fma(v[k], M[(int64_t)k * S + col], acc);
+				y[g * S + col] = acc;
+			}
+			__syncthreads();
+			if (KS > 1 && t < S) {
+				double acc = y[t];
+#pragma unroll
+				for (int q = 1; q < KS; ++q) acc += y[q * S + t];
+				y[t] = acc; // (only this thread reads the column's partial sums)
+			}
+		} else {
+			for (int k = wave; k < n; k += WG_THREADS / 64) {
+				const double *row = M + (int64_t)k * S;
+				double acc = 0.0;
+#pragma unroll
+				for (int j = 0; j < S / 64; ++j) acc = __builtin_fma(row[lane + 64 * j], v[lane + 64 * j], acc);
+				acc = wave_total(acc);
+				if (lane == 0) y[k] = acc;
+			}
+		}
+		__syncthreads();
+		if (wave == 0) { // the sum of the new vector: per lane ascending, then wave_total
+			double s = 0.0;
+#pragma unroll
+			for (int j = 0; j < S / 64; ++j) s += y[lane + 64 * j];
+			s = wave_total(s);
+			if (lane == 0) tot = 1.0 / s;
+		}
+		__syncthreads();
+		if (t < S) {
+			const double a = y[t] * tot;
+			v[t] = a;
+			dst[(int64_t)(BWD ? r.first - i : r.first + i) * S + t] = a;
+		}
+		__syncthreads();
+	}
+}
+
+template <int NPL, int W> static int launch_gap(const WideGap &w, int what)
+{
+	constexpr int S = 64 * NPL * W;
+	hipStream_t st = w.stream;
+	switch (what) {
+	case WG_MAT: hipLaunchKernelGGL((k_wf_gapmat<NPL, W>), dim3(w.n_states), dim3(64 * W), 0, st, w.par, w.T, w.M); break;
+	case WG_CHAIN_F:
+		if (w.n_runs > 0) hipLaunchKernelGGL((k_wf_gapchain<S, false>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, w.ckpt == WCK ? w.xhi : nullptr, w.bexit, w.entry);
+		break;
+	case WG_CHAIN_B:
+		if (w.n_runs > 0) hipLaunchKernelGGL((k_wf_gapchain<S, true>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, nullptr, w.bexit, w.bentry);
+		break;
+	default: return -1;
+	}
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+} // namespace wide
+
+int launch_wide_gap(const WideGap &w, int what)
+{
+	if (w.waves > 1 ? w.ns != 256 * w.waves : (w.ns != 192 && w.ns != 256)) return -1;
+	if (w.ckpt != 1 && !(w.ckpt == wide::WCK && w.xhi)) return -1;
+	switch (w.ns) {
+	case 192: return wide::launch_gap<3, 1>(w, what);
+	case 256: return wide::launch_gap<4, 1>(w, what);
+	case 512: return wide::launch_gap<4, 2>(w, what);
+	case 768: return wide::launch_gap<4, 3>(w, what);
+	case 1024: return wide::launch_gap<4, 4>(w, what);
+	}
+	return -1;
+}
+
+} // namespace psmc

@@ -278,6 +278,33 @@ struct psmc_hip_ctx {
 	double *d_wc_V = nullptr, *d_wc_P = nullptr, *d_wc_a = nullptr, *d_wc_out = nullptr;
 	KRange *d_wc_kr = nullptr; int32_t *d_wc_vrow = nullptr;
 	size_t wc_v_cap = 0, wc_p_cap = 0, wc_kr_cap = 0, wc_vrow_cap = 0; // rows x width | doubles | ranges | tiles
+	// "wide_gap_tiles" = 1: plan_wide (api_wide_fast.hip) classifies the tiles of the wide plan with k_tile_class.  A GAP TILE is a full
+	// tile (exactly T bins) of missing data only that is neither the first nor the last of its segment; a QUALIFYING RUN is a maximal
+	// sequence of consecutive gap tiles of one segment that holds at least "wide_gap_min" bins (0 = auto: a quarter of the plan's
+	// warm-up -- a shorter run leaves three quarters of a warm-up window as data, 12288 bins at the default, which
+	// profiles/wide_fast_timing.txt measured as sufficient).  Glued forward: every gap tile of a qualifying run and every later tile of
+	// the segment whose window lo - wf .. lo - 1 overlaps a tile of the run; backward: the mirror with hi + 1 .. hi + wb; never a tile
+	// anchored in that direction.  Glued tiles do not speculate: the runs are crossed by the transfer-matrix chain of estep_wide_gap.hip.
+	// wg_cls: 0, 1 = gap tile outside a qualifying run, 2 = gap tile of one; wg_glue: bit 0 forward, bit 1 backward, WG_FIRST_F / WG_FIRST_B
+	// (wide_fast.h).  All empty / zero with the option off or without a qualifying run: then the E-step is the one without the option.
+	int wide_gap_tiles = 0, wide_gap_min = 0;
+	std::vector<int32_t> wg_cls, wg_glue;
+	// One direction of the plan's chains (d = 0 forward, 1 backward).  A chain starts behind the run's tiles that are anchored in its
+	// direction (their speculation is exact) and ends with the start vector of the first tile behind the run, where one walk goes on
+	// through the tiles glued behind it (`walk`).  A chain whose first vector comes out of the walk of the run before it in the segment
+	// (two runs closer than a warm-up) is one LEVEL later: levels run one after the other, chains and sweeps of a level side by side.
+	struct WgDir {
+		std::vector<GapRun> runs;           // by level
+		std::vector<int32_t> walk;          // [runs] the tile its walk starts on
+		std::vector<int32_t> list;          // the tiles a level sweeps behind its chains (WG_OWN; the run's own tiles WG_SINGLE), by level
+		std::vector<int32_t> run_off, list_off; // [levels + 1]
+		std::vector<int32_t> spec;          // the tiles that speculate: everything else
+	};
+	WgDir wg[2];
+	int *d_wg_glue = nullptr, *d_wg_list[2] = {nullptr, nullptr}, *d_wg_spec[2] = {nullptr, nullptr};
+	GapRun *d_wg_runs[2] = {nullptr, nullptr}, *d_wg_again = nullptr; // ... and the chains a repair round runs again
+	double *d_wg_M = nullptr; size_t wg_m_cap = 0; // [n][padded width] the transfer matrix of a full gap tile
+	int wg_cap = 0;
 };
 // the padded width of the wide fast path's own tables (api_wide_fast.hip writes them, api_decode.hip reads them): c->ns (192 or 256)
 // up to 256 states, beyond them the next multiple of 256 -- one wave of the tile per 256 states (c->ns stays what the wide exact

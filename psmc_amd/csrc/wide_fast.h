@@ -7,7 +7,18 @@
 
 namespace psmc {
 
-enum { WF_FWD, WF_FWD_REPAIR, WF_BWARM, WF_ACC, WF_ACC_REPAIR, WF_VERIFY_F, WF_VERIFY_B, WF_FINISH };
+enum { WF_FWD, WF_FWD_REPAIR, WF_BWARM, WF_ACC, WF_ACC_REPAIR, WF_VERIFY_F, WF_VERIFY_B, WF_FINISH,
+       // "wide_gap_tiles" (a plan with qualifying runs of missing data): the sweeps over the tiles of WideLaunch::list only, and the
+       // sweeps / repairs that may start from a tile's own start vector (list entries carry WG_OWN / WG_SINGLE)
+       WF_FWD_LIST, WF_FWD_GAP, WF_BWARM_LIST, WF_ACC_LIST, WF_ACC_GAP };
+
+// a list entry of WF_FWD_GAP / WF_ACC_GAP: the tile, and
+constexpr int WG_OWN = 1 << 30;    // start from the tile's own entry / bentry (the transfer-matrix chain wrote it), not from the neighbour's exit vector
+constexpr int WG_SINGLE = 1 << 29; // sweep this tile only: do not walk on
+constexpr int WG_TILE = WG_SINGLE - 1;
+// WideLaunch::glue[b]: bit 0 = glued forward, bit 1 = glued backward (psmc_hip_wide_plan_tiles), and
+constexpr int WG_FIRST_F = 4;      // the first tile the forward chain of a qualifying run writes: no forward walk enters it
+constexpr int WG_FIRST_B = 8;      // ... and the backward chain's (the run's highest chained tile): no backward walk enters it
 
 struct WideLaunch {
 	hipStream_t stream;
@@ -23,9 +34,31 @@ struct WideLaunch {
 	unsigned long long *warm;         // [2] largest mismatch of the last verify, forward | backward (bits of a double)
 	double *X, *inv, *entry, *bentry, *bexit, *part, *LLpart, *stage, *out;
 	double *xhi;                      // ckpt == 8: [n_tiles][ns] every tile's last row X_hi (what its neighbour's verify / repair and the LL read)
+	const int *glue;                  // "wide_gap_tiles": [n_tiles] the plan's glue bits and WG_FIRST_F / WG_FIRST_B; null without a qualifying run
+	int init;                         // WF_FWD_GAP / WF_ACC_GAP: 1 = the launch behind the chain at the start of an E-step (no verify flags yet; walks go through glued tiles)
 };
 
 int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wide_fast.hip; -1: ns and waves do not go together, or ckpt is not 1 or 8 with xhi
+
+// The transfer-matrix chain across qualifying runs of missing data ("wide_gap_tiles", estep_wide_gap.hip).  One chain per run and
+// direction.  Forward: v = the exit vector of tile first - 1 (its last X row; ckpt == 8: xhi), entry[first] = v, then `count` times
+// v <- v M (normalised), entry[first + i] = v.  Backward: v = bexit[first + 1], bentry[first] = v, then v <- M v, bentry[first - i] = v.
+struct GapRun { int32_t first, count; };
+enum { WG_MAT, WG_CHAIN_F, WG_CHAIN_B };
+
+struct WideGap {
+	hipStream_t stream;
+	int ns, n_states, waves, ckpt;    // as WideLaunch
+	int T;                            // WG_MAT: bins of a full tile -- M = (the forward step under the missing symbol)^T
+	const double *par;                // as WideLaunch
+	const Chunk *chunks;
+	double *M;                        // [n_states][ns]: row k = the unit vector of state k swept T bins forward, unscaled
+	const GapRun *runs; int n_runs;   // WG_CHAIN_*: the chains of this launch, one work-group each
+	const double *X, *xhi, *bexit;    // where the chains start
+	double *entry, *bentry;           // what they write
+};
+
+int launch_wide_gap(const WideGap &w, int what); // estep_wide_gap.hip; -1: ns and waves do not go together
 
 // decoding of ONE segment: its tiles are t0 .. t0 + n_tiles - 1 of the plan; every output pointer is the segment's own buffer
 enum { WP_PATH, WP_POST, WP_REC, WP_POST_REC, WP_COUNTS, WP_SCALES };

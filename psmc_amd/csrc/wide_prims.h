@@ -1,5 +1,6 @@
 // wide_prims.h -- what the kernels of the wide fast path share (estep_wide_fast.hip: the E-step; estep_wide_post.hip: decoding
-// from its tables; estep_wide_counts.hip: the V rows of the count matrix).  A tile is ONE work-group of W waves at the padded width
+// from its tables; estep_wide_counts.hip: the V rows of the count matrix; estep_wide_gap.hip: the rows of the transfer matrix of a tile
+// of missing data).  A tile is ONE work-group of W waves at the padded width
 // S = 64 NPL W: (NPL, W) = (3, 1), (4, 1) at 192 / 256 states, (4, 2), (4, 3), (4, 4) at 512 / 768 / 1024.  Thread t holds the NPL
 // adjacent states k = NPL t + i, so wave w holds [64 NPL w, 64 NPL (w + 1)).  Here: the whole-wave scans, the exchange of
 // wave-uniform values between the waves of a tile (Xchg), what crosses the tile through it (sum, mismatch), the parameter block,

@@ -39,7 +39,7 @@ EXPORTS = [
 DIAG_EXPORTS = [
     "psmc_hip_selftest", "psmc_hip_last_timing", "psmc_hip_microbench", "psmc_hip_stream_probe", "psmc_hip_hbm_probe",
     "psmc_hip_load_probe", "psmc_hip_load_probe_st", "psmc_hip_pipe_probe", "psmc_hip_pipe_probe2", "psmc_hip_place_probe",
-    "psmc_hip_cumask_probe", "psmc_hip_plan_tiles",
+    "psmc_hip_cumask_probe", "psmc_hip_plan_tiles", "psmc_hip_wide_plan_tiles",
 ]
 
 
@@ -339,6 +339,22 @@ class HipEStep:
         n2 = d.psmc_hip_plan_tiles(self.h, cls.ctypes.data_as(_i32p), glue.ctypes.data_as(_i32p), n)
         if n2 < 0:
             self._chk(n2, "plan_tiles")
+        return dict(cls=cls, glue=glue)
+
+    def wide_plan_tiles(self):
+        """Per tile of the current plan of the wide fast path (psmc_hip_wide_plan_tiles, the diagnostic library): dict(cls, glue) of
+        int32 arrays -- cls 0, 1 = gap tile outside a qualifying run, 2 = gap tile of a qualifying run (options wide_gap_tiles=1,
+        wide_gap_min=bins); glue bit 0 = glued forward, bit 1 = glued backward.  HipError (invalid state) before the first wide fast
+        E-step."""
+        d = load_diag()
+        d.psmc_hip_wide_plan_tiles.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int]
+        n = d.psmc_hip_wide_plan_tiles(self.h, None, None, 0)
+        if n < 0:
+            self._chk(n, "wide_plan_tiles")
+        cls = np.zeros(n, dtype=np.int32); glue = np.zeros(n, dtype=np.int32)
+        n2 = d.psmc_hip_wide_plan_tiles(self.h, cls.ctypes.data_as(_i32p), glue.ctypes.data_as(_i32p), n)
+        if n2 < 0:
+            self._chk(n2, "wide_plan_tiles")
         return dict(cls=cls, glue=glue)
 
     def tables(self, seg, want_b=True):

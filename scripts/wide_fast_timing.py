@@ -33,6 +33,8 @@
       table's bytes and interval beside each time, and the device memory in use before the context exists and after its E-steps
       (hipMemGetInfo: the context keeps every buffer, so the difference is what the run needs)
 
+  --gap-tiles sets "wide_gap_tiles" = 1 on the wide contexts of every leg (the exact-kernel contexts are what they are).
+
   --ckpt sets "wide_ckpt" = 1 on the wide contexts of (a) and (e): X at every 8th bin only, the rest recomputed in the accumulate
   sweep.  Beside every time, (a) and (e) print what psmc_hip_wide_table_info reports: the bytes of X the context holds.
   With --decode it sets "wide_ckpt" = 1 and "wide_decode_ckpt" = 1 on the wide context of (d): the decoding E-step keeps checkpoints
@@ -42,7 +44,7 @@ Library calls are synchronous.  Writes one JSON object to stdout (progress on st
 
     python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
     python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
-    python scripts/wide_fast_timing.py --stress --states 200,300,1024 --steps 4 --exact-steps 0 [--ckpt]
+    python scripts/wide_fast_timing.py --stress --states 200,300,1024 --steps 4 --exact-steps 0 [--ckpt] [--gap-tiles]
     python scripts/wide_fast_timing.py --decode --stress --states 300,1024
     python scripts/wide_fast_timing.py --decode --stress --states 200,300,1024 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
@@ -93,6 +95,9 @@ def params_seq(n, steps, seed=11):
     return out
 
 
+GAP_OPTS = {}   # --gap-tiles: {"wide_gap_tiles": 1} on the wide contexts of every leg
+
+
 def table_info(es):
     """psmc_hip_wide_table_info; None with a library from before the entry point existed (PSMC_HIP_LIB: A/B against an older build)"""
     try:
@@ -104,7 +109,7 @@ def table_info(es):
 def library_part(hip, segs, n, steps, exact_steps, ckpt=False):
     ps = params_seq(n, steps)
     r = {}
-    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1)
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, **GAP_OPTS)
     if ckpt:
         es.set_option("wide_ckpt", 1)
     es.load_segments(segs)
@@ -112,10 +117,11 @@ def library_part(hip, segs, n, steps, exact_steps, ckpt=False):
     for a, e, a0 in ps:
         t = time.perf_counter(); es.estep_factored(a, e[:2], a0); ms.append((time.perf_counter() - t) * 1e3)
         d = es.fast_diag()
-        rounds.append(dict(fwd_rounds=d["fwd_rounds"], bwd_rounds=d["bwd_rounds"], fwd_tiles=d["fwd_tiles"], bwd_tiles=d["bwd_tiles"]))
+        rounds.append(dict(fwd_rounds=d["fwd_rounds"], bwd_rounds=d["bwd_rounds"], fwd_tiles=d["fwd_tiles"], bwd_tiles=d["bwd_tiles"],
+                           warm_err_fwd=d["warm_err_fwd"], warm_err_bwd=d["warm_err_bwd"]))
     d = es.fast_diag()
     ti = table_info(es)
-    r.update(wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None, fast_later_ms_median=float(np.median(ms[1:])))
+    r.update(wide_gap_tiles=int(bool(GAP_OPTS)), wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None, fast_later_ms_median=float(np.median(ms[1:])))
     r.update(tiles=d["n_chunks"], tile_len=d["tile_len"], warmup=d["warmup"], fast_ms=ms, fast_first_ms=ms[0],
              fast_later_ms_mean=float(np.mean(ms[1:])), fast_later_ms_min=float(np.min(ms[1:])), repairs=rounds)
     es.close()
@@ -155,7 +161,7 @@ def counts_part(hip, segs, n, steps, exact_steps, slab=0, ckpt=False):
     r = {"wide_counts_slab": slab, "wide_counts_ckpt": int(ckpt)}
     hip.load_library().psmc_hip_device_count()   # (the runtime is up before the first reading)
     before = device_bytes_in_use(hip)
-    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_counts=1, wide_counts_slab=slab)
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_counts=1, wide_counts_slab=slab, **GAP_OPTS)
     if ckpt:
         es.set_option("wide_ckpt", 1)
         es.set_option("wide_counts_ckpt", 1)
@@ -205,7 +211,7 @@ def batch_part(hip, segs, n, n_rep, leg, ckpt=False):
     sel = [[int(i) for i in rng.integers(0, len(segs), size=len(segs))] for _ in range(n_rep)]
     r = {"replicates": n_rep, "selections": sel,
          "unique_bins": [int(sum(len(segs[i]) for i in set(x))) for x in sel], "all_bins": int(sum(len(s) for s in segs))}
-    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_batch=1 if leg == "wide" else 0)
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_batch=1 if leg == "wide" else 0, **GAP_OPTS)
     if ckpt:
         es.set_option("wide_ckpt", 1)
     es.load_segments(segs)
@@ -265,7 +271,7 @@ def decode_calls(es, segs, n, full_post):
 def decode_part(hip, segs, n, repeats, full_post, exact, ckpt=False):
     a, e, a0 = params_seq(n, 1)[0]
     r = {"longest_segment_bins": int(max(len(s) for s in segs))}
-    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_decode=1)
+    es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_decode=1, **GAP_OPTS)
     if ckpt:
         es.set_option("wide_ckpt", 1)
         es.set_option("wide_decode_ckpt", 1)
@@ -276,7 +282,7 @@ def decode_part(hip, segs, n, repeats, full_post, exact, ckpt=False):
         t = time.perf_counter(); es.estep_factored(a, e[:2], a0); ms.append((time.perf_counter() - t) * 1e3)
     r["wide_estep_ms"] = _spread(ms)
     ti = table_info(es)
-    r.update(wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None)
+    r.update(wide_gap_tiles=int(bool(GAP_OPTS)), wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None)
     decode_calls(es, segs, n, full_post)   # warm-up
     passes = [decode_calls(es, segs, n, full_post) for _ in range(repeats)]
     r["wide_decode_ms"] = {k: _spread([p[k] for p in passes]) for k in passes[0]}
@@ -338,7 +344,10 @@ def main():
     ap.add_argument("--counts", action="store_true", help="(f): psmc_hip_estep with \"wide_counts\" = 1 against the factored wide E-step and the exact kernels instead of (a), (b)")
     ap.add_argument("--counts-slab", type=int, default=0, help="with --counts: \"wide_counts_slab\" (0 = auto)")
     ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
+    ap.add_argument("--gap-tiles", action="store_true", help="\"wide_gap_tiles\" = 1 on the wide contexts of every leg: runs of missing data are crossed by the transfer-matrix chain (estep_wide_gap.hip); (a) prints the largest verify mismatch of every step beside its rounds")
     args = ap.parse_args()
+    if args.gap_tiles:
+        GAP_OPTS["wide_gap_tiles"] = 1
     from psmc_amd import hip, sim
     if args.stress:
         segs = stress_segs()
