@@ -105,6 +105,32 @@ int psmc_hip_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap)
  * behind it), bit 1: glued backward.  All zero with "wide_gap_tiles" = 0. */
 int psmc_hip_wide_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap);
 
+/* Diagnostics of "wide_gap_tiles" (psmc_hip.h): what the planner made of the qualifying runs and what the last wide fast E-step did
+ * with it.  Host reads and plain device-to-host copies behind a synchronise of the context's stream; none launches a kernel.  All
+ * four return PSMC_HIP_ESTATE under the condition of psmc_hip_wide_plan_tiles (no current wide plan).
+ *
+ * psmc_hip_wide_gap_chains: the transfer-matrix chains of the current plan in direction dir (0 forward, 1 backward), in the order
+ * they are launched (level by level).  Returns their number and fills the first `cap` entries: first[i] = the tile whose start
+ * vector the chain copies from its neighbour's exit vector (the run's first tile in sweep order that is not anchored in that
+ * direction), count[i] = applications of the matrix (the tiles first + 1 .. first + count forward, first - 1 .. first - count
+ * backward; 0: every tile of the run is anchored, only the walk hangs on the chain), walk[i] = the tile its walk starts on (the
+ * last tile the chain writes), level[i] = 0, or one more than the chain before it in the segment when its first vector comes out
+ * of that chain's walk.  0 chains with "wide_gap_tiles" = 0 or without a qualifying run.
+ *
+ * psmc_hip_wide_gap_rechained: out[0] forward, out[1] backward: chains the repair rounds of the last wide fast E-step ran again (a
+ * run whose first chained tile headed a failing run), summed over the rounds.
+ *
+ * psmc_hip_wide_gap_matrix: the transfer matrix of one full tile of missing data as the last wide fast E-step built it, n rows of
+ * the padded width (192 or 256 up to 256 states, the next multiple of 256 beyond): row k = the unit vector of state k swept T
+ * bins forward.  Returns the number of doubles and copies the first `cap`; PSMC_HIP_ESTATE when that E-step built none.
+ *
+ * psmc_hip_wide_tile_vectors: every tile's start vector after the last wide fast E-step, forward (which = 0: entry) or backward
+ * (which = 1: bentry), tiles x the padded width.  Returns the number of doubles and copies the first `cap`. */
+int psmc_hip_wide_gap_chains(psmc_hip_ctx *ctx, int dir, int32_t *first, int32_t *count, int32_t *walk, int32_t *level, int cap);
+int psmc_hip_wide_gap_rechained(psmc_hip_ctx *ctx, int out[2]);
+int64_t psmc_hip_wide_gap_matrix(psmc_hip_ctx *ctx, double *M, int64_t cap);
+int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *ctx, int which, double *out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

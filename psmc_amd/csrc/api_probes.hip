@@ -307,3 +307,61 @@ extern "C" int psmc_hip_wide_plan_tiles(psmc_hip_ctx *c, int32_t *cls, int32_t *
 	}
 	return nc;
 }
+
+// ---- what "wide_gap_tiles" planned and did (api_wide_fast.hip): host reads and plain copies behind a stream synchronise, no kernel
+static int no_wide_plan(psmc_hip_ctx *c, const char *who)
+{
+	std::string msg = std::string(who) + ": no current wide plan (run a wide fast E-step first)";
+	return fail(c, PSMC_HIP_ESTATE, msg.c_str());
+}
+
+extern "C" int psmc_hip_wide_gap_chains(psmc_hip_ctx *c, int dir, int32_t *first, int32_t *count, int32_t *walk, int32_t *level, int cap)
+{
+	if (!c || dir < 0 || dir > 1 || cap < 0 || (cap > 0 && (!first || !count || !walk || !level))) return PSMC_HIP_EINVAL;
+	if (c->plan_dirty || c->wf_chunks.empty() || !c->wf_ran) return no_wide_plan(c, "wide_gap_chains");
+	const psmc_hip_ctx::WgDir &D = c->wg[dir];
+	const int nr = (int)D.runs.size();
+	int lev = 0;
+	for (int i = 0; i < nr && i < cap; ++i) {
+		while (lev + 1 < (int)D.run_off.size() && i >= D.run_off[lev + 1]) ++lev; // (run_off: [levels + 1], ascending)
+		first[i] = D.runs[i].first; count[i] = D.runs[i].count; walk[i] = D.walk[i]; level[i] = lev;
+	}
+	return nr;
+}
+
+extern "C" int psmc_hip_wide_gap_rechained(psmc_hip_ctx *c, int out[2])
+{
+	if (!c || !out) return PSMC_HIP_EINVAL;
+	if (c->plan_dirty || c->wf_chunks.empty() || !c->wf_ran) return no_wide_plan(c, "wide_gap_rechained");
+	out[0] = c->wg_rechained[0]; out[1] = c->wg_rechained[1];
+	return PSMC_HIP_OK;
+}
+
+extern "C" int64_t psmc_hip_wide_gap_matrix(psmc_hip_ctx *c, double *M, int64_t cap)
+{
+	if (!c || cap < 0 || (cap > 0 && !M)) return PSMC_HIP_EINVAL;
+	if (c->plan_dirty || c->wf_chunks.empty() || !c->wf_ran) return no_wide_plan(c, "wide_gap_matrix");
+	if (!c->wg_m_valid || !c->d_wg_M) return fail(c, PSMC_HIP_ESTATE, "wide_gap_matrix: the last wide fast E-step built no transfer matrix (no qualifying run, or \"wide_gap_tiles\" = 0)");
+	const int64_t len = (int64_t)c->n * wf_width(c);
+	if (cap > 0) {
+		HIPCHK(c, hipSetDevice(c->device));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(M, c->d_wg_M, sizeof(double) * (size_t)std::min(cap, len), hipMemcpyDeviceToHost));
+	}
+	return len;
+}
+
+extern "C" int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *c, int which, double *out, int64_t cap)
+{
+	if (!c || which < 0 || which > 1 || cap < 0 || (cap > 0 && !out)) return PSMC_HIP_EINVAL;
+	if (c->plan_dirty || c->wf_chunks.empty() || !c->wf_ran) return no_wide_plan(c, "wide_tile_vectors");
+	const double *src = which ? c->d_wf_bentry : c->d_wf_entry;
+	if (!src) return no_wide_plan(c, "wide_tile_vectors");
+	const int64_t len = (int64_t)c->wf_chunks.size() * wf_width(c);
+	if (cap > 0) {
+		HIPCHK(c, hipSetDevice(c->device));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(out, src, sizeof(double) * (size_t)std::min(cap, len), hipMemcpyDeviceToHost));
+	}
+	return len;
+}

@@ -254,6 +254,7 @@ static int wide_rounds(psmc_hip_ctx *c, WideLaunch &w, bool bwd, int &rounds, in
 				g->runs = c->d_wg_again; g->n_runs = (int)chains.size();
 				if (launch_wide_gap(*g, bwd ? WG_CHAIN_B : WG_CHAIN_F)) return fail(c, PSMC_HIP_EDEVICE, "k_wf_gapchain", hipGetLastError());
 				n_again = (int)again.size();
+				c->wg_rechained[bwd ? 1 : 0] += n_again;
 			}
 			for (int b = 0; b < nc; ++b) {
 				if (own[b]) heads.push_back(b | WG_OWN | (own[b] == 1 ? WG_SINGLE : 0));
@@ -348,6 +349,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	w.part = c->d_wf_part; w.LLpart = c->d_wf_ll; w.stage = c->d_stage; w.out = d_out;
 	c->report = FastReport{0, 0, 0, 0, 0, 0, 2};
 	c->wf_ran = true; c->wc_ran = false; c->last_fused = 3; c->wf_last_iv = iv;
+	c->wg_m_valid = false; c->wg_rechained[0] = c->wg_rechained[1] = 0;
 	// "wide_gap_tiles" with a qualifying run in the plan: the tiles glued at plan time do not speculate.  Per direction: the sweeps of
 	// the others; the transfer matrix (once); then level by level the chains across the runs and ONE launch with the sweeps of the runs'
 	// tiles from the chain's vectors and the walks behind the runs (no work-group of it reads what another one of it writes).
@@ -383,6 +385,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 		w.list = c->d_wg_spec[1];
 		if (launch_wide_fast(w, WF_BWARM_LIST, (int)c->wg[1].spec.size())) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
 		if (launch_wide_gap(g, WG_MAT) || gap_levels(0)) return fail(c, PSMC_HIP_EDEVICE, "wide gap chains (forward)", hipGetLastError());
+		c->wg_m_valid = true;
 	}
 	int r = 0, t = 0;
 	rc = wide_rounds(c, w, false, r, t, gaps ? &g : nullptr);

@@ -293,6 +293,13 @@ struct psmc_hip_ctx {
 	// direction (their speculation is exact) and ends with the start vector of the first tile behind the run, where one walk goes on
 	// through the tiles glued behind it (`walk`).  A chain whose first vector comes out of the walk of the run before it in the segment
 	// (two runs closer than a warm-up) is one LEVEL later: levels run one after the other, chains and sweeps of a level side by side.
+	// In full, per direction and in sweep order: `first` is the run's first tile that is not anchored, the chain applies the matrix once
+	// per tile from there to the run's last tile (`count` times) and `walk` is the tile behind the run.  A run that is anchored throughout
+	// has no tile to cross: its chain has count 0 and stands on the first tile behind the run that is not anchored (first = walk), where only
+	// the walk starts -- if that tile is glued in the direction, belongs to no qualifying run (then that run's chain starts there) and no
+	// earlier chain's walk has been through it.  When every tile from the run to the segment's end is anchored there is no chain.  A walk
+	// goes through the consecutive tiles behind its start that are glued in the direction and belong to no qualifying run.  A chain's
+	// level is 0, or one more than the level of the chain before it when the tile before `first` is one that chain wrote or walked through.
 	struct WgDir {
 		std::vector<GapRun> runs;           // by level
 		std::vector<int32_t> walk;          // [runs] the tile its walk starts on
@@ -304,6 +311,8 @@ struct psmc_hip_ctx {
 	int *d_wg_glue = nullptr, *d_wg_list[2] = {nullptr, nullptr}, *d_wg_spec[2] = {nullptr, nullptr};
 	GapRun *d_wg_runs[2] = {nullptr, nullptr}, *d_wg_again = nullptr; // ... and the chains a repair round runs again
 	double *d_wg_M = nullptr; size_t wg_m_cap = 0; // [n][padded width] the transfer matrix of a full gap tile
+	bool wg_m_valid = false;        // the last wide fast E-step built d_wg_M (psmc_hip_wide_gap_matrix, the diagnostic library)
+	int wg_rechained[2] = {0, 0};   // chains the last wide fast E-step's repair rounds ran again, forward | backward (psmc_hip_wide_gap_rechained)
 	int wg_cap = 0;
 };
 // the padded width of the wide fast path's own tables (api_wide_fast.hip writes them, api_decode.hip reads them): c->ns (192 or 256)

@@ -40,6 +40,7 @@ DIAG_EXPORTS = [
     "psmc_hip_selftest", "psmc_hip_last_timing", "psmc_hip_microbench", "psmc_hip_stream_probe", "psmc_hip_hbm_probe",
     "psmc_hip_load_probe", "psmc_hip_load_probe_st", "psmc_hip_pipe_probe", "psmc_hip_pipe_probe2", "psmc_hip_place_probe",
     "psmc_hip_cumask_probe", "psmc_hip_plan_tiles", "psmc_hip_wide_plan_tiles",
+    "psmc_hip_wide_gap_chains", "psmc_hip_wide_gap_rechained", "psmc_hip_wide_gap_matrix", "psmc_hip_wide_tile_vectors",
 ]
 
 
@@ -356,6 +357,55 @@ class HipEStep:
         if n2 < 0:
             self._chk(n2, "wide_plan_tiles")
         return dict(cls=cls, glue=glue)
+
+    def wide_gap_chains(self):
+        """The transfer-matrix chains of the current wide plan (psmc_hip_wide_gap_chains, the diagnostic library): per direction
+        (forward, backward) the list of (first, count, walk, level) in launch order.  Two empty lists with wide_gap_tiles=0."""
+        d = load_diag()
+        d.psmc_hip_wide_gap_chains.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int]
+        out = []
+        for dr in (0, 1):
+            n = d.psmc_hip_wide_gap_chains(self.h, dr, None, None, None, None, 0)
+            if n < 0:
+                self._chk(n, "wide_gap_chains")
+            v = np.zeros((4, max(n, 1)), dtype=np.int32)
+            n2 = d.psmc_hip_wide_gap_chains(self.h, dr, *[v[i].ctypes.data_as(_i32p) for i in range(4)], n)
+            if n2 < 0:
+                self._chk(n2, "wide_gap_chains")
+            out.append([tuple(int(x) for x in v[:, i]) for i in range(n)])
+        return out
+
+    def wide_gap_rechained(self):
+        """[forward, backward]: chains the last wide fast E-step's repair rounds ran again (psmc_hip_wide_gap_rechained)."""
+        d = load_diag()
+        o = (C.c_int * 2)()
+        d.psmc_hip_wide_gap_rechained.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        self._chk(d.psmc_hip_wide_gap_rechained(self.h, o), "wide_gap_rechained")
+        return [int(o[0]), int(o[1])]
+
+    def _diag_doubles(self, name, *lead):
+        fn = getattr(load_diag(), name)
+        fn.argtypes = [C.c_void_p] + [C.c_int] * len(lead) + [_dp, C.c_int64]
+        fn.restype = C.c_int64
+        n = fn(self.h, *lead, None, 0)
+        if n < 0:
+            self._chk(int(n), name)
+        out = np.zeros(n)
+        n2 = fn(self.h, *lead, _p(out), n)
+        if n2 < 0:
+            self._chk(int(n2), name)
+        return out
+
+    def wide_gap_matrix(self):
+        """(n, padded width): the transfer matrix of one full tile of missing data as the last wide fast E-step built it
+        (psmc_hip_wide_gap_matrix); HipError (invalid state) when it built none."""
+        return self._diag_doubles("psmc_hip_wide_gap_matrix").reshape(self.n, -1)
+
+    def wide_tile_vectors(self, which):
+        """(tiles, padded width): every tile's forward (which=0, entry) or backward (which=1, bentry) start vector after the last wide
+        fast E-step (psmc_hip_wide_tile_vectors)."""
+        v = self._diag_doubles("psmc_hip_wide_tile_vectors", int(which))
+        return v.reshape(-1, 64 * ((self.n + 63) // 64) if self.n <= 256 else 256 * ((self.n + 255) // 256))
 
     def tables(self, seg, want_b=True):
         L = int(self.lens[seg])

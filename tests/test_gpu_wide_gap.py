@@ -266,7 +266,9 @@ def test_gap_stress(hip):
 
 # ------------------------------------------------------------------ (f) options
 def test_gap_options(hip, golden, wide):
-    """Bad values are EINVAL; wide_plan_tiles before any E-step is ESTATE; without "wide_fast" the option changes nothing."""
+    """Bad values are EINVAL; wide_plan_tiles and the chain diagnostics (wide_gap_chains, wide_gap_rechained, wide_gap_matrix,
+    wide_tile_vectors) are ESTATE before any E-step and after an option that dirties the plan; with the option off there are no chains and
+    no matrix; without "wide_fast" the option changes nothing."""
     a, e, a0 = params(200, wide)
     segs = [sandwich(golden.segs_mid[3])]
     es = hip.HipEStep(200, mode=hip.MODE_FAST, wide_fast=1)
@@ -275,13 +277,27 @@ def test_gap_options(hip, golden, wide):
             es.set_option(k, v)
     es.set_option("wide_gap_tiles", 1); es.set_option("wide_gap_min", 0); es.set_option("wide_gap_min", 4096)
     es.load_segments(segs)
-    with pytest.raises(hip.HipError, match="no current wide plan"):
-        es.wide_plan_tiles()
+    for k, v in dict(wide_gap_min=2048, **SANDWICH).items():   # the tiling of test_gap_sandwich: one chain per direction
+        es.set_option(k, v)
+    probes = (es.wide_plan_tiles, es.wide_gap_chains, es.wide_gap_rechained, es.wide_gap_matrix, lambda: es.wide_tile_vectors(0), lambda: es.wide_tile_vectors(1))
+    for f in probes:
+        with pytest.raises(hip.HipError, match="no current wide plan"):
+            f()
     es.estep_factored(a, e[:2], a0)
-    assert len(es.wide_plan_tiles()["cls"]) == ran_wide(es)["n_chunks"]
+    nt = ran_wide(es)["n_chunks"]
+    assert len(es.wide_plan_tiles()["cls"]) == nt
+    ch = es.wide_gap_chains()
+    assert len(ch) == 2 and len(ch[0]) == 1 and len(ch[1]) == 1 and es.wide_gap_rechained() == [0, 0]
+    assert es.wide_gap_matrix().shape == (200, 256) and es.wide_tile_vectors(0).shape == (nt, 256) and es.wide_tile_vectors(1).shape == (nt, 256)
     es.set_option("wide_gap_min", 100)   # the plan is dirty again
-    with pytest.raises(hip.HipError, match="no current wide plan"):
-        es.wide_plan_tiles()
+    for f in probes:
+        with pytest.raises(hip.HipError, match="no current wide plan"):
+            f()
+    es.set_option("wide_gap_tiles", 0)   # off: a plan without chains, and an E-step that builds no matrix
+    es.estep_factored(a, e[:2], a0)
+    assert es.wide_gap_chains() == [[], []] and es.wide_gap_rechained() == [0, 0] and es.wide_tile_vectors(0).shape == (nt, 256)
+    with pytest.raises(hip.HipError, match="built no transfer matrix"):
+        es.wide_gap_matrix()
     es.close()
     out = []
     for opts in (dict(), dict(wide_gap_tiles=1)):   # without "wide_fast": the exact wide kernels, whatever the option says
