@@ -131,6 +131,38 @@ int psmc_hip_wide_gap_rechained(psmc_hip_ctx *ctx, int out[2]);
 int64_t psmc_hip_wide_gap_matrix(psmc_hip_ctx *ctx, double *M, int64_t cap);
 int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *ctx, int which, double *out, int64_t cap);
 
+/* Diagnostics of the transfer-matrix chains of the fast path up to 128 states (the glued runs of the structured plan: learned runs,
+ * "gap_tiles", "hom_tiles"): what the list builder made of the runs and what the last fast E-step (psmc_hip_estep, _factored, _device)
+ * left behind.  Host reads and plain device-to-host copies behind a synchronise of the context's stream; none launches a kernel.  All
+ * four return PSMC_HIP_ESTATE when there is no current fast plan with built item lists (no successful structured fast E-step of at
+ * most 128 states since load / select / an option that changes the plan).  S below is the padded state count: 64, or 128 beyond 64.
+ *
+ * psmc_hip_fast_chain_info: out[0], out[1] = chained runs forward, backward; out[2] = KcTiles (one per matrix application of any
+ * chain); out[3] = matrix slots; out[4] = step ranges per tile in use ("kc_sub" as planned at S = 64, 1 at S = 128); out[5] = S;
+ * out[6] = tiles of the plan; out[7] = the tile length.
+ *
+ * psmc_hip_fast_chain_list: returns the length in ints of list `which` and copies the first `cap`:
+ *   0  the chained runs in launch order, forward ones first: (first, count, kc0, 0) each -- the chain starts from the start vector of
+ *      tile `first` (forward) or first + count - 1 (backward), which a walk leaves, and writes the start vectors of the run's other
+ *      count - 1 tiles; kc0 = index of the run's first KcTile;
+ *   1  the KcTiles (tile, dir) each, dir 0 forward, 1 backward: the tile whose steps application j of a chain crosses;
+ *   2  kslot[j]: the matrix slot of KcTile j (the gap tiles of a direction share one, and so do the all-homozygous tiles of the
+ *      qualifying runs of "hom_tiles", when the tile length is a multiple of four);
+ *   3  kuniq[u]: the KcTile slot u's matrices are computed from.
+ *
+ * psmc_hip_fast_chain_matrices: slots x ranges matrices of S x S doubles, then slots x ranges x S exponents, as the last E-step left
+ * them: element [(j * S + col) * S + k], j = slot * ranges + range, is state k of the unit vector of state `col` after the range's
+ * steps, scaled by 2^-exponent[j * S + col].  Returns the number of doubles (0 without a chain) and copies the first `cap`.
+ *
+ * psmc_hip_fast_tile_vectors: which = 0 entry (forward start vectors, proportional to X at lo - 1), 1 bentry (backward start vectors,
+ * proportional to bt at min(hi, L - 1) + 1), 2 bexit (backward exit vectors), tiles x S each, after the last E-step.  The entry of a
+ * segment's first tile is never written (position 1 is an initial condition).  Returns the number of doubles and copies the first
+ * `cap`. */
+int psmc_hip_fast_chain_info(psmc_hip_ctx *ctx, int out[8]);
+int psmc_hip_fast_chain_list(psmc_hip_ctx *ctx, int which, int32_t *out, int cap);
+int64_t psmc_hip_fast_chain_matrices(psmc_hip_ctx *ctx, double *out, int64_t cap);
+int64_t psmc_hip_fast_tile_vectors(psmc_hip_ctx *ctx, int which, double *out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -365,3 +365,72 @@ extern "C" int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *c, int which, double
 	}
 	return len;
 }
+
+// ---- the transfer-matrix chains of the fast path up to 128 states (api_fast.hip build_items, estep_struct.hip k_kcol_struct / k_kcol2_struct /
+// k_kchain_struct): host reads and plain copies behind a stream synchronise, no kernel.  build_items keeps its lists on the device only:
+// they are copied from d_items at the offsets enqueue_fast hands to the launch.
+static int no_fast_lists(psmc_hip_ctx *c, const char *who)
+{
+	std::string msg = std::string(who) + ": no current fast plan with built item lists (run a structured fast E-step at up to 128 states first)";
+	return fail(c, PSMC_HIP_ESTATE, msg.c_str());
+}
+static bool fast_lists_ok(const psmc_hip_ctx *c)
+{
+	// (dec_kind: the last fast E-step of this context succeeded, so build_items has run for the current plan)
+	return c->mode == PSMC_HIP_MODE_FAST && c->ns <= 128 && !c->wf_ran && !c->plan_dirty && !c->chunks.empty() && c->use_struct && c->planned_struct &&
+	       c->d_items && c->dec_kind != DEC_NONE && c->dec_kind != DEC_EXACT;
+}
+
+extern "C" int psmc_hip_fast_chain_info(psmc_hip_ctx *c, int out[8])
+{
+	if (!c || !out) return PSMC_HIP_EINVAL;
+	if (!fast_lists_ok(c)) return no_fast_lists(c, "fast_chain_info");
+	out[0] = c->n_chain_f; out[1] = c->n_chain_b; out[2] = c->n_kc; out[3] = c->n_kuniq;
+	out[4] = kcol2_on(c) ? c->kc_sub_used : 1; out[5] = c->ns; out[6] = (int)c->chunks.size(); out[7] = c->chunk_used;
+	return PSMC_HIP_OK;
+}
+
+extern "C" int psmc_hip_fast_chain_list(psmc_hip_ctx *c, int which, int32_t *out, int cap)
+{
+	if (!c || which < 0 || which > 3 || cap < 0 || (cap > 0 && !out)) return PSMC_HIP_EINVAL;
+	if (!fast_lists_ok(c)) return no_fast_lists(c, "fast_chain_list");
+	const size_t nc = c->chunks.size();
+	// d_items + 16 nc: KcTile (tile, dir) | + 20 nc: KcRun (first, count, kc0, pad), forward runs then backward | + 26 nc: kslot | + 28 nc: kuniq
+	const size_t off = which == 0 ? 20 * nc : (which == 1 ? 16 * nc : (which == 2 ? 26 * nc : 28 * nc));
+	const int len = c->n_kc <= 0 ? 0 : (which == 0 ? 4 * (c->n_chain_f + c->n_chain_b) : (which == 1 ? 2 * c->n_kc : (which == 2 ? c->n_kc : c->n_kuniq)));
+	if (cap > 0 && len > 0) {
+		HIPCHK(c, hipSetDevice(c->device));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(out, c->d_items + off, sizeof(int) * (size_t)std::min(cap, len), hipMemcpyDeviceToHost));
+	}
+	return len;
+}
+
+extern "C" int64_t psmc_hip_fast_chain_matrices(psmc_hip_ctx *c, double *out, int64_t cap)
+{
+	if (!c || cap < 0 || (cap > 0 && !out)) return PSMC_HIP_EINVAL;
+	if (!fast_lists_ok(c)) return no_fast_lists(c, "fast_chain_matrices");
+	const int64_t sub = kcol2_on(c) ? c->kc_sub_used : 1;
+	const int64_t len = c->n_kc <= 0 || !c->d_Kcol ? 0 : (int64_t)c->n_kuniq * sub * ((int64_t)c->ns * c->ns + c->ns);
+	if (cap > 0 && len > 0) {
+		HIPCHK(c, hipSetDevice(c->device));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(out, c->d_Kcol, sizeof(double) * (size_t)std::min(cap, len), hipMemcpyDeviceToHost));
+	}
+	return len;
+}
+
+extern "C" int64_t psmc_hip_fast_tile_vectors(psmc_hip_ctx *c, int which, double *out, int64_t cap)
+{
+	if (!c || which < 0 || which > 2 || cap < 0 || (cap > 0 && !out)) return PSMC_HIP_EINVAL;
+	if (!fast_lists_ok(c)) return no_fast_lists(c, "fast_tile_vectors");
+	const double *src = which == 0 ? c->d_entry : (which == 1 ? c->d_bentry : c->d_bexit);
+	if (!src) return no_fast_lists(c, "fast_tile_vectors");
+	const int64_t len = (int64_t)c->chunks.size() * c->ns;
+	if (cap > 0) {
+		HIPCHK(c, hipSetDevice(c->device));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(out, src, sizeof(double) * (size_t)std::min(cap, len), hipMemcpyDeviceToHost));
+	}
+	return len;
+}

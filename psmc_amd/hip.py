@@ -41,6 +41,7 @@ DIAG_EXPORTS = [
     "psmc_hip_load_probe", "psmc_hip_load_probe_st", "psmc_hip_pipe_probe", "psmc_hip_pipe_probe2", "psmc_hip_place_probe",
     "psmc_hip_cumask_probe", "psmc_hip_plan_tiles", "psmc_hip_wide_plan_tiles",
     "psmc_hip_wide_gap_chains", "psmc_hip_wide_gap_rechained", "psmc_hip_wide_gap_matrix", "psmc_hip_wide_tile_vectors",
+    "psmc_hip_fast_chain_info", "psmc_hip_fast_chain_list", "psmc_hip_fast_chain_matrices", "psmc_hip_fast_tile_vectors",
 ]
 
 
@@ -406,6 +407,39 @@ class HipEStep:
         fast E-step (psmc_hip_wide_tile_vectors)."""
         v = self._diag_doubles("psmc_hip_wide_tile_vectors", int(which))
         return v.reshape(-1, 64 * ((self.n + 63) // 64) if self.n <= 256 else 256 * ((self.n + 255) // 256))
+
+    def fast_chains(self):
+        """The transfer-matrix chains of the current fast plan up to 128 states and what the last E-step left of them (the
+        psmc_hip_fast_chain_* diagnostics): dict(S padded states, sub step ranges per tile, tiles, tile_len, runs = (forward, backward)
+        lists of (first, count, kc0) in launch order, kc = [(tile, dir)], kslot, kuniq, K (slots, sub, S columns, S) and Kexp (slots, sub,
+        S)).  HipError (invalid state) before the first structured fast E-step."""
+        d = load_diag()
+        o = (C.c_int * 8)()
+        d.psmc_hip_fast_chain_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        self._chk(d.psmc_hip_fast_chain_info(self.h, o), "fast_chain_info")
+        nf, nb, nkc, nu, sub, S, nc, T = [int(x) for x in o]
+        d.psmc_hip_fast_chain_list.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int]
+        lists = []
+        for which in range(4):
+            n = d.psmc_hip_fast_chain_list(self.h, which, None, 0)
+            if n < 0:
+                self._chk(n, "fast_chain_list")
+            v = np.zeros(max(n, 1), dtype=np.int32)
+            n2 = d.psmc_hip_fast_chain_list(self.h, which, v.ctypes.data_as(_i32p), n)
+            if n2 < 0:
+                self._chk(n2, "fast_chain_list")
+            lists.append(v[:n])
+        runs = [tuple(int(x) for x in r[:3]) for r in lists[0].reshape(-1, 4)]
+        m = self._diag_doubles("psmc_hip_fast_chain_matrices")
+        nm = nu * sub if len(m) else 0
+        return dict(S=S, sub=sub, tiles=nc, tile_len=T, runs=(runs[:nf], runs[nf:nf + nb]) if len(runs) else ([], []),
+                    kc=[(int(a), int(b)) for a, b in lists[1].reshape(-1, 2)], kslot=lists[2].copy(), kuniq=lists[3].copy(),
+                    K=m[:nm * S * S].reshape(-1, sub, S, S), Kexp=m[nm * S * S:].reshape(-1, sub, S))
+
+    def fast_tile_vectors(self, which):
+        """(tiles, S): every tile's entry (which=0), bentry (1) or bexit (2) vector after the last fast E-step up to 128 states
+        (psmc_hip_fast_tile_vectors); S = 64, or 128 beyond 64 states."""
+        return self._diag_doubles("psmc_hip_fast_tile_vectors", int(which)).reshape(-1, 64 if self.n <= 64 else 128)
 
     def tables(self, seg, want_b=True):
         L = int(self.lens[seg])
