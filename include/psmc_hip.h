@@ -237,6 +237,24 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *  "wide_gap_min"  auto     bins of missing data a run of gap tiles needs to qualify; 0 = auto = a quarter of the wide plan's warm-up (4096
  *                           at the default 16384): a shorter run leaves at least 12288 data bins in a warm-up window, which
  *                           profiles/wide_fast_timing.txt measured as sufficient.  Negative: PSMC_HIP_EINVAL
+ *  "wide_hom_tiles" 0       1: the same for runs of homozygosity, which a warm-up crosses no better (two start vectors still disagree by
+ *                           0.03-0.08 after 16384 homozygous bins: DESIGN.md section 7).  A hom tile is a full tile of homozygous bins only
+ *                           (no het, no missing bin) that is neither the first nor the last tile of its segment.  A chain tile is a gap
+ *                           tile when "wide_gap_tiles" is on, or a hom tile when this option is on; a run is a maximal sequence of
+ *                           consecutive chain tiles of one segment, and it qualifies when "wide_gap_tiles" is on and its gap tiles hold
+ *                           at least "wide_gap_min" bins, or this option is on and its hom tiles hold at least "wide_hom_min" bins.  Glue,
+ *                           chains, levels, verification and repair are those of "wide_gap_tiles"; across a hom tile the chain applies
+ *                           the matrix M_h of one full tile of homozygous bins, built once per E-step beside M: a pilot sweep of the
+ *                           uniform vector yields the power-of-two scale factors of such a tile, and the n unit vectors are swept
+ *                           with them (under symbol 0 every step shrinks the vector, an unscaled row would drift towards underflow).
+ *                           A het-free tile that holds homozygous AND missing bins is an ordinary data tile: it ends a run, and the run
+ *                           that resumes behind it is chained after the walk through it.  Device memory: n x (padded states) doubles
+ *                           for M_h and a quarter of a tile's bins in factors, and four bytes per tile.  Results stay bit-reproducible
+ *                           and within the fast-mode tolerances, with every option "wide_gap_tiles" goes with.  0: plan and E-step are
+ *                           bit for bit what they are without the option.  Accepted and ignored where the wide fast path does not run
+ *                           (exact mode, up to 128 states, "wide_fast" = 0).  Other values: PSMC_HIP_EINVAL
+ *  "wide_hom_min"  auto     bins of hom tiles a run needs to qualify through them; 0 = auto = a quarter of the wide plan's warm-up, as
+ *                           "wide_gap_min" and "hom_min".  Negative: PSMC_HIP_EINVAL
  *  "two_phase"     auto     2: the fused back half runs as two launches, odd tiles of the second list start from the exit
  *                           vector of the tile above instead of speculating backward; 0: every tile speculates, one
  *                           launch when the tiles fit one round.  auto: 2 with two rounds, 0 with one

@@ -102,12 +102,14 @@ int psmc_hip_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap)
  * select / an option that changes the plan) -- and fills the first `cap` entries: cls[b] = 0, 1 = gap tile (a full tile of missing
  * data, neither first nor last in its segment) outside a qualifying run, 2 = gap tile of a qualifying run; glue[b] = bit 0: glued
  * forward (the tile does not speculate: its start vector comes from the transfer-matrix chain across the run, or from the walk
- * behind it), bit 1: glued backward.  All zero with "wide_gap_tiles" = 0. */
+ * behind it), bit 1: glued backward.  With "wide_hom_tiles" = 1 also 3 = hom tile (a full tile of
+ * homozygous bins only, neither first nor last in its segment) outside a qualifying run, 4 = hom tile of a qualifying run.  All zero
+ * with "wide_gap_tiles" = 0 and "wide_hom_tiles" = 0. */
 int psmc_hip_wide_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap);
 
 /* Diagnostics of "wide_gap_tiles" (psmc_hip.h): what the planner made of the qualifying runs and what the last wide fast E-step did
  * with it.  Host reads and plain device-to-host copies behind a synchronise of the context's stream; none launches a kernel.  All
- * four return PSMC_HIP_ESTATE under the condition of psmc_hip_wide_plan_tiles (no current wide plan).
+ * of them return PSMC_HIP_ESTATE under the condition of psmc_hip_wide_plan_tiles (no current wide plan).
  *
  * psmc_hip_wide_gap_chains: the transfer-matrix chains of the current plan in direction dir (0 forward, 1 backward), in the order
  * they are launched (level by level).  Returns their number and fills the first `cap` entries: first[i] = the tile whose start
@@ -124,11 +126,19 @@ int psmc_hip_wide_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int
  * the padded width (192 or 256 up to 256 states, the next multiple of 256 beyond): row k = the unit vector of state k swept T
  * bins forward.  Returns the number of doubles and copies the first `cap`; PSMC_HIP_ESTATE when that E-step built none.
  *
+ * psmc_hip_wide_hom_matrix ("wide_hom_tiles"): the matrix of one full tile of T homozygous bins as the last wide fast E-step built it,
+ * n rows of the padded width -- row k = the unit vector of state k swept T bins forward under symbol 0 with the pilot's power-of-two
+ * factors -- followed by those ceil(T / 4) factors (factor j was applied at bin 4 j of the tile, counted from 0): dividing every
+ * entry by their product gives the unscaled matrix.  Returns the number of doubles, n x width + ceil(T / 4), and copies the first
+ * `cap`; PSMC_HIP_ESTATE when that E-step built none (no qualifying run with a hom tile).  A chain applies it across the tiles of
+ * class 4: forward v <- v M_h, backward v <- D M_h D^-1 v with D = diag(e0), normalised to sum 1 after every application.
+ *
  * psmc_hip_wide_tile_vectors: every tile's start vector after the last wide fast E-step, forward (which = 0: entry) or backward
  * (which = 1: bentry), tiles x the padded width.  Returns the number of doubles and copies the first `cap`. */
 int psmc_hip_wide_gap_chains(psmc_hip_ctx *ctx, int dir, int32_t *first, int32_t *count, int32_t *walk, int32_t *level, int cap);
 int psmc_hip_wide_gap_rechained(psmc_hip_ctx *ctx, int out[2]);
 int64_t psmc_hip_wide_gap_matrix(psmc_hip_ctx *ctx, double *M, int64_t cap);
+int64_t psmc_hip_wide_hom_matrix(psmc_hip_ctx *ctx, double *M, int64_t cap);
 int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *ctx, int which, double *out, int64_t cap);
 
 /* Diagnostics of the transfer-matrix chains of the fast path up to 128 states (the glued runs of the structured plan: learned runs,

@@ -351,6 +351,20 @@ extern "C" int64_t psmc_hip_wide_gap_matrix(psmc_hip_ctx *c, double *M, int64_t 
 	return len;
 }
 
+extern "C" int64_t psmc_hip_wide_hom_matrix(psmc_hip_ctx *c, double *M, int64_t cap)
+{
+	if (!c || cap < 0 || (cap > 0 && !M)) return PSMC_HIP_EINVAL;
+	if (c->plan_dirty || c->wf_chunks.empty() || !c->wf_ran) return no_wide_plan(c, "wide_hom_matrix");
+	if (!c->wg_mh_T || !c->d_wg_Mh) return fail(c, PSMC_HIP_ESTATE, "wide_hom_matrix: the last wide fast E-step built no matrix of a homozygous tile (no qualifying run with a hom tile, or \"wide_hom_tiles\" = 0)");
+	const int64_t len = (int64_t)c->n * wf_width(c) + (c->wg_mh_T + 3) / 4; // M_h, then the pilot's factors
+	if (cap > 0) {
+		HIPCHK(c, hipSetDevice(c->device));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(M, c->d_wg_Mh, sizeof(double) * (size_t)std::min(cap, len), hipMemcpyDeviceToHost));
+	}
+	return len;
+}
+
 extern "C" int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *c, int which, double *out, int64_t cap)
 {
 	if (!c || which < 0 || which > 1 || cap < 0 || (cap > 0 && !out)) return PSMC_HIP_EINVAL;

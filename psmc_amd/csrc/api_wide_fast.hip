@@ -26,6 +26,9 @@
 // through the tiles glued behind it; then the verify / repair rounds as below.  A repair walk stops in front of a run's first
 // chained tile; a run whose first chained tile heads a failing run is chained again for that round (one head tile in fast_diag).
 // Off, or without a qualifying run: the plan and the launches below, nothing else.
+// "wide_hom_tiles" = 1: the same for runs of homozygosity -- full tiles of symbol 0 only are chain tiles too, a run qualifies through its
+// gap tiles ("wide_gap_min") or through its hom tiles ("wide_hom_min"), and across a hom tile the chain applies the matrix of a full
+// tile of homozygous bins, built beside the other one (pilot, then rows: estep_wide_gap.hip).  Glue, levels, lists, rounds: unchanged.
 //
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
 // of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,
@@ -44,10 +47,10 @@ void free_wide_fast(psmc_hip_ctx *c)
 	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
 	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi, c->d_wc_V, c->d_wc_Xs, c->d_wc_P, c->d_wc_a, c->d_wc_out, c->d_wc_kr, c->d_wc_vrow};
 	for (void *q : p) if (q) (void)hipFree(q);
-	void *gp[] = {c->d_wg_glue, c->d_wg_list[0], c->d_wg_list[1], c->d_wg_spec[0], c->d_wg_spec[1], c->d_wg_runs[0], c->d_wg_runs[1], c->d_wg_again, c->d_wg_M};
+	void *gp[] = {c->d_wg_glue, c->d_wg_list[0], c->d_wg_list[1], c->d_wg_spec[0], c->d_wg_spec[1], c->d_wg_runs[0], c->d_wg_runs[1], c->d_wg_again, c->d_wg_M, c->d_wg_Mh, c->d_wg_cls};
 	for (void *q : gp) if (q) (void)hipFree(q);
 	c->d_wg_glue = c->d_wg_list[0] = c->d_wg_list[1] = c->d_wg_spec[0] = c->d_wg_spec[1] = nullptr;
-	c->d_wg_runs[0] = c->d_wg_runs[1] = c->d_wg_again = nullptr; c->d_wg_M = nullptr; c->wg_cap = 0; c->wg_m_cap = 0;
+	c->d_wg_runs[0] = c->d_wg_runs[1] = c->d_wg_again = nullptr; c->d_wg_M = c->d_wg_Mh = nullptr; c->d_wg_cls = nullptr; c->wg_cap = 0; c->wg_m_cap = c->wg_mh_cap = 0; c->wg_mh_T = 0;
 	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
 	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
 	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
@@ -60,8 +63,9 @@ void free_wide_fast(psmc_hip_ctx *c)
 // rows of the X table over `bins` positions at one row per `iv` positions (iv = 8: the rows at p % 8 == 0, by absolute position)
 static inline int64_t wide_table_rows(int64_t bins, int iv) { return (bins + iv - 1) / iv; }
 
-// "wide_gap_tiles": runs of missing data in the wide plan (the rule: psmc_hip_ctx.h).  One launch of k_tile_class (estep_struct.hip; 1 =
-// missing data only) over the plan's tiles, with d_wf_dirty borrowed as scratch; everything else is host work.  The result is a function
+// "wide_gap_tiles" / "wide_hom_tiles": runs of missing data and of homozygosity in the wide plan (the rule: psmc_hip_ctx.h).  One launch
+// of k_tile_class (estep_struct.hip; 1 = missing data only, 2 = homozygous bins only, 3 = both: an ordinary data tile here) over the plan's tiles,
+// with d_wf_dirty borrowed as scratch; everything else is host work.  The result is a function
 // of the selection, the data and the options, and lives with the plan.  Without a qualifying run nothing but wg_cls / wg_glue (for
 // psmc_hip_wide_plan_tiles) is left, and the E-step is the one without the option.
 static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
@@ -76,28 +80,39 @@ static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
 	std::vector<int32_t> &gc = c->wg_cls, &glue = c->wg_glue;
 	gc.assign(nc, 0); glue.assign(nc, 0);
 	auto same = [&](int x, int y) { return x >= 0 && y >= 0 && x < nc && y < nc && ch[x].off == ch[y].off; };
-	for (int b = 0; b < nc; ++b) gc[b] = cls[b] == 1 && ch[b].lo > 1 && ch[b].hi < ch[b].L && ch[b].hi - ch[b].lo + 1 == T; // a FULL tile, not the first, not the last
-	const int64_t need = c->wide_gap_min > 0 ? c->wide_gap_min : W / 4;
+	// a chain tile: a FULL tile, not the first, not the last, of missing data only (gc 1) or, "wide_hom_tiles", of homozygous bins only (gc 3)
+	for (int b = 0; b < nc; ++b) {
+		const bool inner = ch[b].lo > 1 && ch[b].hi < ch[b].L && ch[b].hi - ch[b].lo + 1 == T;
+		gc[b] = !inner ? 0 : (cls[b] == 1 && c->wide_gap_tiles ? 1 : (cls[b] == 2 && c->wide_hom_tiles ? 3 : 0));
+	}
+	const int64_t need = c->wide_gap_min > 0 ? c->wide_gap_min : W / 4, need_hom = c->wide_hom_min > 0 ? c->wide_hom_min : W / 4;
 	std::vector<std::pair<int, int>> runs; // first and last tile of every qualifying run
+	std::vector<char> inrun(nc, 0);        // tile of a qualifying run
+	c->wg_mats = 0;
 	for (int b = 0; b < nc;) {
 		if (!gc[b]) { ++b; continue; }
 		int e = b;
-		while (e < nc && same(b, e) && gc[e]) ++e;
-		if ((int64_t)(e - b) * T >= need) { runs.push_back({b, e - 1}); for (int t = b; t < e; ++t) gc[t] = 2; }
+		int64_t n_gap = 0, n_hom = 0;
+		while (e < nc && same(b, e) && gc[e]) { if (gc[e] == 1) ++n_gap; else ++n_hom; ++e; }
+		if ((n_gap > 0 && n_gap * T >= need) || (n_hom > 0 && n_hom * T >= need_hom)) {
+			runs.push_back({b, e - 1});
+			for (int t = b; t < e; ++t) { inrun[t] = 1; ++gc[t]; } // 1 -> 2, 3 -> 4
+			c->wg_mats |= (n_gap > 0 ? 1 : 0) | (n_hom > 0 ? 2 : 0);
+		}
 		b = e;
 	}
 	if (runs.empty()) return 0;
 	std::vector<int> inq(nc + 1, 0), first(nc, 0); // prefix sums of "tile of a qualifying run"; the segment's first tile
-	for (int b = 0; b < nc; ++b) { inq[b + 1] = inq[b] + (gc[b] == 2); first[b] = same(b - 1, b) ? first[b - 1] : b; }
+	for (int b = 0; b < nc; ++b) { inq[b + 1] = inq[b] + inrun[b]; first[b] = same(b - 1, b) ? first[b - 1] : b; }
 	for (int b = 0; b < nc; ++b) { // the tile that holds position p of the segment is first + (p - 1) / T
 		const Chunk &k = ch[b];
 		if (!(k.flags & CHUNK_ANCHOR_F) && same(b - 1, b)) { // forward: positions lo - wf .. lo - 1, the tiles t0 .. b - 1
 			const int t0 = first[b] + (int)((std::max<int64_t>(1, (int64_t)k.lo - k.wf) - 1) / T);
-			if (gc[b] == 2 || (k.wf > 0 && inq[b] - inq[t0] > 0)) glue[b] |= 1;
+			if (inrun[b] || (k.wf > 0 && inq[b] - inq[t0] > 0)) glue[b] |= 1;
 		}
 		if (!(k.flags & CHUNK_ANCHOR_B) && same(b, b + 1)) { // backward: positions hi + 1 .. hi + wb, the tiles b + 1 .. t1
 			const int t1 = first[b] + (int)((std::min<int64_t>(k.L, (int64_t)k.hi + k.wb) - 1) / T);
-			if (gc[b] == 2 || (k.wb > 0 && inq[t1 + 1] - inq[b + 1] > 0)) glue[b] |= 2;
+			if (inrun[b] || (k.wb > 0 && inq[t1 + 1] - inq[b + 1] > 0)) glue[b] |= 2;
 		}
 	}
 	// the chains, one direction at a time, in sweep order
@@ -117,13 +132,13 @@ static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
 			const bool inside = d ? f >= out : f <= out;
 			if (inside) { t.g = GapRun{f, std::abs(out - f) + 1}; t.walk = out + step; glue[f] |= d ? WG_FIRST_B : WG_FIRST_F; }
 			else { // the whole run is anchored: no tile to cross, but the tiles glued behind it still hang on one walk from the last anchored tile's exit
-				if (!(glue[f] & bit) || gc[f] == 2 || late[f]) continue; // (a later run's tile: that run's chain starts there)
+				if (!(glue[f] & bit) || inrun[f] || late[f]) continue; // (a later run's tile: that run's chain starts there)
 				t.g = GapRun{f, 0}; t.walk = f;
 			}
 			t.lev = late[f - step] ? last_lev + 1 : 0; // its first vector comes out of the walk before it
 			last_lev = t.lev;
 			for (int b = f; b != t.walk + step; b += step) late[b] = 1;
-			for (int b = t.walk + step; same(f, b) && (glue[b] & bit) && gc[b] != 2; b += step) late[b] = 1; // what the walk goes through at once
+			for (int b = t.walk + step; same(f, b) && (glue[b] & bit) && !inrun[b]; b += step) late[b] = 1; // what the walk goes through at once
 			tmp.push_back(t);
 		}
 		std::stable_sort(tmp.begin(), tmp.end(), [](const Tmp &x, const Tmp &y) { return x.lev < y.lev; });
@@ -145,10 +160,11 @@ static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
 		if ((rc = dev_alloc(c, &c->d_wg_glue, (size_t)nc))) return rc;
 		for (int d = 0; d < 2; ++d) // (a run has at least one tile, a walk one more: no list is longer than the plan)
 			if ((rc = dev_alloc(c, &c->d_wg_list[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_spec[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_runs[d], (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wg_again, (size_t)nc))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wg_again, (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_cls, (size_t)nc))) return rc;
 		c->wg_cap = nc;
 	}
 	HIPCHK(c, hipMemcpy(c->d_wg_glue, glue.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice));
+	HIPCHK(c, hipMemcpy(c->d_wg_cls, gc.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice));
 	for (int d = 0; d < 2; ++d) {
 		const psmc_hip_ctx::WgDir &D = c->wg[d];
 		if (!D.list.empty()) HIPCHK(c, hipMemcpy(c->d_wg_list[d], D.list.data(), sizeof(int32_t) * D.list.size(), hipMemcpyHostToDevice));
@@ -202,7 +218,8 @@ static int plan_wide(psmc_hip_ctx *c)
 	c->wf_T = T; c->wf_W = W;
 	c->wg_cls.clear(); c->wg_glue.clear();
 	for (auto &d : c->wg) { d.runs.clear(); d.walk.clear(); d.list.clear(); d.run_off.clear(); d.list_off.clear(); d.spec.clear(); }
-	if (c->wide_gap_tiles && nc > 0 && (rc = plan_wide_gaps(c, T, W))) return rc;
+	c->wg_mats = 0;
+	if ((c->wide_gap_tiles || c->wide_hom_tiles) && nc > 0 && (rc = plan_wide_gaps(c, T, W))) return rc;
 	c->plan_dirty = false;
 	return 0;
 }
@@ -349,7 +366,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	w.part = c->d_wf_part; w.LLpart = c->d_wf_ll; w.stage = c->d_stage; w.out = d_out;
 	c->report = FastReport{0, 0, 0, 0, 0, 0, 2};
 	c->wf_ran = true; c->wc_ran = false; c->last_fused = 3; c->wf_last_iv = iv;
-	c->wg_m_valid = false; c->wg_rechained[0] = c->wg_rechained[1] = 0;
+	c->wg_m_valid = false; c->wg_mh_T = 0; c->wg_rechained[0] = c->wg_rechained[1] = 0;
 	// "wide_gap_tiles" with a qualifying run in the plan: the tiles glued at plan time do not speculate.  Per direction: the sweeps of
 	// the others; the transfer matrix (once); then level by level the chains across the runs and ONE launch with the sweeps of the runs'
 	// tiles from the chain's vectors and the walks behind the runs (no work-group of it reads what another one of it writes).
@@ -357,11 +374,22 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	WideGap g;
 	memset(&g, 0, sizeof(g));
 	if (gaps) {
-		if (c->wg_m_cap < (size_t)n * S) {
+		if ((c->wg_mats & 1) && c->wg_m_cap < (size_t)n * S) {
 			c->wg_m_cap = 0;
 			if ((rc = dev_alloc(c, &c->d_wg_M, (size_t)n * S))) return rc;
 			c->wg_m_cap = (size_t)n * S;
 		}
+		const size_t mh = (size_t)n * S + (size_t)(c->wf_T + 3) / 4; // M_h, then the pilot's factors
+		if ((c->wg_mats & 2) && c->wg_mh_cap < mh) {
+			c->wg_mh_cap = 0;
+			if (dev_alloc(c, &c->d_wg_Mh, mh)) {
+				snprintf(msg, sizeof msg, "estep_factored: no device memory for the matrix of a homozygous tile (\"wide_hom_tiles\"): %lld bytes (%d states x %d padded states x 8, and %d scale factors)",
+				         (long long)mh * 8, n, S, (c->wf_T + 3) / 4);
+				return fail(c, PSMC_HIP_ENOMEM, msg);
+			}
+			c->wg_mh_cap = mh;
+		}
+		g.mats = c->wg_mats; g.Mh = c->d_wg_Mh; g.cls = c->d_wg_cls;
 		g.stream = st; g.ns = S; g.n_states = n; g.waves = w.waves; g.ckpt = iv; g.T = c->wf_T; g.par = c->d_wf_par; g.chunks = c->d_wf_chunks;
 		g.M = c->d_wg_M; g.X = c->d_wf_X; g.xhi = w.xhi; g.bexit = c->d_wf_bexit; g.entry = c->d_wf_entry; g.bentry = c->d_wf_bentry;
 		w.glue = c->d_wg_glue;
@@ -385,7 +413,8 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 		w.list = c->d_wg_spec[1];
 		if (launch_wide_fast(w, WF_BWARM_LIST, (int)c->wg[1].spec.size())) return fail(c, PSMC_HIP_EDEVICE, "wide sweeps", hipGetLastError());
 		if (launch_wide_gap(g, WG_MAT) || gap_levels(0)) return fail(c, PSMC_HIP_EDEVICE, "wide gap chains (forward)", hipGetLastError());
-		c->wg_m_valid = true;
+		c->wg_m_valid = (c->wg_mats & 1) != 0;
+		if (c->wg_mats & 2) c->wg_mh_T = c->wf_T;
 	}
 	int r = 0, t = 0;
 	rc = wide_rounds(c, w, false, r, t, gaps ? &g : nullptr);

@@ -25,7 +25,21 @@
 //   k_wf_gapmat                              62     0 8       78     0 6       82   192 5       85   288 5       89   384 5
 //   k_wf_gapchain forward                    68  9224 7       68 10248 7       68 12296 7       48 12296 8       46 16392 8
 //   k_wf_gapchain backward                   28  9224 8       30 10248 8       46 12296 8       64 12296 8       82 16392 5
+//   k_wf_hompilot                            72     0 7       94     0 5       94   192 5       98   288 4      106   384 4
+//   k_wf_hommat                              78     0 6       98     0 4       90   192 5       93   288 5       97   384 4
+//   k_wf_gapchain forward  HOM               70  9224 7       68 10248 7       68 12296 7       48 12296 8       44 16392 8
+//   k_wf_gapchain backward HOM               34  9224 8       36 10248 8       52 12296 8       70 12296 7       88 16392 5
 // (the chain is one work-group of 16 waves whatever the width: four waves per SIMD of one compute unit)
+//
+// "wide_hom_tiles": the same across runs of homozygosity (symbol 0 only).  A full tile of T homozygous bins maps its start vector by
+// M_h = (a D)^T-th power forward and (D a)^T-th power = D M_h D^-1 backward, D = diag(e0):
+//   k_wf_hompilot  once per E-step, one work-group: the uniform vector swept T bins under symbol 0, which yields the power-of-two
+//                  factors of a sweep through such a tile (M_h is far from stochastic: e0 < 1 at every bin);
+//   k_wf_hommat    row k of M_h = the unit vector of state k swept T bins under symbol 0 with the pilot's factors: all rows on one
+//                  scale, none can overflow (the argument: at the kernel);
+//   k_wf_gapchain HOM  the chain of a plan whose qualifying runs hold hom tiles: per tile the matrix of the tile's class (a device
+//                  copy of wg_cls), backward across a hom tile D M_h D^-1 v.  Read order, summation order and normalisation are the
+//                  plain chain's; a run of gap tiles alone gives the same bits through either instantiation.
 #include <hip/hip_runtime.h>
 #include "wave_prims.h"
 #include "struct_prims.h"
@@ -55,13 +69,73 @@ __global__ __launch_bounds__(64 * W) void k_wf_gapmat(const double *__restrict__
 	st<NPL>(M + (int64_t)k * S + k0, x);
 }
 
+// "wide_hom_tiles": the pilot of the matrix of a full tile of homozygous bins (symbol 0).  Under symbol 0 a step multiplies by e0 < 1,
+// so that matrix is far from stochastic and an unscaled row would drift towards underflow on long tiles.  ONE work-group sweeps the
+// uniform vector 1/n through T bins of symbol 0 exactly as the forward sweep steps (fstep, the power-of-two factor at every fourth
+// bin computed from the vector) and stores the factors it used: fac[j] scaled bin 4 j, ceil(T / 4) of them.
+template <int NPL, int W>
+__global__ __launch_bounds__(64 * W) void k_wf_hompilot(const double *__restrict__ par, int n, int T, double *__restrict__ fac)
+{
+	constexpr int S = 64 * NPL * W;
+	__shared__ double xs[2 * WX_SLOTS * W];
+	Xchg<W> xc = make_xchg<W>(xs);
+	const int tid = threadIdx.x, k0 = NPL * tid;
+	const WaveScanMasks wm = wave_scan_masks(xc.lane);
+	StructParN<NPL> sc;
+	load_par<NPL, S>(par, k0, true, sc);
+	double e0[NPL], e1[NPL];
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+	double x[NPL];
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) x[i] = k0 + i < n ? 1.0 / n : 0.0;
+	for (int p = 0; p < T; ++p) { // (T, p: the same in every wave)
+		if ((p & 3) == 0) {
+			const double iv = fstep<NPL, W, true, false>(sc, wm, 0, e0, e1, x, 1.0, xc);
+			if (tid == 0) fac[p >> 2] = iv;
+		} else fstep<NPL, W, false, false>(sc, wm, 0, e0, e1, x, 1.0, xc);
+	}
+}
+
+// ... and the matrix: row k of M_h is the unit vector of state k swept T bins under symbol 0 with the PILOT's factors (fstep GIVEN), one
+// work-group per row as k_wf_gapmat.  Every row is multiplied by the same powers of two, which is exact: M_h is the sweep's own tile
+// map, x -> e0 . (a^T x) taken T times, on one common scale -- and the chain normalises after every application, so the scale drops
+// out.  No row can overflow: all entries are non-negative and e_k <= n u elementwise (u the uniform vector), so by linearity
+// e_k M_h <= n (u M_h) elementwise, and u M_h is the pilot's own vector, which its factors hold at a sum below 2 at every scaled bin
+// (it only shrinks in between: every step's column sums are at most max e0 <= 1).  A row underflows only where it is negligible
+// against the pilot by the whole range of a double -- a state the chain's product could not see either.
+template <int NPL, int W>
+__global__ __launch_bounds__(64 * W) void k_wf_hommat(const double *__restrict__ par, int T, const double *__restrict__ fac, double *__restrict__ M)
+{
+	constexpr int S = 64 * NPL * W;
+	__shared__ double xs[2 * WX_SLOTS * W];
+	Xchg<W> xc = make_xchg<W>(xs);
+	const int tid = threadIdx.x, k0 = NPL * tid, k = blockIdx.x;
+	const WaveScanMasks wm = wave_scan_masks(xc.lane);
+	StructParN<NPL> sc;
+	load_par<NPL, S>(par, k0, true, sc);
+	double e0[NPL], e1[NPL];
+	ld<NPL>(par + WP_E0 * S + k0, e0); ld<NPL>(par + WP_E1 * S + k0, e1);
+	double x[NPL];
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) x[i] = k0 + i == k ? 1.0 : 0.0;
+	for (int p = 0; p < T; ++p) { // (T, p: the same in every wave)
+		if ((p & 3) == 0) fstep<NPL, W, true, true>(sc, wm, 0, e0, e1, x, fac[p >> 2], xc);
+		else fstep<NPL, W, false, false>(sc, wm, 0, e0, e1, x, 1.0, xc);
+	}
+	st<NPL>(M + (int64_t)k * S + k0, x);
+}
+
 constexpr int WG_THREADS = 1024;
 
-template <int S, bool BWD>
+// HOM ("wide_hom_tiles", a plan whose qualifying runs hold hom tiles; false: the kernel as it was, the three last arguments unused): the
+// matrix of every application is the crossed tile's own -- M_h where cls says 4, else M -- and the backward product of a hom tile is
+// bt_lo = D M_h D^-1 bt_{hi+1}, D = diag(e0): the sweep's backward map is (D a)^T = D (a D)^T D^-1, and (a D)^T is what k_wf_hommat built.
+template <int S, bool BWD, bool HOM = false>
 __global__ __launch_bounds__(WG_THREADS) void k_wf_gapchain(const double *__restrict__ M, int n, const Chunk *__restrict__ chunks,
                                                               const GapRun *__restrict__ runs, const double *__restrict__ X,
                                                               const double *__restrict__ xhi, const double *__restrict__ bexit,
-                                                              double *__restrict__ dst)
+                                                              double *__restrict__ dst, const double *__restrict__ Mh = nullptr,
+                                                              const int *__restrict__ cls = nullptr, const double *__restrict__ e0 = nullptr)
 {
 	constexpr int KS = WG_THREADS / S; // forward: ranges of rows (5 at S = 192, 4, 2, 1, 1)
 	__shared__ double v[S], y[KS * S], tot;
@@ -78,13 +152,22 @@ __global__ __launch_bounds__(WG_THREADS) void k_wf_gapchain(const double *__rest
 	}
 	__syncthreads();
 	for (int i = 1; i <= r.count; ++i) { // (r, n: the same in every thread -- every barrier below is reached by all)
+		const double *Mt = M;
+		bool hom = false; // (the crossed tile's class: the same in every thread)
+		if constexpr (HOM) { hom = cls[BWD ? r.first - i + 1 : r.first + i - 1] == 4; if (hom) Mt = Mh; }
+		if constexpr (HOM && BWD) {
+			if (hom) { // D^-1 bt_{hi+1}, in place (states n .. S - 1 are 0 and stay so)
+				if (t < n) v[t] = v[t] / e0[t];
+				__syncthreads();
+			}
+		}
 		if (!BWD) {
 			const int g = t / S, col = t - g * S, kc = (n + KS - 1) / KS;
 			if (g < KS) {
 				const int k1 = min(n, (g + 1) * kc);
 				double acc = 0.0;
 #pragma unroll 8
-				for (int k = g * kc; k < k1; ++k) acc = __builtin_fma(v[k], M[(int64_t)k * S + col], acc);
+				for (int k = g * kc; k < k1; ++k) acc = __builtin_fma(v[k], Mt[(int64_t)k * S + col], acc);
 				y[g * S + col] = acc;
 			}
 			__syncthreads();
@@ -96,12 +179,12 @@ __global__ __launch_bounds__(WG_THREADS) void k_wf_gapchain(const double *__rest
 			}
 		} else {
 			for (int k = wave; k < n; k += WG_THREADS / 64) {
-				const double *row = M + (int64_t)k * S;
+				const double *row = Mt + (int64_t)k * S;
 				double acc = 0.0;
 #pragma unroll
 				for (int j = 0; j < S / 64; ++j) acc = __builtin_fma(row[lane + 64 * j], v[lane + 64 * j], acc);
 				acc = wave_total(acc);
-				if (lane == 0) y[k] = acc;
+				if (lane == 0) y[k] = HOM && hom ? acc * e0[k] : acc;
 			}
 		}
 		__syncthreads();
@@ -127,12 +210,21 @@ template <int NPL, int W> static int launch_gap(const WideGap &w, int what)
 	constexpr int S = 64 * NPL * W;
 	hipStream_t st = w.stream;
 	switch (what) {
-	case WG_MAT: hipLaunchKernelGGL((k_wf_gapmat<NPL, W>), dim3(w.n_states), dim3(64 * W), 0, st, w.par, w.T, w.M); break;
+	case WG_MAT:
+		if (w.mats & 1) hipLaunchKernelGGL((k_wf_gapmat<NPL, W>), dim3(w.n_states), dim3(64 * W), 0, st, w.par, w.T, w.M);
+		if (w.mats & 2) { // the pilot, then the rows of M_h with its factors (behind M_h in the same buffer)
+			double *fac = w.Mh + (int64_t)w.n_states * S;
+			hipLaunchKernelGGL((k_wf_hompilot<NPL, W>), dim3(1), dim3(64 * W), 0, st, w.par, w.n_states, w.T, fac);
+			hipLaunchKernelGGL((k_wf_hommat<NPL, W>), dim3(w.n_states), dim3(64 * W), 0, st, w.par, w.T, fac, w.Mh);
+		}
+		break;
 	case WG_CHAIN_F:
-		if (w.n_runs > 0) hipLaunchKernelGGL((k_wf_gapchain<S, false>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, w.ckpt == WCK ? w.xhi : nullptr, w.bexit, w.entry);
+		if (w.n_runs > 0 && (w.mats & 2)) hipLaunchKernelGGL((k_wf_gapchain<S, false, true>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, w.ckpt == WCK ? w.xhi : nullptr, w.bexit, w.entry, w.Mh, w.cls, w.par + WP_E0 * S);
+		else if (w.n_runs > 0) hipLaunchKernelGGL((k_wf_gapchain<S, false>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, w.ckpt == WCK ? w.xhi : nullptr, w.bexit, w.entry);
 		break;
 	case WG_CHAIN_B:
-		if (w.n_runs > 0) hipLaunchKernelGGL((k_wf_gapchain<S, true>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, nullptr, w.bexit, w.bentry);
+		if (w.n_runs > 0 && (w.mats & 2)) hipLaunchKernelGGL((k_wf_gapchain<S, true, true>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, nullptr, w.bexit, w.bentry, w.Mh, w.cls, w.par + WP_E0 * S);
+		else if (w.n_runs > 0) hipLaunchKernelGGL((k_wf_gapchain<S, true>), dim3(w.n_runs), dim3(WG_THREADS), 0, st, w.M, w.n_states, w.chunks, w.runs, w.X, nullptr, w.bexit, w.bentry);
 		break;
 	default: return -1;
 	}
@@ -145,6 +237,7 @@ int launch_wide_gap(const WideGap &w, int what)
 {
 	if (w.waves > 1 ? w.ns != 256 * w.waves : (w.ns != 192 && w.ns != 256)) return -1;
 	if (w.ckpt != 1 && !(w.ckpt == wide::WCK && w.xhi)) return -1;
+	if (!(w.mats & 3) || ((w.mats & 2) && !(w.Mh && w.cls))) return -1;
 	switch (w.ns) {
 	case 192: return wide::launch_gap<3, 1>(w, what);
 	case 256: return wide::launch_gap<4, 1>(w, what);

@@ -288,6 +288,16 @@ struct psmc_hip_ctx {
 	// wg_cls: 0, 1 = gap tile outside a qualifying run, 2 = gap tile of one; wg_glue: bit 0 forward, bit 1 backward, WG_FIRST_F / WG_FIRST_B
 	// (wide_fast.h).  All empty / zero with the option off or without a qualifying run: then the E-step is the one without the option.
 	int wide_gap_tiles = 0, wide_gap_min = 0;
+	// "wide_hom_tiles" = 1, the same for runs of homozygosity.  k_tile_class answers 0 het, 1 all missing, 2 all homozygous, 3 het-free
+	// mix.  A HOM TILE is a full tile (exactly T bins) of class 2 that is neither the first nor the last of its segment.  A CHAIN TILE is a
+	// gap tile when "wide_gap_tiles" is on, or a hom tile when "wide_hom_tiles" is on; a RUN is a maximal sequence of consecutive chain
+	// tiles of one segment, and it QUALIFIES when "wide_gap_tiles" is on and its gap tiles total at least "wide_gap_min" bins, or
+	// "wide_hom_tiles" is on and its hom tiles total at least "wide_hom_min" bins (0 = auto for either: a quarter of the plan's warm-up).
+	// With "wide_hom_tiles" = 0 that is the rule above.  Glue, levels, lists and chains do not look at what a tile holds: everything
+	// above and below holds with "tile of a qualifying run" for "gap tile of a qualifying run".  A het-free tile with both kinds of bin
+	// (class 3) is an ordinary data tile: it ends a run.  wg_cls gains 3 = hom tile outside a qualifying run, 4 = hom tile of one; the
+	// chain applies the matrix of the tile's own kind (estep_wide_gap.hip: d_wg_Mh across class 4, d_wg_M across class 2).
+	int wide_hom_tiles = 0, wide_hom_min = 0;
 	std::vector<int32_t> wg_cls, wg_glue;
 	// One direction of the plan's chains (d = 0 forward, 1 backward).  A chain starts behind the run's tiles that are anchored in its
 	// direction (their speculation is exact) and ends with the start vector of the first tile behind the run, where one walk goes on
@@ -312,6 +322,10 @@ struct psmc_hip_ctx {
 	GapRun *d_wg_runs[2] = {nullptr, nullptr}, *d_wg_again = nullptr; // ... and the chains a repair round runs again
 	double *d_wg_M = nullptr; size_t wg_m_cap = 0; // [n][padded width] the transfer matrix of a full gap tile
 	bool wg_m_valid = false;        // the last wide fast E-step built d_wg_M (psmc_hip_wide_gap_matrix, the diagnostic library)
+	int wg_mats = 0;                // what the plan's qualifying runs hold: bit 0 gap tiles (d_wg_M), bit 1 hom tiles (d_wg_Mh, d_wg_cls)
+	double *d_wg_Mh = nullptr; size_t wg_mh_cap = 0; // [n][padded width] the matrix of a full hom tile on the pilot's scale, then the pilot's ceil(T / 4) factors
+	int wg_mh_T = 0;                // the tile length d_wg_Mh was built for by the last wide fast E-step; 0: it built none (psmc_hip_wide_hom_matrix)
+	int *d_wg_cls = nullptr;        // [tiles] wg_cls on the device (sized with d_wg_glue)
 	int wg_rechained[2] = {0, 0};   // chains the last wide fast E-step's repair rounds ran again, forward | backward (psmc_hip_wide_gap_rechained)
 	int wg_cap = 0;
 };

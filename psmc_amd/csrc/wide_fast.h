@@ -43,6 +43,7 @@ int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wi
 // The transfer-matrix chain across qualifying runs of missing data ("wide_gap_tiles", estep_wide_gap.hip).  One chain per run and
 // direction.  Forward: v = the exit vector of tile first - 1 (its last X row; ckpt == 8: xhi), entry[first] = v, then `count` times
 // v <- v M (normalised), entry[first + i] = v.  Backward: v = bexit[first + 1], bentry[first] = v, then v <- M v, bentry[first - i] = v.
+// "wide_hom_tiles": across a hom tile (class 4) the matrix is Mh -- forward v <- v Mh, backward v <- D Mh D^-1 v with D = diag(e0).
 struct GapRun { int32_t first, count; };
 enum { WG_MAT, WG_CHAIN_F, WG_CHAIN_B };
 
@@ -53,6 +54,9 @@ struct WideGap {
 	const double *par;                // as WideLaunch
 	const Chunk *chunks;
 	double *M;                        // [n_states][ns]: row k = the unit vector of state k swept T bins forward, unscaled
+	int mats;                         // bit 0: the plan's qualifying runs hold gap tiles (M); bit 1: they hold hom tiles ("wide_hom_tiles": Mh, cls)
+	double *Mh;                       // bit 1: [n_states][ns] the same under symbol 0 with the pilot's power-of-two factors, then the ceil(T / 4) factors
+	const int *cls;                   // bit 1: [tiles of the plan] wg_cls -- a chain applies Mh across a tile of class 4, M across every other
 	const GapRun *runs; int n_runs;   // WG_CHAIN_*: the chains of this launch, one work-group each
 	const double *X, *xhi, *bexit;    // where the chains start
 	double *entry, *bentry;           // what they write

@@ -35,6 +35,11 @@
 
   --gap-tiles sets "wide_gap_tiles" = 1 on the wide contexts of every leg (the exact-kernel contexts are what they are).
 
+  --hom-tiles sets "wide_hom_tiles" = 1 on the same contexts: runs of homozygosity are crossed by the chain with the matrix of a
+  homozygous tile.  --plant-hom LEN[,LEN...] plants such runs in the chosen input first: stretch k of m (k = 1 .. m) starts at bin
+  k total / (m + 1) of the input, counted over its segments in order, and ends after LEN bins or at its segment's end; its het bins
+  become symbol 0 (missing bins stay).  No random draw: the same input at every call.
+
   --ckpt sets "wide_ckpt" = 1 on the wide contexts of (a) and (e): X at every 8th bin only, the rest recomputed in the accumulate
   sweep.  Beside every time, (a) and (e) print what psmc_hip_wide_table_info reports: the bytes of X the context holds.
   With --decode it sets "wide_ckpt" = 1 and "wide_decode_ckpt" = 1 on the wide context of (d): the decoding E-step keeps checkpoints
@@ -45,6 +50,7 @@ Library calls are synchronous.  Writes one JSON object to stdout (progress on st
     python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
     python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
     python scripts/wide_fast_timing.py --stress --states 200,300,1024 --steps 4 --exact-steps 0 [--ckpt] [--gap-tiles]
+    python scripts/wide_fast_timing.py --states 200,300,1024 --steps 4 --exact-steps 0 --plant-hom 20000,20000,200000 [--hom-tiles]
     python scripts/wide_fast_timing.py --decode --stress --states 300,1024
     python scripts/wide_fast_timing.py --decode --stress --states 200,300,1024 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
@@ -95,7 +101,24 @@ def params_seq(n, steps, seed=11):
     return out
 
 
-GAP_OPTS = {}   # --gap-tiles: {"wide_gap_tiles": 1} on the wide contexts of every leg
+GAP_OPTS = {}   # --gap-tiles: {"wide_gap_tiles": 1} on the wide contexts of every leg; --hom-tiles: "wide_hom_tiles" likewise
+
+
+def plant_hom(segs, lens):
+    """--plant-hom: stretch k of m = len(lens) starts at bin k total / (m + 1) of the input (k = 1 .. m) and holds lens[k - 1] bins or
+    ends with its segment; its het bins become symbol 0.  Returns the segments and [(segment, first bin, bins, hets removed)]."""
+    segs = [np.array(s, dtype=np.uint8) for s in segs]
+    ends = np.cumsum([len(s) for s in segs])
+    total, m, planted = int(ends[-1]), len(lens), []
+    for k, ln in enumerate(lens, 1):
+        at = k * total // (m + 1)
+        i = int(np.searchsorted(ends, at, side="right"))
+        lo = at - (int(ends[i - 1]) if i else 0)
+        hi = min(len(segs[i]), lo + ln)
+        hets = int((segs[i][lo:hi] == 1).sum())
+        segs[i][lo:hi][segs[i][lo:hi] == 1] = 0
+        planted.append((i, int(lo), int(hi - lo), hets))
+    return segs, planted
 
 
 def table_info(es):
@@ -121,7 +144,13 @@ def library_part(hip, segs, n, steps, exact_steps, ckpt=False):
                            warm_err_fwd=d["warm_err_fwd"], warm_err_bwd=d["warm_err_bwd"]))
     d = es.fast_diag()
     ti = table_info(es)
-    r.update(wide_gap_tiles=int(bool(GAP_OPTS)), wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None, fast_later_ms_median=float(np.median(ms[1:])))
+    r.update(wide_gap_tiles=int(GAP_OPTS.get("wide_gap_tiles", 0)), wide_hom_tiles=int(GAP_OPTS.get("wide_hom_tiles", 0)), wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None, fast_later_ms_median=float(np.median(ms[1:])))
+    if GAP_OPTS:
+        try:
+            cls = es.wide_plan_tiles()["cls"]
+            r.update(plan_classes=[int(x) for x in np.bincount(cls, minlength=5)], chains=[len(c) for c in es.wide_gap_chains()], rechained=es.wide_gap_rechained())
+        except Exception as ex:   # (PSMC_HIP_LIB: an older build without the diagnostics)
+            r.update(plan_classes=str(ex))
     r.update(tiles=d["n_chunks"], tile_len=d["tile_len"], warmup=d["warmup"], fast_ms=ms, fast_first_ms=ms[0],
              fast_later_ms_mean=float(np.mean(ms[1:])), fast_later_ms_min=float(np.min(ms[1:])), repairs=rounds)
     es.close()
@@ -345,9 +374,13 @@ def main():
     ap.add_argument("--counts-slab", type=int, default=0, help="with --counts: \"wide_counts_slab\" (0 = auto)")
     ap.add_argument("--stress", action="store_true", help="the stress fixture (tests/golden/stress, 2.2 M bins) instead of the simulated genome")
     ap.add_argument("--gap-tiles", action="store_true", help="\"wide_gap_tiles\" = 1 on the wide contexts of every leg: runs of missing data are crossed by the transfer-matrix chain (estep_wide_gap.hip); (a) prints the largest verify mismatch of every step beside its rounds")
+    ap.add_argument("--hom-tiles", action="store_true", help="\"wide_hom_tiles\" = 1 on the wide contexts of every leg: runs of homozygosity are crossed by the transfer-matrix chain with the matrix of a homozygous tile")
+    ap.add_argument("--plant-hom", default="", help="LEN[,LEN...]: turn the het bins of stretches of these lengths into symbol 0, at offsets k total / (m + 1) of the chosen input")
     args = ap.parse_args()
     if args.gap_tiles:
         GAP_OPTS["wide_gap_tiles"] = 1
+    if args.hom_tiles:
+        GAP_OPTS["wide_hom_tiles"] = 1
     from psmc_amd import hip, sim
     if args.stress:
         segs = stress_segs()
@@ -359,6 +392,9 @@ def main():
         t = time.perf_counter()
         segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
         out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
+    if args.plant_hom:
+        segs, planted = plant_hom(segs, [int(x) for x in args.plant_hom.split(",") if x])
+        out["planted_hom"] = planted
     for n in [int(x) for x in args.states.split(",") if x]:
         if args.counts:
             out["n%d" % n] = counts_part(hip, segs, n, args.steps, args.exact_steps, args.counts_slab, args.ckpt)
