@@ -255,6 +255,22 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           (exact mode, up to 128 states, "wide_fast" = 0).  Other values: PSMC_HIP_EINVAL
  *  "wide_hom_min"  auto     bins of hom tiles a run needs to qualify through them; 0 = auto = a quarter of the wide plan's warm-up, as
  *                           "wide_gap_min" and "hom_min".  Negative: PSMC_HIP_EINVAL
+ *  "wide_mix_tiles" 0       1 (it has an effect only with "wide_hom_tiles" = 1): het-free tiles that hold BOTH homozygous and missing bins
+ *                           join the chain -- a real .psmcfa has `N` bins scattered through its runs of homozygosity, and without this
+ *                           option every such tile ends a run.  A mix tile is a full tile without a het that holds both symbols and is
+ *                           neither the first nor the last tile of its segment.  Mix tiles are admitted in plan order while the
+ *                           matrices of all admitted ones fit "wide_mix_mb" (and at most 65535 tiles); this happens before runs are formed, so a refused tile ends
+ *                           a run as it does without the option.  Admitted mix tiles are chain tiles beside gap and hom tiles; their
+ *                           bins count towards "wide_hom_min" like those of hom tiles.  Glue, chains, levels, verification and repair
+ *                           are unchanged.  Every mix tile of a qualifying run owns two matrices of n x (padded states) doubles, its own
+ *                           forward map F = a D_lo ... a D_hi and backward map B = D_lo a ... D_hi a (D_p = diag(e0) at a homozygous bin,
+ *                           the identity at a missing one; no diagonal relation ties the two), both swept row by row through the
+ *                           tile's symbols with the power-of-two factors of a pilot sweep of their own; all of them are built by two
+ *                           launches per E-step.  Results stay bit-reproducible and within the fast-mode tolerances.  0, or an input
+ *                           without such a tile: plan, launches and bits are those without the option.  Other values: PSMC_HIP_EINVAL
+ *  "wide_mix_mb"   2048     cap, in MB (10^6 bytes), on the matrices of the mix tiles; 1 .. 262144, anything else: PSMC_HIP_EINVAL.  A
+ *                           condition, not a tuned number: at 1024 states a tile's two matrices are 16.8 MB and the default holds about
+ *                           120 tiles; at 200 states (256 padded) they are 0.8 MB and it holds about 2500
  *  "two_phase"     auto     2: the fused back half runs as two launches, odd tiles of the second list start from the exit
  *                           vector of the tile above instead of speculating backward; 0: every tile speculates, one
  *                           launch when the tiles fit one round.  auto: 2 with two rounds, 0 with one

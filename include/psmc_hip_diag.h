@@ -103,7 +103,9 @@ int psmc_hip_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap)
  * data, neither first nor last in its segment) outside a qualifying run, 2 = gap tile of a qualifying run; glue[b] = bit 0: glued
  * forward (the tile does not speculate: its start vector comes from the transfer-matrix chain across the run, or from the walk
  * behind it), bit 1: glued backward.  With "wide_hom_tiles" = 1 also 3 = hom tile (a full tile of
- * homozygous bins only, neither first nor last in its segment) outside a qualifying run, 4 = hom tile of a qualifying run.  All zero
+ * homozygous bins only, neither first nor last in its segment) outside a qualifying run, 4 = hom tile of a qualifying run.  With
+ * "wide_mix_tiles" = 1 beside it also 5 = mix tile (a full het-free tile with both homozygous and missing bins, neither first nor
+ * last in its segment) outside a qualifying run, or over "wide_mix_mb", 6 = mix tile of a qualifying run.  All zero
  * with "wide_gap_tiles" = 0 and "wide_hom_tiles" = 0. */
 int psmc_hip_wide_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int cap);
 
@@ -133,12 +135,22 @@ int psmc_hip_wide_plan_tiles(psmc_hip_ctx *ctx, int32_t *cls, int32_t *glue, int
  * `cap`; PSMC_HIP_ESTATE when that E-step built none (no qualifying run with a hom tile).  A chain applies it across the tiles of
  * class 4: forward v <- v M_h, backward v <- D M_h D^-1 v with D = diag(e0), normalised to sum 1 after every application.
  *
+ * psmc_hip_wide_mix_matrix ("wide_mix_tiles"): one of the two matrices of the mix tile `tile` (class 6) as the last wide fast E-step
+ * built it -- dir 0: F, row k = the unit vector of state k swept forward through the tile's own symbols; dir 1: B, row k = the unit
+ * vector times the first bin's emission swept forward through the symbols from the second bin on and one missing bin -- n rows of the
+ * padded width, on the scale of that direction's pilot, followed by the pilot's ceil(T / 4) factors.  Returns the number of doubles,
+ * n x width + ceil(T / 4), and copies the first `cap`; PSMC_HIP_ESTATE when that E-step built none, PSMC_HIP_EINVAL for a tile that is
+ * not class 6 or a dir that is not 0 or 1.  A matrix is built where a chain of the plan crosses the tile in that direction
+ * (psmc_hip_wide_gap_chains: the tiles first, first +- 1, ... of a chain, `count` of them); for a class-6 tile that is anchored in
+ * the direction, or whose run has no chain, there is none: PSMC_HIP_ESTATE.  A chain applies them across the tile: forward v <- v F, backward v <- B v, normalised.
+ *
  * psmc_hip_wide_tile_vectors: every tile's start vector after the last wide fast E-step, forward (which = 0: entry) or backward
  * (which = 1: bentry), tiles x the padded width.  Returns the number of doubles and copies the first `cap`. */
 int psmc_hip_wide_gap_chains(psmc_hip_ctx *ctx, int dir, int32_t *first, int32_t *count, int32_t *walk, int32_t *level, int cap);
 int psmc_hip_wide_gap_rechained(psmc_hip_ctx *ctx, int out[2]);
 int64_t psmc_hip_wide_gap_matrix(psmc_hip_ctx *ctx, double *M, int64_t cap);
 int64_t psmc_hip_wide_hom_matrix(psmc_hip_ctx *ctx, double *M, int64_t cap);
+int64_t psmc_hip_wide_mix_matrix(psmc_hip_ctx *ctx, int tile, int dir, double *out, int64_t cap);
 int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *ctx, int which, double *out, int64_t cap);
 
 /* Diagnostics of the transfer-matrix chains of the fast path up to 128 states (the glued runs of the structured plan: learned runs,

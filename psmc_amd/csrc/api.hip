@@ -242,6 +242,8 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "wide_gap_min") { if (!(v >= 0 && v <= 2147483647.0)) return PSMC_HIP_EINVAL; c->wide_gap_min = (int)v; c->plan_dirty = true; }
 	else if (k == "wide_hom_tiles") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_hom_tiles = (int)v; c->plan_dirty = true; } // api_wide_fast.hip plan_wide_gaps
 	else if (k == "wide_hom_min") { if (!(v >= 0 && v <= 2147483647.0)) return PSMC_HIP_EINVAL; c->wide_hom_min = (int)v; c->plan_dirty = true; }
+	else if (k == "wide_mix_tiles") { if (v != 0 && v != 1) return PSMC_HIP_EINVAL; c->wide_mix_tiles = (int)v; c->plan_dirty = true; } // api_wide_fast.hip plan_wide_gaps
+	else if (k == "wide_mix_mb") { if (!(v >= 1 && v <= 262144.0) || v != (double)(int)v) return PSMC_HIP_EINVAL; c->wide_mix_mb = (int)v; c->plan_dirty = true; }
 	else if (k == "rep_impl") c->rep_impl = v < 0 ? -1 : (v != 0 ? 1 : 0);
 	else return PSMC_HIP_EINVAL;
 	return PSMC_HIP_OK;

@@ -365,6 +365,25 @@ extern "C" int64_t psmc_hip_wide_hom_matrix(psmc_hip_ctx *c, double *M, int64_t 
 	return len;
 }
 
+extern "C" int64_t psmc_hip_wide_mix_matrix(psmc_hip_ctx *c, int tile, int dir, double *out, int64_t cap)
+{
+	if (!c || cap < 0 || (cap > 0 && !out)) return PSMC_HIP_EINVAL;
+	if (c->plan_dirty || c->wf_chunks.empty() || !c->wf_ran) return no_wide_plan(c, "wide_mix_matrix");
+	if (!c->wg_mx_T || !c->wg_mx_n || !c->d_wg_Mx) return fail(c, PSMC_HIP_ESTATE, "wide_mix_matrix: the last wide fast E-step built no matrix of a mix tile (no qualifying run with a mix tile, or \"wide_mix_tiles\" = 0)");
+	if (dir < 0 || dir > 1 || tile < 0 || tile >= (int)c->wg_cls.size() || c->wg_cls[tile] != 6 || c->wg_mix_slot[tile] < 0)
+		return fail(c, PSMC_HIP_EINVAL, "wide_mix_matrix: not a mix tile of a qualifying run (class 6 of psmc_hip_wide_plan_tiles), or dir is not 0 or 1");
+	const int64_t ms = (int64_t)c->n * wf_width(c), nf = (c->wg_mx_T + 3) / 4, at = 2 * (int64_t)c->wg_mix_slot[tile] + dir;
+	if (std::find(c->wg_mix_jobs.begin(), c->wg_mix_jobs.end(), (int32_t)at) == c->wg_mix_jobs.end())
+		return fail(c, PSMC_HIP_ESTATE, "wide_mix_matrix: no chain of the plan crosses this tile in this direction (psmc_hip_wide_gap_chains), so the last wide fast E-step built no such matrix");
+	if (cap > 0) { // the matrix, then its pilot's factors (which lie behind all matrices)
+		HIPCHK(c, hipSetDevice(c->device));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		HIPCHK(c, hipMemcpy(out, c->d_wg_Mx + at * ms, sizeof(double) * (size_t)std::min(cap, ms), hipMemcpyDeviceToHost));
+		if (cap > ms) HIPCHK(c, hipMemcpy(out + ms, c->d_wg_Mx + 2 * (int64_t)c->wg_mx_n * ms + at * nf, sizeof(double) * (size_t)std::min(cap - ms, nf), hipMemcpyDeviceToHost));
+	}
+	return ms + nf;
+}
+
 extern "C" int64_t psmc_hip_wide_tile_vectors(psmc_hip_ctx *c, int which, double *out, int64_t cap)
 {
 	if (!c || which < 0 || which > 1 || cap < 0 || (cap > 0 && !out)) return PSMC_HIP_EINVAL;

@@ -29,6 +29,9 @@
 // "wide_hom_tiles" = 1: the same for runs of homozygosity -- full tiles of symbol 0 only are chain tiles too, a run qualifies through its
 // gap tiles ("wide_gap_min") or through its hom tiles ("wide_hom_min"), and across a hom tile the chain applies the matrix of a full
 // tile of homozygous bins, built beside the other one (pilot, then rows: estep_wide_gap.hip).  Glue, levels, lists, rounds: unchanged.
+// "wide_mix_tiles" = 1 (with "wide_hom_tiles"): het-free tiles that hold both symbol 0 and `N` are chain tiles too, as far as "wide_mix_mb"
+// admits their matrices -- two per tile, the tile's own forward and backward map, each built where a chain of the plan crosses the tile
+// in that direction, all of them by one pilot launch and one row launch per E-step beside the other two matrices, on the same stream.  Glue, levels, lists, rounds: unchanged.
 //
 // One E-step: forward sweep of every tile and backward warm-up of every tile; forward verify / repair rounds; the accumulate sweep
 // of every tile; backward verify / repair rounds; LL and the fixed-order reduction.  A round copies the verify flags to the host,
@@ -47,10 +50,11 @@ void free_wide_fast(psmc_hip_ctx *c)
 	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
 	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi, c->d_wc_V, c->d_wc_Xs, c->d_wc_P, c->d_wc_a, c->d_wc_out, c->d_wc_kr, c->d_wc_vrow};
 	for (void *q : p) if (q) (void)hipFree(q);
-	void *gp[] = {c->d_wg_glue, c->d_wg_list[0], c->d_wg_list[1], c->d_wg_spec[0], c->d_wg_spec[1], c->d_wg_runs[0], c->d_wg_runs[1], c->d_wg_again, c->d_wg_M, c->d_wg_Mh, c->d_wg_cls};
+	void *gp[] = {c->d_wg_glue, c->d_wg_list[0], c->d_wg_list[1], c->d_wg_spec[0], c->d_wg_spec[1], c->d_wg_runs[0], c->d_wg_runs[1], c->d_wg_again, c->d_wg_M, c->d_wg_Mh, c->d_wg_cls, c->d_wg_mix_slot, c->d_wg_mix_tiles, c->d_wg_mix_jobs, c->d_wg_Mx};
 	for (void *q : gp) if (q) (void)hipFree(q);
 	c->d_wg_glue = c->d_wg_list[0] = c->d_wg_list[1] = c->d_wg_spec[0] = c->d_wg_spec[1] = nullptr;
 	c->d_wg_runs[0] = c->d_wg_runs[1] = c->d_wg_again = nullptr; c->d_wg_M = c->d_wg_Mh = nullptr; c->d_wg_cls = nullptr; c->wg_cap = 0; c->wg_m_cap = c->wg_mh_cap = 0; c->wg_mh_T = 0;
+	c->d_wg_mix_slot = c->d_wg_mix_tiles = c->d_wg_mix_jobs = nullptr; c->d_wg_Mx = nullptr; c->wg_mx_cap = 0; c->wg_mx_T = c->wg_mx_n = 0;
 	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
 	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
 	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
@@ -63,8 +67,8 @@ void free_wide_fast(psmc_hip_ctx *c)
 // rows of the X table over `bins` positions at one row per `iv` positions (iv = 8: the rows at p % 8 == 0, by absolute position)
 static inline int64_t wide_table_rows(int64_t bins, int iv) { return (bins + iv - 1) / iv; }
 
-// "wide_gap_tiles" / "wide_hom_tiles": runs of missing data and of homozygosity in the wide plan (the rule: psmc_hip_ctx.h).  One launch
-// of k_tile_class (estep_struct.hip; 1 = missing data only, 2 = homozygous bins only, 3 = both: an ordinary data tile here) over the plan's tiles,
+// "wide_gap_tiles" / "wide_hom_tiles" / "wide_mix_tiles": runs of missing data and of homozygosity in the wide plan (the rule: psmc_hip_ctx.h).  One launch
+// of k_tile_class (estep_struct.hip; 1 = missing data only, 2 = homozygous bins only, 3 = both: a mix tile, a chain tile with "wide_mix_tiles", else an ordinary data tile) over the plan's tiles,
 // with d_wf_dirty borrowed as scratch; everything else is host work.  The result is a function
 // of the selection, the data and the options, and lives with the plan.  Without a qualifying run nothing but wg_cls / wg_glue (for
 // psmc_hip_wide_plan_tiles) is left, and the E-step is the one without the option.
@@ -81,27 +85,40 @@ static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
 	gc.assign(nc, 0); glue.assign(nc, 0);
 	auto same = [&](int x, int y) { return x >= 0 && y >= 0 && x < nc && y < nc && ch[x].off == ch[y].off; };
 	// a chain tile: a FULL tile, not the first, not the last, of missing data only (gc 1) or, "wide_hom_tiles", of homozygous bins only (gc 3)
+	// "wide_mix_tiles" (with "wide_hom_tiles"): such a tile of both symbols 0 and `N` (gc 5) is a chain tile too when its two matrices are
+	// ADMITTED under "wide_mix_mb" -- in plan order, before runs are formed; a refused one ends a run as every mix tile does without the option
+	const bool mix_on = c->wide_mix_tiles && c->wide_hom_tiles;
+	const int64_t mix_bytes = (int64_t)2 * c->n * wf_width(c) * 8, mix_cap = (int64_t)c->wide_mix_mb * 1000000;
+	int64_t mix_used = 0;
+	int n_adm = 0; // (at most WG_MIX_MAX tiles are admitted whatever the cap says: the slots are numbered in 16 bits' worth of grid)
+	std::vector<char> chain(nc, 0);
 	for (int b = 0; b < nc; ++b) {
 		const bool inner = ch[b].lo > 1 && ch[b].hi < ch[b].L && ch[b].hi - ch[b].lo + 1 == T;
-		gc[b] = !inner ? 0 : (cls[b] == 1 && c->wide_gap_tiles ? 1 : (cls[b] == 2 && c->wide_hom_tiles ? 3 : 0));
+		gc[b] = !inner ? 0 : (cls[b] == 1 && c->wide_gap_tiles ? 1 : (cls[b] == 2 && c->wide_hom_tiles ? 3 : (cls[b] == 3 && mix_on ? 5 : 0)));
+		chain[b] = gc[b] == 1 || gc[b] == 3;
+		if (gc[b] == 5 && mix_used + mix_bytes <= mix_cap && n_adm < psmc_hip_ctx::WG_MIX_MAX) { chain[b] = 1; mix_used += mix_bytes; ++n_adm; }
 	}
 	const int64_t need = c->wide_gap_min > 0 ? c->wide_gap_min : W / 4, need_hom = c->wide_hom_min > 0 ? c->wide_hom_min : W / 4;
 	std::vector<std::pair<int, int>> runs; // first and last tile of every qualifying run
 	std::vector<char> inrun(nc, 0);        // tile of a qualifying run
 	c->wg_mats = 0;
 	for (int b = 0; b < nc;) {
-		if (!gc[b]) { ++b; continue; }
+		if (!chain[b]) { ++b; continue; }
 		int e = b;
-		int64_t n_gap = 0, n_hom = 0;
-		while (e < nc && same(b, e) && gc[e]) { if (gc[e] == 1) ++n_gap; else ++n_hom; ++e; }
-		if ((n_gap > 0 && n_gap * T >= need) || (n_hom > 0 && n_hom * T >= need_hom)) {
+		int64_t n_gap = 0, n_hom = 0, n_mix = 0; // (the bins of a mix tile count towards "wide_hom_min" like those of a hom tile)
+		while (e < nc && same(b, e) && chain[e]) { if (gc[e] == 1) ++n_gap; else if (gc[e] == 3) ++n_hom; else ++n_mix; ++e; }
+		if ((n_gap > 0 && n_gap * T >= need) || (n_hom + n_mix > 0 && (n_hom + n_mix) * T >= need_hom)) {
 			runs.push_back({b, e - 1});
-			for (int t = b; t < e; ++t) { inrun[t] = 1; ++gc[t]; } // 1 -> 2, 3 -> 4
-			c->wg_mats |= (n_gap > 0 ? 1 : 0) | (n_hom > 0 ? 2 : 0);
+			for (int t = b; t < e; ++t) { inrun[t] = 1; ++gc[t]; } // 1 -> 2, 3 -> 4, 5 -> 6
+			c->wg_mats |= (n_gap > 0 ? 1 : 0) | (n_hom > 0 ? 2 : 0) | (n_mix > 0 ? 4 : 0);
 		}
 		b = e;
 	}
 	if (runs.empty()) return 0;
+	if (c->wg_mats & 4) { // the slots of the class-6 tiles' matrices, in plan order
+		c->wg_mix_slot.assign(nc, -1);
+		for (int b = 0; b < nc; ++b) if (gc[b] == 6) { c->wg_mix_slot[b] = (int32_t)c->wg_mix_tiles.size(); c->wg_mix_tiles.push_back(b); }
+	}
 	std::vector<int> inq(nc + 1, 0), first(nc, 0); // prefix sums of "tile of a qualifying run"; the segment's first tile
 	for (int b = 0; b < nc; ++b) { inq[b + 1] = inq[b] + inrun[b]; first[b] = same(b - 1, b) ? first[b - 1] : b; }
 	for (int b = 0; b < nc; ++b) { // the tile that holds position p of the segment is first + (p - 1) / T
@@ -154,6 +171,15 @@ static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
 		for (int b = 0; b < nc; ++b) if (!late[b]) D.spec.push_back(b);
 	}
 	if (c->wg[0].runs.empty() && c->wg[1].runs.empty()) return 0;
+	// the matrices to build: a class-6 tile's F where a forward chain crosses it, its B where a backward chain does (a tile anchored in
+	// a direction is not crossed in it, and a run whose chain was dropped above is not crossed at all)
+	if (c->wg_mats & 4)
+		for (int d = 0; d < 2; ++d)
+			for (const GapRun &r : c->wg[d].runs)
+				for (int j = 0; j < r.count; ++j) {
+					const int t = r.first + (d ? -j : j);
+					if (gc[t] == 6) c->wg_mix_jobs.push_back(2 * c->wg_mix_slot[t] + d);
+				}
 	int rc;
 	if (nc > c->wg_cap) {
 		c->wg_cap = 0;
@@ -161,10 +187,16 @@ static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
 		for (int d = 0; d < 2; ++d) // (a run has at least one tile, a walk one more: no list is longer than the plan)
 			if ((rc = dev_alloc(c, &c->d_wg_list[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_spec[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_runs[d], (size_t)nc))) return rc;
 		if ((rc = dev_alloc(c, &c->d_wg_again, (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_cls, (size_t)nc))) return rc;
+		if ((rc = dev_alloc(c, &c->d_wg_mix_slot, (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_mix_tiles, (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_mix_jobs, (size_t)2 * nc))) return rc;
 		c->wg_cap = nc;
 	}
 	HIPCHK(c, hipMemcpy(c->d_wg_glue, glue.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice));
 	HIPCHK(c, hipMemcpy(c->d_wg_cls, gc.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice));
+	if (c->wg_mats & 4) {
+		HIPCHK(c, hipMemcpy(c->d_wg_mix_slot, c->wg_mix_slot.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice));
+		HIPCHK(c, hipMemcpy(c->d_wg_mix_tiles, c->wg_mix_tiles.data(), sizeof(int32_t) * c->wg_mix_tiles.size(), hipMemcpyHostToDevice));
+		if (!c->wg_mix_jobs.empty()) HIPCHK(c, hipMemcpy(c->d_wg_mix_jobs, c->wg_mix_jobs.data(), sizeof(int32_t) * c->wg_mix_jobs.size(), hipMemcpyHostToDevice));
+	}
 	for (int d = 0; d < 2; ++d) {
 		const psmc_hip_ctx::WgDir &D = c->wg[d];
 		if (!D.list.empty()) HIPCHK(c, hipMemcpy(c->d_wg_list[d], D.list.data(), sizeof(int32_t) * D.list.size(), hipMemcpyHostToDevice));
@@ -218,7 +250,8 @@ static int plan_wide(psmc_hip_ctx *c)
 	c->wf_T = T; c->wf_W = W;
 	c->wg_cls.clear(); c->wg_glue.clear();
 	for (auto &d : c->wg) { d.runs.clear(); d.walk.clear(); d.list.clear(); d.run_off.clear(); d.list_off.clear(); d.spec.clear(); }
-	c->wg_mats = 0;
+	c->wg_mats = 0; c->wg_mix_slot.clear(); c->wg_mix_tiles.clear(); c->wg_mix_jobs.clear();
+	c->wg_mx_T = c->wg_mx_n = 0; // (what psmc_hip_wide_mix_matrix reads beside the plan's slots: an E-step under this plan sets them again)
 	if ((c->wide_gap_tiles || c->wide_hom_tiles) && nc > 0 && (rc = plan_wide_gaps(c, T, W))) return rc;
 	c->plan_dirty = false;
 	return 0;
@@ -366,7 +399,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	w.part = c->d_wf_part; w.LLpart = c->d_wf_ll; w.stage = c->d_stage; w.out = d_out;
 	c->report = FastReport{0, 0, 0, 0, 0, 0, 2};
 	c->wf_ran = true; c->wc_ran = false; c->last_fused = 3; c->wf_last_iv = iv;
-	c->wg_m_valid = false; c->wg_mh_T = 0; c->wg_rechained[0] = c->wg_rechained[1] = 0;
+	c->wg_m_valid = false; c->wg_mh_T = 0; c->wg_mx_T = c->wg_mx_n = 0; c->wg_rechained[0] = c->wg_rechained[1] = 0;
 	// "wide_gap_tiles" with a qualifying run in the plan: the tiles glued at plan time do not speculate.  Per direction: the sweeps of
 	// the others; the transfer matrix (once); then level by level the chains across the runs and ONE launch with the sweeps of the runs'
 	// tiles from the chain's vectors and the walks behind the runs (no work-group of it reads what another one of it writes).
@@ -389,7 +422,20 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 			}
 			c->wg_mh_cap = mh;
 		}
+		const int n_mix = (int)c->wg_mix_tiles.size();
+		const size_t mx = (size_t)2 * n_mix * ((size_t)n * S + (size_t)(c->wf_T + 3) / 4); // every class-6 tile's F and B, then their pilots' factors
+		if ((c->wg_mats & 4) && c->wg_mx_cap < mx) {
+			c->wg_mx_cap = 0;
+			if (dev_alloc(c, &c->d_wg_Mx, mx)) {
+				snprintf(msg, sizeof msg, "estep_factored: no device memory for the matrices of the mix tiles (\"wide_mix_tiles\"): %lld bytes (%d tiles x 2 x %d states x %d padded states x 8, and their scale factors); \"wide_mix_mb\" caps them",
+				         (long long)mx * 8, n_mix, n, S);
+				return fail(c, PSMC_HIP_ENOMEM, msg);
+			}
+			c->wg_mx_cap = mx;
+		}
 		g.mats = c->wg_mats; g.Mh = c->d_wg_Mh; g.cls = c->d_wg_cls;
+		g.obs = c->d_obs; g.n_mix = n_mix; g.mix_tiles = c->d_wg_mix_tiles; g.mix_slot = c->d_wg_mix_slot; g.Mx = c->d_wg_Mx;
+		g.n_jobs = (int)c->wg_mix_jobs.size(); g.mix_jobs = c->d_wg_mix_jobs;
 		g.stream = st; g.ns = S; g.n_states = n; g.waves = w.waves; g.ckpt = iv; g.T = c->wf_T; g.par = c->d_wf_par; g.chunks = c->d_wf_chunks;
 		g.M = c->d_wg_M; g.X = c->d_wf_X; g.xhi = w.xhi; g.bexit = c->d_wf_bexit; g.entry = c->d_wf_entry; g.bentry = c->d_wf_bentry;
 		w.glue = c->d_wg_glue;
@@ -415,6 +461,7 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 		if (launch_wide_gap(g, WG_MAT) || gap_levels(0)) return fail(c, PSMC_HIP_EDEVICE, "wide gap chains (forward)", hipGetLastError());
 		c->wg_m_valid = (c->wg_mats & 1) != 0;
 		if (c->wg_mats & 2) c->wg_mh_T = c->wf_T;
+		if (c->wg_mats & 4) { c->wg_mx_T = c->wf_T; c->wg_mx_n = (int)c->wg_mix_tiles.size(); }
 	}
 	int r = 0, t = 0;
 	rc = wide_rounds(c, w, false, r, t, gaps ? &g : nullptr);

@@ -298,6 +298,25 @@ struct psmc_hip_ctx {
 	// (class 3) is an ordinary data tile: it ends a run.  wg_cls gains 3 = hom tile outside a qualifying run, 4 = hom tile of one; the
 	// chain applies the matrix of the tile's own kind (estep_wide_gap.hip: d_wg_Mh across class 4, d_wg_M across class 2).
 	int wide_hom_tiles = 0, wide_hom_min = 0;
+	// "wide_mix_tiles" = 1 (it has an effect only with "wide_hom_tiles" = 1): the class-3 tiles join the chain.  A MIX TILE is a full tile
+	// (exactly T bins) of k_tile_class 3 -- no het, both symbol 0 and missing bins -- that is neither the first nor the last of its
+	// segment.  Every mix tile of a qualifying run owns two matrices of n x S doubles (S the padded width), and "wide_mix_mb" (default
+	// 2048, 1 .. 262144) caps their total: the mix tiles are ADMITTED in plan order for as long as the matrices of all admitted ones stay
+	// within the cap (and they are no more than WG_MIX_MAX = 65535 tiles), and that happens before runs are formed.  An admitted mix tile is a chain tile beside gap and hom tiles; a mix
+	// tile that is not admitted is an ordinary data tile and ends a run, as every mix tile does without the option.  A RUN is a maximal
+	// sequence of consecutive chain tiles of one segment; the bins of its mix tiles count towards "wide_hom_min" like those of its hom
+	// tiles.  Glue, chains, levels and walks are unchanged: they look only at which tiles belong to a qualifying run.  wg_cls gains
+	// 5 = mix tile outside a qualifying run, or over the memory cap, and 6 = mix tile of a qualifying run; wg_mats gains bit 2.  The cap is
+	// a condition, not a tuned number: at 1024 states a tile's two matrices are 16.8 MB, so the default holds about 120 tiles; at 200
+	// states (S = 256) they are 0.8 MB and it holds about 2500.  With the option off, or without a class-3 chain tile in the input, plan,
+	// launches and bits are those without it.
+	int wide_mix_tiles = 0, wide_mix_mb = 2048;
+	static constexpr int WG_MIX_MAX = 65535;
+	std::vector<int32_t> wg_mix_slot, wg_mix_tiles; // [tiles] the slot of a class-6 tile's matrices, else -1; [slots] slot -> tile
+	std::vector<int32_t> wg_mix_jobs; // 2 slot + dir for every matrix an E-step builds: F (dir 0) of a class-6 tile that a forward chain of the plan crosses, B (dir 1) where a backward chain does
+	int *d_wg_mix_slot = nullptr, *d_wg_mix_tiles = nullptr, *d_wg_mix_jobs = nullptr; // ... on the device (sized with d_wg_glue; jobs: twice that)
+	double *d_wg_Mx = nullptr; size_t wg_mx_cap = 0; // [slots][2][n][padded width] every class-6 tile's F and B (written where wg_mix_jobs says), then [slots][2][ceil(T / 4)] their pilots' factors
+	int wg_mx_T = 0, wg_mx_n = 0;   // the tile length and the slots d_wg_Mx was built for by the last wide fast E-step; 0: it built none (psmc_hip_wide_mix_matrix)
 	std::vector<int32_t> wg_cls, wg_glue;
 	// One direction of the plan's chains (d = 0 forward, 1 backward).  A chain starts behind the run's tiles that are anchored in its
 	// direction (their speculation is exact) and ends with the start vector of the first tile behind the run, where one walk goes on
@@ -322,7 +341,7 @@ struct psmc_hip_ctx {
 	GapRun *d_wg_runs[2] = {nullptr, nullptr}, *d_wg_again = nullptr; // ... and the chains a repair round runs again
 	double *d_wg_M = nullptr; size_t wg_m_cap = 0; // [n][padded width] the transfer matrix of a full gap tile
 	bool wg_m_valid = false;        // the last wide fast E-step built d_wg_M (psmc_hip_wide_gap_matrix, the diagnostic library)
-	int wg_mats = 0;                // what the plan's qualifying runs hold: bit 0 gap tiles (d_wg_M), bit 1 hom tiles (d_wg_Mh, d_wg_cls)
+	int wg_mats = 0;                // what the plan's qualifying runs hold: bit 0 gap tiles (d_wg_M), bit 1 hom tiles (d_wg_Mh, d_wg_cls), bit 2 mix tiles (d_wg_Mx, d_wg_mix_slot)
 	double *d_wg_Mh = nullptr; size_t wg_mh_cap = 0; // [n][padded width] the matrix of a full hom tile on the pilot's scale, then the pilot's ceil(T / 4) factors
 	int wg_mh_T = 0;                // the tile length d_wg_Mh was built for by the last wide fast E-step; 0: it built none (psmc_hip_wide_hom_matrix)
 	int *d_wg_cls = nullptr;        // [tiles] wg_cls on the device (sized with d_wg_glue)

@@ -44,6 +44,7 @@ int launch_wide_fast(const WideLaunch &w, int what, int n_list = 0); // estep_wi
 // direction.  Forward: v = the exit vector of tile first - 1 (its last X row; ckpt == 8: xhi), entry[first] = v, then `count` times
 // v <- v M (normalised), entry[first + i] = v.  Backward: v = bexit[first + 1], bentry[first] = v, then v <- M v, bentry[first - i] = v.
 // "wide_hom_tiles": across a hom tile (class 4) the matrix is Mh -- forward v <- v Mh, backward v <- D Mh D^-1 v with D = diag(e0).
+// "wide_mix_tiles": across a mix tile (class 6) the matrix is the tile's own -- forward v <- v F, backward v <- B v, no D scaling.
 struct GapRun { int32_t first, count; };
 enum { WG_MAT, WG_CHAIN_F, WG_CHAIN_B };
 
@@ -57,6 +58,14 @@ struct WideGap {
 	int mats;                         // bit 0: the plan's qualifying runs hold gap tiles (M); bit 1: they hold hom tiles ("wide_hom_tiles": Mh, cls)
 	double *Mh;                       // bit 1: [n_states][ns] the same under symbol 0 with the pilot's power-of-two factors, then the ceil(T / 4) factors
 	const int *cls;                   // bit 1: [tiles of the plan] wg_cls -- a chain applies Mh across a tile of class 4, M across every other
+	// bit 2 of mats ("wide_mix_tiles"): the qualifying runs hold mix tiles, het-free tiles with both symbol 0 and `N` (class 6).  Each owns
+	// two matrices, F forward and B backward, swept bin by bin through the tile's own symbols (estep_wide_gap.hip):
+	const uint8_t *obs;               // as WideLaunch
+	int n_mix;                        // class-6 tiles of the plan, at most 65535 (a grid dimension)
+	const int *mix_tiles;             // [n_mix] slot -> tile
+	const int *mix_slot;              // [tiles of the plan] tile -> slot (read for class-6 tiles only)
+	int n_jobs; const int *mix_jobs;  // WG_MAT: [n_jobs] 2 slot + dir -- the matrices to build: the directions in which a chain of the plan crosses the tile
+	double *Mx;                       // [n_mix][2][n_states][ns] slot's F, then its B, each on its own pilot's scale (built where a job asks for it); then [n_mix][2][ceil(T / 4)] those pilots' factors
 	const GapRun *runs; int n_runs;   // WG_CHAIN_*: the chains of this launch, one work-group each
 	const double *X, *xhi, *bexit;    // where the chains start
 	double *entry, *bentry;           // what they write

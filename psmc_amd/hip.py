@@ -40,7 +40,7 @@ DIAG_EXPORTS = [
     "psmc_hip_selftest", "psmc_hip_last_timing", "psmc_hip_microbench", "psmc_hip_stream_probe", "psmc_hip_hbm_probe",
     "psmc_hip_load_probe", "psmc_hip_load_probe_st", "psmc_hip_pipe_probe", "psmc_hip_pipe_probe2", "psmc_hip_place_probe",
     "psmc_hip_cumask_probe", "psmc_hip_plan_tiles", "psmc_hip_wide_plan_tiles",
-    "psmc_hip_wide_gap_chains", "psmc_hip_wide_gap_rechained", "psmc_hip_wide_gap_matrix", "psmc_hip_wide_hom_matrix", "psmc_hip_wide_tile_vectors",
+    "psmc_hip_wide_gap_chains", "psmc_hip_wide_gap_rechained", "psmc_hip_wide_gap_matrix", "psmc_hip_wide_hom_matrix", "psmc_hip_wide_mix_matrix", "psmc_hip_wide_tile_vectors",
     "psmc_hip_fast_chain_info", "psmc_hip_fast_chain_list", "psmc_hip_fast_chain_matrices", "psmc_hip_fast_tile_vectors",
 ]
 
@@ -346,7 +346,7 @@ class HipEStep:
     def wide_plan_tiles(self):
         """Per tile of the current plan of the wide fast path (psmc_hip_wide_plan_tiles, the diagnostic library): dict(cls, glue) of
         int32 arrays -- cls 0, 1 = gap tile outside a qualifying run, 2 = gap tile of a qualifying run (options wide_gap_tiles=1,
-        wide_gap_min=bins), 3 / 4 = the same for a hom tile (wide_hom_tiles=1, wide_hom_min=bins); glue bit 0 = glued forward, bit 1 = glued backward.  HipError (invalid state) before the first wide fast
+        wide_gap_min=bins), 3 / 4 = the same for a hom tile (wide_hom_tiles=1, wide_hom_min=bins), 5 / 6 for a mix tile (wide_mix_tiles=1; 5 also: over wide_mix_mb); glue bit 0 = glued forward, bit 1 = glued backward.  HipError (invalid state) before the first wide fast
         E-step."""
         d = load_diag()
         d.psmc_hip_wide_plan_tiles.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int]
@@ -407,6 +407,16 @@ class HipEStep:
         the scale of the pilot's power-of-two factors, and those ceil(T / 4) factors (psmc_hip_wide_hom_matrix, option
         wide_hom_tiles=1); HipError (invalid state) when it built none."""
         v = self._diag_doubles("psmc_hip_wide_hom_matrix")
+        S = 64 * ((self.n + 63) // 64) if self.n <= 256 else 256 * ((self.n + 255) // 256)
+        return v[:self.n * S].reshape(self.n, S), v[self.n * S:]
+
+    def wide_mix_matrix(self, tile, dir):
+        """(matrix, factors) of the mix tile `tile` (class 6 of wide_plan_tiles; options wide_hom_tiles=1, wide_mix_tiles=1) as the last
+        wide fast E-step built it: dir=0 the forward map F, dir=1 the backward map B, (n, padded width), each on the scale of its own
+        pilot's ceil(T / 4) power-of-two factors (psmc_hip_wide_mix_matrix).  HipError: invalid state when that E-step built none,
+        invalid argument for a tile that is not class 6.  A matrix exists where a chain of the plan crosses the tile in that direction
+        (wide_gap_chains); for a class-6 tile anchored in the direction there is none: invalid state."""
+        v = self._diag_doubles("psmc_hip_wide_mix_matrix", int(tile), int(dir))
         S = 64 * ((self.n + 63) // 64) if self.n <= 256 else 256 * ((self.n + 255) // 256)
         return v[:self.n * S].reshape(self.n, S), v[self.n * S:]
 

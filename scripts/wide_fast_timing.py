@@ -40,6 +40,9 @@
   k total / (m + 1) of the input, counted over its segments in order, and ends after LEN bins or at its segment's end; its het bins
   become symbol 0 (missing bins stay).  No random draw: the same input at every call.
 
+  --mix-tiles sets "wide_mix_tiles" = 1 beside --hom-tiles: het-free tiles that hold both symbol 0 and missing bins join the chain, each
+  with two matrices of its own.
+
   --ckpt sets "wide_ckpt" = 1 on the wide contexts of (a) and (e): X at every 8th bin only, the rest recomputed in the accumulate
   sweep.  Beside every time, (a) and (e) print what psmc_hip_wide_table_info reports: the bytes of X the context holds.
   With --decode it sets "wide_ckpt" = 1 and "wide_decode_ckpt" = 1 on the wide context of (d): the decoding E-step keeps checkpoints
@@ -50,7 +53,7 @@ Library calls are synchronous.  Writes one JSON object to stdout (progress on st
     python scripts/wide_fast_timing.py [--bins 30000000] [--steps 6] [--states 149,200,256] [--cli]
     python scripts/wide_fast_timing.py --stress --states 300,512,768,1024 --steps 4 --exact-steps 1
     python scripts/wide_fast_timing.py --stress --states 200,300,1024 --steps 4 --exact-steps 0 [--ckpt] [--gap-tiles]
-    python scripts/wide_fast_timing.py --states 200,300,1024 --steps 4 --exact-steps 0 --plant-hom 20000,20000,200000 [--hom-tiles]
+    python scripts/wide_fast_timing.py --states 200,300,1024 --steps 4 --exact-steps 0 --plant-hom 20000,20000,200000 [--hom-tiles [--mix-tiles]]
     python scripts/wide_fast_timing.py --decode --stress --states 300,1024
     python scripts/wide_fast_timing.py --decode --stress --states 200,300,1024 --exact-steps 0 [--ckpt]
     python scripts/wide_fast_timing.py --stress --batch 4 --states 200 --batch-leg wide    (then --batch-leg exact; the same at 300)
@@ -144,11 +147,11 @@ def library_part(hip, segs, n, steps, exact_steps, ckpt=False):
                            warm_err_fwd=d["warm_err_fwd"], warm_err_bwd=d["warm_err_bwd"]))
     d = es.fast_diag()
     ti = table_info(es)
-    r.update(wide_gap_tiles=int(GAP_OPTS.get("wide_gap_tiles", 0)), wide_hom_tiles=int(GAP_OPTS.get("wide_hom_tiles", 0)), wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None, fast_later_ms_median=float(np.median(ms[1:])))
+    r.update(wide_gap_tiles=int(GAP_OPTS.get("wide_gap_tiles", 0)), wide_hom_tiles=int(GAP_OPTS.get("wide_hom_tiles", 0)), wide_mix_tiles=int(GAP_OPTS.get("wide_mix_tiles", 0)), wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None, fast_later_ms_median=float(np.median(ms[1:])))
     if GAP_OPTS:
         try:
             cls = es.wide_plan_tiles()["cls"]
-            r.update(plan_classes=[int(x) for x in np.bincount(cls, minlength=5)], chains=[len(c) for c in es.wide_gap_chains()], rechained=es.wide_gap_rechained())
+            r.update(plan_classes=[int(x) for x in np.bincount(cls, minlength=7)], chains=[len(c) for c in es.wide_gap_chains()], rechained=es.wide_gap_rechained())
         except Exception as ex:   # (PSMC_HIP_LIB: an older build without the diagnostics)
             r.update(plan_classes=str(ex))
     r.update(tiles=d["n_chunks"], tile_len=d["tile_len"], warmup=d["warmup"], fast_ms=ms, fast_first_ms=ms[0],
@@ -376,7 +379,10 @@ def main():
     ap.add_argument("--gap-tiles", action="store_true", help="\"wide_gap_tiles\" = 1 on the wide contexts of every leg: runs of missing data are crossed by the transfer-matrix chain (estep_wide_gap.hip); (a) prints the largest verify mismatch of every step beside its rounds")
     ap.add_argument("--hom-tiles", action="store_true", help="\"wide_hom_tiles\" = 1 on the wide contexts of every leg: runs of homozygosity are crossed by the transfer-matrix chain with the matrix of a homozygous tile")
     ap.add_argument("--plant-hom", default="", help="LEN[,LEN...]: turn the het bins of stretches of these lengths into symbol 0, at offsets k total / (m + 1) of the chosen input")
+    ap.add_argument("--mix-tiles", action="store_true", help="\"wide_mix_tiles\" = 1 beside --hom-tiles: het-free tiles with both symbol 0 and missing bins join the chain with two matrices each")
     args = ap.parse_args()
+    if args.mix_tiles:
+        GAP_OPTS["wide_mix_tiles"] = 1
     if args.gap_tiles:
         GAP_OPTS["wide_gap_tiles"] = 1
     if args.hom_tiles:
