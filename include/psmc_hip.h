@@ -525,7 +525,30 @@ int psmc_hip_post_counts(psmc_hip_ctx *ctx, int seg, const int32_t *cnt1, int32_
  * vector at its first position and s_1 = sum_k a0_k e_k(o_1); within 1e-11 relative of the exact value. */
 int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
 
-/* Decoding on a FAST context (up to 128 states): psmc_hip_decode, _posterior, _post_counts and _scales read what the last
+/* Per-bin posterior expectations of one segment on the device: the local TMRCA track (what utils/dec2ctime.pl and friends make of
+ * the rows of -D).  w is an n_w x n array of per-state weights, 1 <= n_w <= PSMC_HIP_MAX_MEAN_COLS, and
+ *   mean[(u-1)*n_w + j] = sum_k gamma_u(k) * w[j*n + k],   u = 1..L, j = 0..n_w-1,
+ * gamma_u being the posterior row psmc_hip_posterior returns for the same call state: w = t_k gives the expected coalescence time,
+ * w = t_k^2 its second moment, an indicator P(T > x).  8*n_w bytes per bin leave the GPU instead of the 8*n of the rows.  The fifth
+ * sibling of _decode / _posterior / _post_counts / _scales: the same state rules ("Decoding on a FAST context": which tables are
+ * read, ESTATE, ENOTSUP, "wide_decode", "wide_decode_ckpt", selection and reload), and it reads tables only.  PSMC_HIP_EINVAL for a
+ * NULL w or mean and for n_w outside 1..PSMC_HIP_MAX_MEAN_COLS (four: on the wide fast path every column takes one slot of the
+ * exchange between a tile's waves beside the row sum, and a wave publishes six values at most).  Per source:
+ *   - the exact tables (exact mode, the exact fallbacks of a fast context, beyond 128 states without "wide_decode"):
+ *     gamma_u(k) = f*b*s multiplied left to right, t_k = gamma_u(k) * w[j][k] rounded once (no FMA), and the sum in state order,
+ *     ((t_0 + t_1) + t_2) + ... -- bit for bit what a C loop over the rows of psmc_hip_posterior gives (estep_post_mean.hip);
+ *   - the fast tables up to 128 states: the sum of gamma_u(k) w[j][k] over the doubles psmc_hip_posterior returns, in the order of
+ *     the wave's reduction and with FMAs (estep_post_fast.hip): within (n + 8) * 2^-52 * max_k |w[j][k]| of the exact sum over
+ *     those rows;
+ *   - the wide fast tables (full or checkpoints): (sum_k g_p(k) w[j][k]) / G_p from the sweep's unnormalised g (estep_wide_post.hip),
+ *     within the same bound of the sum over the rows; from checkpoints the bits of the full table.
+ * Against an exact context given the same parameters, the fast sources are within 1e-9 * sum_k |w[j][k]| (the posterior's 1e-9
+ * absolute per state).  Every column is computed on its own: a call with several columns returns, column by column, the bits of
+ * the calls with one. */
+#define PSMC_HIP_MAX_MEAN_COLS 4
+int psmc_hip_post_mean(psmc_hip_ctx *ctx, int seg, const double *w, int32_t n_w, double *mean);
+
+/* Decoding on a FAST context (up to 128 states): psmc_hip_decode, _posterior, _post_counts, _scales and _post_mean read what the last
  * single E-step (psmc_hip_estep / _estep_device) left:
  *   - the fast tables X and bt -- the dense sweeps (any matrix, <= 64 states) or the structured ones with the unfused back half
  *     ("fuse" = 0 up to 64 states, "fuse128" = 0 for 65..128): scale-free kernels (estep_post_fast.hip) compute

@@ -1,6 +1,6 @@
-// api_decode.hip -- the decoding entry points psmc_hip_decode / _posterior / _post_counts / _scales: one segment of the last single
-// E-step, from whichever tables that E-step left (decode_source):
-//   DEC_EXACT  f, b and s of the exact kernels (estep_exact.hip, estep_wide.hip beyond 128 states)
+// api_decode.hip -- the decoding entry points psmc_hip_decode / _posterior / _post_counts / _scales / _post_mean: one segment of the
+// last single E-step, from whichever tables that E-step left (decode_source):
+//   DEC_EXACT  f, b and s of the exact kernels (estep_exact.hip, estep_wide.hip beyond 128 states; _post_mean: estep_post_mean.hip)
 //   DEC_FAST   X and bt of a fast E-step with the unfused back half, up to 128 states (estep_post_fast.hip)
 //   DEC_WIDE   X, 1/d, entry and bentry of a wide fast E-step with "wide_decode": 129..256 states (estep_wide_post.hip), and
 //              257..1024 states with "wide_fast" = 2 (the same file; the tables are 512, 768 or 1024 states wide).  After a
@@ -212,6 +212,48 @@ extern "C" int psmc_hip_post_counts(psmc_hip_ctx *c, int seg, const int32_t *cnt
 	hipError_t e3 = hipStreamSynchronize(c->stream);
 	if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
 		return fail(c, PSMC_HIP_EDEVICE, src == DEC_WIDE ? "post_counts (wide fast tables)" : "post_counts");
+	return PSMC_HIP_OK;
+}
+
+static_assert(MEAN_COLS == PSMC_HIP_MAX_MEAN_COLS, "the kernels' column count is the header's");
+
+extern "C" int psmc_hip_post_mean(psmc_hip_ctx *c, int seg, const double *w, int32_t n_w, double *mean)
+{
+	if (!c || seg < 0 || seg >= c->n_seg || !w || !mean || n_w < 1 || n_w > PSMC_HIP_MAX_MEAN_COLS) return fail(c, PSMC_HIP_EINVAL, "post_mean: bad argument");
+	int t0 = 0, nt = 0;
+	const int src = decode_source(c, seg, "post_mean", &t0, &nt);
+	if (src < 0) return src;
+	if (src == DEC_EXACT && (!c->d_f || !c->have_b || c->tables_batch)) return fail(c, PSMC_HIP_ESTATE, "post_mean: no single E-step yet");
+	HIPCHK(c, hipSetDevice(c->device));
+	const int L = c->L[seg], n = c->n;
+	// the weights at the tables' padded width, zeros beyond the n states
+	const int ws = src == DEC_WIDE ? wf_width(c) : c->ns;
+	std::vector<double> hw((size_t)n_w * ws, 0.0);
+	for (int j = 0; j < n_w; ++j) memcpy(hw.data() + (size_t)j * ws, w + (size_t)j * n, sizeof(double) * (size_t)n);
+	Scratch sc;
+	double *dw = sc.get<double>(hw.size());
+	double *dm = sc.get<double>((size_t)L * n_w);
+	if (!sc.ok) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
+	hipError_t e0 = hipMemcpyAsync(dw, hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice, c->stream);
+	int rc;
+	switch (src) {
+	case DEC_WIDE: {
+		WidePost wp;
+		wide_post_common(c, wp, WP_MEAN, t0, nt);
+		wp.wts = dw; wp.n_w = n_w; wp.mean = dm;
+		rc = launch_wide_post(wp);
+		break;
+	}
+	case DEC_FAST:
+		rc = launch_post_mean_fast(c->stream, c->d_f, c->d_b, par_re(c), c->d_obs, c->off[seg], L, c->ns, dw, n_w, dm);
+		break;
+	default:
+		rc = launch_post_mean_exact(c->stream, c->d_f, c->d_b, c->d_s, c->off[seg], L, n, c->ns, dw, n_w, dm);
+	}
+	hipError_t e1 = hipMemcpyAsync(mean, dm, sizeof(double) * (size_t)L * n_w, hipMemcpyDeviceToHost, c->stream);
+	hipError_t e2 = hipStreamSynchronize(c->stream); // (hw lives until here: the upload has been consumed)
+	if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess)
+		return fail(c, PSMC_HIP_EDEVICE, src == DEC_WIDE ? "post_mean (wide fast tables)" : "post_mean");
 	return PSMC_HIP_OK;
 }
 

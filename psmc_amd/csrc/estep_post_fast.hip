@@ -1,5 +1,5 @@
 // estep_post_fast.hip -- posterior decoding from the tables of a FAST-mode E-step (psmc_hip_decode / _posterior /
-// _post_counts / _scales on a fast context whose last single E-step left both X and bt: the dense sweeps, or the
+// _post_counts / _scales / _post_mean on a fast context whose last single E-step left both X and bt: the dense sweeps, or the
 // structured sweeps with the unfused back half, "fuse=0" / "fuse128=0").
 //
 // Conventions of the tables (estep_fast.hip, estep_struct.hip; g = seg_off + u - 1):
@@ -101,6 +101,40 @@ __global__ __launch_bounds__(64) void k_post_fast(const double *__restrict__ f, 
 	}
 }
 
+// psmc_hip_post_mean: mean[(u-1)*n_w + j] = sum_k gamma_u(k) w[j][k], gamma the doubles k_post_fast stores (gam / G).
+// w: [n_w][S], zeros beyond the n states (the padded states' gam is 0 as well).
+template <int S>
+__global__ __launch_bounds__(64) void k_post_mean_fast(const double *__restrict__ f, const double *__restrict__ b,
+                                                         const double *__restrict__ re, const uint8_t *__restrict__ obs, int64_t off,
+                                                         int L, const double *__restrict__ w, int n_w, double *__restrict__ mean)
+{
+	constexpr int PER = S / 64, MW = MEAN_COLS;
+	const int lane = threadIdx.x;
+	const int u0 = blockIdx.x * POST_BLK + 1, u1 = min(L, u0 + POST_BLK - 1);
+	double wv[MW][PER];
+#pragma unroll
+	for (int c = 0; c < MW; ++c)
+#pragma unroll
+		for (int j = 0; j < PER; ++j) wv[c][j] = c < n_w ? w[c * S + lane + 64 * j] : 0.0;
+	for (int u = u0; u <= u1; ++u) {
+		const int64_t g = off + u - 1;
+		PostRow<S> r;
+		post_row<S>(f, b, re, (int)obs[g], g, u, L, lane, r);
+		double pv[PER];
+#pragma unroll
+		for (int j = 0; j < PER; ++j) pv[j] = r.gam[j] / r.G;
+#pragma unroll
+		for (int c = 0; c < MW; ++c)
+			if (c < n_w) {
+				double t = pv[0] * wv[c][0];
+#pragma unroll
+				for (int j = 1; j < PER; ++j) t = __builtin_fma(pv[j], wv[c][j], t);
+				const double m = wsum(t);
+				if (lane == 0) mean[(int64_t)(u - 1) * n_w + c] = m;
+			}
+	}
+}
+
 // -s: the reference's scaling factors s_u (hmm_forward, khmm.c:170-186).  Tiles of the segment: T bins each, the first
 // one is tile `first` of the plan (its start vectors in entry).
 template <int S>
@@ -196,6 +230,15 @@ int launch_post_fast(hipStream_t st, const double *f, const double *b, const dou
 	const dim3 grid((L + POST_BLK - 1) / POST_BLK);
 	if (ns == 128) hipLaunchKernelGGL(k_post_fast<128>, grid, dim3(64), 0, st, f, b, sb, re, a, obs, off, L, n, post, recomb, path, maxp);
 	else hipLaunchKernelGGL(k_post_fast<64>, grid, dim3(64), 0, st, f, b, sb, re, a, obs, off, L, n, post, recomb, path, maxp);
+	return (int)hipGetLastError();
+}
+
+int launch_post_mean_fast(hipStream_t st, const double *f, const double *b, const double *re, const uint8_t *obs, int64_t off, int L,
+                          int ns, const double *w, int n_w, double *mean)
+{
+	const dim3 grid((L + POST_BLK - 1) / POST_BLK);
+	if (ns == 128) hipLaunchKernelGGL(k_post_mean_fast<128>, grid, dim3(64), 0, st, f, b, re, obs, off, L, w, n_w, mean);
+	else hipLaunchKernelGGL(k_post_mean_fast<64>, grid, dim3(64), 0, st, f, b, re, obs, off, L, w, n_w, mean);
 	return (int)hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // estep_wide_post.hip -- decoding on the wide fast path (129..1024 states, options "wide_fast" + "wide_decode"; api_decode.hip
-// drives it): psmc_hip_decode / _posterior / _post_counts / _scales from what the last wide fast E-step left, without a backward table.
+// drives it): psmc_hip_decode / _posterior / _post_counts / _scales / _post_mean from what the last wide fast E-step left, without a backward table.
 //
 // The E-step keeps the lag-normalised forward table X (and 1/d_p at p % 4 == 0), every tile's forward start vector `entry` and its
 // backward start vector bentry = bt_{top+1}, converged to "warm_tol" by the verify / repair rounds.  One more backward sweep per
@@ -17,6 +17,9 @@
 //                r = sum X a_kk bt_{p+1} rides (it does not depend on y), and one for G and, for the path, every wave's maximum
 //                and the state that holds it (an index up to 1023 is exact in a double).  iG comes from exchanged values only:
 //                the same bits in every wave.  Position L: one exchange.
+//                MEAN (psmc_hip_post_mean): instead of rows, up to four posterior expectations sum_k gamma_p(k) w_j(k) per position.  A
+//                thread keeps the NPL x n_w weights of its states in registers; a wave's share of sum_k g_p(k) w_j(k) rides in slot
+//                1 + j of the exchange that carries G (WX_SLOTS = 6: G and four columns), and mean_j = that sum * iG, stored by thread 0
 //   k_wp_cnt_add the tiles' partials added in tile order (deterministic)
 //   k_wp_scales  s_p = sum X_p / sum X_{p-1} / inv_p from X alone (X_{lo-1}: the tile's own `entry`), s_1 = sum_k a0_k e_k(o_1).
 //                ONE wave per tile at every width adds the W blocks of 64 NPL states of a row, lowest block first: no LDS, no barrier
@@ -41,6 +44,8 @@
 //   k_wp_dec  posterior + recomb., CKPT     102 10752 4      128 14336 3      130 28864 3      134 43296 3      136 57728 2
 //   k_wp_dec  counts                        118     0 4      152     0 3      156   192 3      160   288 3      162   384 3
 //   k_wp_dec  counts, CKPT                  116 10752 4      148 14336 3      150 28864 3      156 43296 3      160 57728 2
+//   k_wp_dec  mean                          126     0 4      158     0 3      154   192 3      158   288 3      162   384 3
+//   k_wp_dec  mean, CKPT                    124 10752 4      156 14336 3      150 28864 3      156 43296 3      160 57728 2
 //   k_wp_scales (64 threads)                 16     0 8       16     0 8       22     0 8       30     0 8       40     0 8
 //   k_wp_scales_ck                           80     0 6      102     0 4      106   192 4      110   288 4      112   384 4
 //   k_wp_cnt_add                         8 VGPRs at every width, no LDS
@@ -59,14 +64,27 @@ constexpr int CB = 4; // count columns one sweep of k_wp_dec carries (CB x NPL a
 // step's exchange), last: position L, whose recombination probability is 0.  One exchange (G; PATH: the waves' maxima); every wave
 // of the tile calls it.  The tie rule of the path: within a wave the lowest state of the lowest lane that holds the wave's
 // maximum, across waves the lowest wave whose maximum equals the tile's -- the lowest state wins (a NaN: wave 0's, lane 0's).
-template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT>
+// MEAN (psmc_hip_post_mean): wt = the weights of the thread's states, column by column; the wave's share of sum_k g(k) w_j(k) rides
+// in slot 1 + j of the same exchange (PATH, which uses the slots 1 and 2, is never on with it), and mean_j = that sum * iG.
+template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool MEAN>
 __device__ __forceinline__ void emit(int p, int tid, int n, const double (&g)[NPL], double r, bool last, Xchg<W> &xc,
                                      double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
                                      double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0, int min_l,
-                                     double (&acc)[CB][NPL])
+                                     double (&acc)[CB][NPL], const double (&wt)[MEAN_COLS][NPL], int n_w, double *__restrict__ mean)
 {
+	static_assert(!(MEAN && PATH) && 1 + MEAN_COLS <= WX_SLOTS, "G takes slot 0 and every column of weights one more slot");
 	const int k0 = NPL * tid;
 	xc.put(0, wave_total(lsum<NPL>(g)));
+	if (MEAN) { // (n_w is a kernel argument: the same in every wave)
+#pragma unroll
+		for (int j = 0; j < MEAN_COLS; ++j)
+			if (j < n_w) {
+				double t = g[0] * wt[j][0];
+#pragma unroll
+				for (int i = 1; i < NPL; ++i) t = __builtin_fma(g[i], wt[j][i], t);
+				xc.put(1 + j, wave_total(t));
+			}
+	}
 	if (PATH) { // the wave's first maximum: the lowest i of the lane, then the lowest lane that holds the wave's maximum
 		double best = g[0]; int arg = 0;
 #pragma unroll
@@ -89,6 +107,11 @@ __device__ __forceinline__ void emit(int p, int tid, int n, const double (&g)[NP
 			if (xc.get(1, w) == top) ktop = xc.get(2, w);
 		if (xc.get(1, 0) == top) ktop = xc.get(2, 0); // (no wave's maximum equals it -- a NaN: wave 0's)
 	}
+	double mj[MEAN_COLS];
+	if (MEAN) { // from exchanged values only: the same bits in every wave
+#pragma unroll
+		for (int j = 0; j < MEAN_COLS; ++j) mj[j] = j < n_w ? xc.sum(1 + j) * iG : 0.0;
+	}
 	xc.next();
 	if (POST) {
 		double *row = post + (int64_t)(p - 1) * n;
@@ -98,6 +121,11 @@ __device__ __forceinline__ void emit(int p, int tid, int n, const double (&g)[NP
 	}
 	if (REC && tid == 0) recomb[p - 1] = last ? 0.0 : 1.0 - r * iG;
 	if (PATH && tid == 0) { path[p - 1] = (int32_t)ktop; maxp[p - 1] = top * iG; }
+	if (MEAN && tid == 0) {
+#pragma unroll
+		for (int j = 0; j < MEAN_COLS; ++j)
+			if (j < n_w) mean[(int64_t)(p - 1) * n_w + j] = mj[j];
+	}
 	if (CNT && p <= min_l) {
 		const int32_t *c1 = cnt1 + (int64_t)(p - 1) * n_cnt + j0;
 #pragma unroll
@@ -139,14 +167,15 @@ __device__ __forceinline__ void dstep(const StructParN<NPL> &sc, const WaveScanM
 // The hang rule: the branches that enclose an exchange are `c.hi == c.L` and `top >= lo` (the tile descriptor), the bounds of the
 // loops (top, lo, the block bounds q, pb, pe), `p > top || p < lo`, `q >= lo`, `lo > 1` and `p & 3` (the loop counters) and the
 // template flags -- the same in every wave.
-template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool CKPT>
+template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool CKPT, bool MEAN>
 __global__ __launch_bounds__(64 * W) void k_wp_dec(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                      const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
                                                      const double *__restrict__ inv, const double *__restrict__ entry,
                                                      const double *__restrict__ xhi, const double *__restrict__ bentry, int n,
                                                      double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
                                                      double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0,
-                                                     int min_l, double *__restrict__ part)
+                                                     int min_l, double *__restrict__ part, const double *__restrict__ wts, int n_w,
+                                                     double *__restrict__ mean)
 {
 	constexpr int S = 64 * NPL * W;
 	__shared__ double xs[2 * WX_SLOTS * W];
@@ -165,10 +194,15 @@ __global__ __launch_bounds__(64 * W) void k_wp_dec(const double *__restrict__ pa
 	for (int j = 0; j < CB; ++j)
 #pragma unroll
 		for (int i = 0; i < NPL; ++i) acc[j][i] = 0.0;
+	double wt[MEAN_COLS][NPL]; // MEAN: the weights of the thread's states, from wts [n_w][S] (zeros beyond n)
+#pragma unroll
+	for (int j = 0; j < MEAN_COLS; ++j)
+#pragma unroll
+		for (int i = 0; i < NPL; ++i) wt[j][i] = MEAN && j < n_w ? wts[j * S + k0 + i] : 0.0;
 	const uint8_t *o = obs + c.off;
 	const double *fo = X + c.off * S + k0;
 #define WP_EMIT(p, g, r, last) \
-	emit<NPL, W, POST, REC, PATH, CNT>(p, tid, n, g, r, last, xc, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc)
+	emit<NPL, W, POST, REC, PATH, CNT, MEAN>(p, tid, n, g, r, last, xc, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc, wt, n_w, mean)
 	if (c.hi == c.L) { // position L: beta_L = 1
 		double g[NPL];
 		if (CKPT) ld<NPL>(xhi + (int64_t)b * S + k0, g); else ld<NPL>(fo + (int64_t)(c.L - 1) * S, g);
@@ -337,16 +371,20 @@ template <int NPL, int W, bool CKPT> static int launch_post(const WidePost &w)
 {
 	const dim3 grid(w.n_tiles), blk(64 * W);
 	hipStream_t st = w.stream;
-#define WP_DEC(POST, REC, PATH, CNT, j0) \
-	hipLaunchKernelGGL((k_wp_dec<NPL, W, POST, REC, PATH, CNT, CKPT>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.inv, w.entry, w.xhi, \
-	                   w.bentry, w.n_states, w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part)
+#define WP_DEC(POST, REC, PATH, CNT, MEAN, j0) \
+	hipLaunchKernelGGL((k_wp_dec<NPL, W, POST, REC, PATH, CNT, CKPT, MEAN>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.inv, w.entry, w.xhi, \
+	                   w.bentry, w.n_states, w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part, w.wts, w.n_w, w.mean)
 	switch (w.what) {
-	case WP_PATH: WP_DEC(false, false, true, false, 0); break;
-	case WP_POST: WP_DEC(true, false, false, false, 0); break;
-	case WP_REC: WP_DEC(false, true, false, false, 0); break;
-	case WP_POST_REC: WP_DEC(true, true, false, false, 0); break;
+	case WP_PATH: WP_DEC(false, false, true, false, false, 0); break;
+	case WP_POST: WP_DEC(true, false, false, false, false, 0); break;
+	case WP_REC: WP_DEC(false, true, false, false, false, 0); break;
+	case WP_POST_REC: WP_DEC(true, true, false, false, false, 0); break;
+	case WP_MEAN:
+		if (w.n_w < 1 || w.n_w > MEAN_COLS || !w.wts || !w.mean) return -1;
+		WP_DEC(false, false, false, false, true, 0);
+		break;
 	case WP_COUNTS:
-		for (int j0 = 0; j0 < w.n_cnt; j0 += CB) WP_DEC(false, false, false, true, j0);
+		for (int j0 = 0; j0 < w.n_cnt; j0 += CB) WP_DEC(false, false, false, true, false, j0);
 		if (hipGetLastError() != hipSuccess) return -1;
 		return launch_wide_post_cnt_add(w);
 	case WP_SCALES:

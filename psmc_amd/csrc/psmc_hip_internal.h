@@ -244,6 +244,12 @@ int launch_scales_fast(hipStream_t st, const double *f, const double *invd, cons
 int post_counts_fast_blocks(int min_l); // partials (n_cnt x ns doubles each) launch_post_counts_fast needs in `part`
 int launch_post_counts_fast(hipStream_t st, const double *f, const double *b, const double *re, const uint8_t *obs, int64_t off,
                             int L, int min_l, const int32_t *cnt1, int n_cnt, int n, int ns, double *part, double *cnt);
+// psmc_hip_post_mean: w is [n_w][the tables' padded width], zeros beyond the n states; mean is [L][n_w]
+constexpr int MEAN_COLS = 4; // PSMC_HIP_MAX_MEAN_COLS (api_decode.hip asserts it): G and four columns fit the WX_SLOTS of wide_prims.h
+int launch_post_mean_fast(hipStream_t st, const double *f, const double *b, const double *re, const uint8_t *obs, int64_t off, int L,
+                          int ns, const double *w, int n_w, double *mean); // estep_post_fast.hip
+int launch_post_mean_exact(hipStream_t st, const double *f, const double *b, const double *s, int64_t off, int L, int n, int S,
+                           const double *w, int n_w, double *mean);        // estep_post_mean.hip: the exact tables, any width
 int run_selftest(hipStream_t stream, unsigned *d_flags);
 int run_microbench(hipStream_t stream, double *d_out);
 int run_pipe_probe(hipStream_t stream, double *d_out, int n_waves, unsigned mask, int rounds);

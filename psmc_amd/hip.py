@@ -28,7 +28,7 @@ EXPORTS = [
     "psmc_hip_last_error", "psmc_hip_set_option", "psmc_hip_load_segments",
     "psmc_hip_load_segments_device", "psmc_hip_select", "psmc_hip_estep",
     "psmc_hip_estep_segments", "psmc_hip_estep_batch", "psmc_hip_estep_batch_cb", "psmc_hip_reserve_batch_tables", "psmc_hip_batch_info", "psmc_hip_estep_device", "psmc_hip_fast_diag", "psmc_hip_fast_repairs", "psmc_hip_fast_info", "psmc_hip_estep_factored",
-    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales",
+    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales", "psmc_hip_post_mean",
     "psmc_hip_group_selfcheck", "psmc_hip_fast_plan",
     "psmc_hip_group_create", "psmc_hip_group_destroy", "psmc_hip_group_last_error", "psmc_hip_group_set_option",
     "psmc_hip_group_load_segments", "psmc_hip_group_estep", "psmc_hip_group_estep_factored", "psmc_hip_group_info",
@@ -502,6 +502,18 @@ class HipEStep:
         self.lib.psmc_hip_scales.argtypes = [C.c_void_p, C.c_int, _dp]
         self._chk(self.lib.psmc_hip_scales(self.h, int(seg), _p(s)), "scales")
         return s
+
+    def post_mean(self, seg, w):
+        """mean (L, n_w): per-bin posterior expectations sum_k gamma_u(k) w[j, k] of segment `seg` (psmc_hip_post_mean); w is
+        (n_w, n) or (n,), 1 <= n_w <= 4 -- w = t_k: the local TMRCA.  Exact tables: bit for bit the state-order sum over the rows
+        of posterior(); fast tables: within the tolerances of include/psmc_hip.h."""
+        w = np.ascontiguousarray(np.atleast_2d(np.asarray(w, dtype=np.float64)))
+        assert w.ndim == 2 and w.shape[1] == self.n, w.shape
+        L = int(self.lens[seg])
+        mean = np.zeros((L, max(w.shape[0], 1)))
+        self.lib.psmc_hip_post_mean.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int32, _dp]
+        self._chk(self.lib.psmc_hip_post_mean(self.h, int(seg), _p(w), w.shape[0], _p(mean)), "post_mean")
+        return mean
 
     def timing(self):
         ms = np.zeros(7)

@@ -205,6 +205,7 @@ static int hb_decode(void *self, int seg, int32_t *path, double *maxp) { HB_DECO
 static int hb_posterior(void *self, int seg, double *post, double *recomb) { HB_DECODE_CALL(psmc_hip_posterior(c, l, post, recomb)) }
 static int hb_post_counts(void *self, int seg, const int32_t *cnt1, int32_t l1, int32_t n_cnt, double *cnt) { HB_DECODE_CALL(psmc_hip_post_counts(c, l, cnt1, l1, n_cnt, cnt)) }
 static int hb_scales(void *self, int seg, double *s) { HB_DECODE_CALL(psmc_hip_scales(c, l, s)) }
+static int hb_post_mean(void *self, int seg, const double *w, int32_t n_w, double *mean) { HB_DECODE_CALL(psmc_hip_post_mean(c, l, w, n_w, mean)) }
 #undef HB_DECODE_CALL
 static void hb_destroy(void *self)
 {
@@ -251,6 +252,7 @@ int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_fa
 	be->self = h; be->load = hb_load; be->estep = hb_estep; be->tables = hb_tables; be->decode = hb_decode;
 	be->estep_factored = use_factored ? hb_estep_factored : 0; be->error = hb_error; be->destroy = hb_destroy;
 	be->posterior = hb_posterior; be->post_counts = hb_post_counts; be->prepare_decode = hb_prepare_decode; be->scales = hb_scales;
+	be->post_mean = hb_post_mean;
 	return 0;
 }
 

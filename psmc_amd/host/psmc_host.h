@@ -107,6 +107,9 @@ typedef struct psmc_estep_backend {
 	int  (*prepare_decode)(void *self);
 	/* optional (may be NULL): the scaling factors s[L] of one segment (the PR line of -s, aux.c:159-164) without the tables */
 	int  (*scales)(void *self, int seg, double *s);
+	/* optional (may be NULL; last, so that an aggregate initialiser without it says no): per-bin posterior expectations
+	 * mean[(u-1)*n_w + j] = sum_k post[u][k] * w[j*n + k] of one segment, n_w <= 4 (psmc_hip_post_mean; the PSMC_TMRCA track) */
+	int  (*post_mean)(void *self, int seg, const double *w, int32_t n_w, double *mean);
 } psmc_estep_backend;
 
 /* ---- run state + driver (main.c, em.c, aux.c) */

@@ -12,6 +12,7 @@ Device times: the library calls are synchronous (hipStreamSynchronize before the
 the best of three is reported.  D2H bytes: what the call copies back.  Writes one JSON object to stdout.
 
     python scripts/decode_timing.py [--bins 30000000] [--skip-cli]
+    python scripts/decode_timing.py --mean      (psmc_hip_post_mean beside the other decoding calls: profiles/post_mean.txt)
 """
 import argparse
 import json
@@ -85,6 +86,35 @@ def library_part(hip, segs, n, params, out):
     print(json.dumps({"n%d" % n: r}), file=sys.stderr, flush=True)
 
 
+def mean_part(hip, segs, n, params, out):
+    """--mean: psmc_hip_post_mean (two columns: t_k and t_k^2, all segments) beside psmc_hip_posterior (rows only) and the four
+    older decoding calls, on the same tables: exact, and fast with the unfused back half.  A library without post_mean (the
+    parent commit's, through PSMC_HIP_LIB) gives the other columns alone."""
+    a, e, a0 = params
+    nseg, bins = len(segs), int(sum(len(s) for s in segs))
+    w = np.stack([np.linspace(0.01, 15.0, n), np.linspace(0.01, 15.0, n) ** 2])
+    cnt1 = [np.ones((len(s), 2), np.int32) for s in segs]
+    cnt = np.zeros((n, 2))
+    have = hasattr(hip.load_library(), "psmc_hip_post_mean")
+    for kind in ("exact", "fast"):
+        es = hip.HipEStep(n, mode=hip.MODE_EXACT) if kind == "exact" else hip.HipEStep(n, mode=hip.MODE_FAST, **({"fuse": 0} if n <= 64 else {"fuse128": 0}))
+        es.load_segments(segs)
+        es.estep(a, e, a0)
+        r = {"bins": bins}
+        if have:
+            r["post_mean_2col_ms"] = best_of(lambda: [es.post_mean(i, w) for i in range(nseg)])
+            r["post_mean_d2h_bytes"] = 16 * bins
+        r["posterior_rows_ms"] = best_of(lambda: [es.posterior(i, want_recomb=False) for i in range(nseg)], k=1)
+        r["posterior_d2h_bytes"] = 8 * n * bins
+        r["decode_ms"] = best_of(lambda: [es.decode(i) for i in range(nseg)])
+        r["scales_ms"] = best_of(lambda: [es.scales(i) for i in range(nseg)])
+        r["post_counts_2col_ms"] = best_of(lambda: [es.post_counts(i, cnt1[i], cnt) for i in range(nseg)])
+        r["recomb_only_ms"] = best_of(lambda: [es.posterior(i, want_post=False) for i in range(nseg)])
+        es.close()
+        out["mean_n%d_%s" % (n, kind)] = r
+        print(json.dumps({"mean_n%d_%s" % (n, kind): r}), file=sys.stderr, flush=True)
+
+
 def cli_part(segs, out):
     psmc = os.path.join(ROOT, "psmc_amd", "host", "psmc")
     r = {}
@@ -128,6 +158,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bins", type=int, default=30_000_000)
     ap.add_argument("--skip-cli", action="store_true")
+    ap.add_argument("--mean", action="store_true", help="time psmc_hip_post_mean beside psmc_hip_posterior and the other decoding calls (64 states, exact and fast) and nothing else")
     args = ap.parse_args()
     from psmc_amd import hip, sim
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -139,6 +170,10 @@ def main():
     t = time.perf_counter()
     segs = sim.simulate_genome(*p64, lens, seed=43)   # bench.py's genome
     out = {"bins": int(lens.sum()), "segments": len(segs), "simulate_s": time.perf_counter() - t}
+    if args.mean:
+        mean_part(hip, segs, 64, p64, out)
+        print(json.dumps(out))
+        return
     library_part(hip, segs, 64, p64, out)
     library_part(hip, segs, 128, p128, out)
     if not args.skip_cli:

@@ -281,7 +281,7 @@ def _spread(xs):
     return dict(min=float(np.min(xs)), median=float(np.median(xs)), max=float(np.max(xs)))
 
 
-def decode_calls(es, segs, n, full_post):
+def decode_calls(es, segs, n, full_post, mean=False):
     """one pass of every decoding call over all segments: seconds per kind"""
     longest = int(np.argmax([len(s) for s in segs]))
     c1 = [np.ones((len(s), 3), np.int32) for s in segs]
@@ -297,10 +297,17 @@ def decode_calls(es, segs, n, full_post):
     for i in (range(len(segs)) if full_post else [longest]):
         es.posterior(i)
     out["posterior_all" if full_post else "posterior_longest"] = (time.perf_counter() - t) * 1e3
+    if mean:   # --mean: psmc_hip_post_mean, two columns, beside psmc_hip_posterior's rows alone -- both over all segments
+        w = np.stack([np.linspace(0.01, 15.0, n), np.linspace(0.01, 15.0, n) ** 2])
+        for name, f in (("post_mean_2col", lambda i: es.post_mean(i, w)), ("posterior_rows_all", lambda i: es.posterior(i, want_recomb=False))):
+            t = time.perf_counter()
+            for i in range(len(segs)):
+                f(i)
+            out[name] = (time.perf_counter() - t) * 1e3
     return out
 
 
-def decode_part(hip, segs, n, repeats, full_post, exact, ckpt=False):
+def decode_part(hip, segs, n, repeats, full_post, exact, ckpt=False, mean=False):
     a, e, a0 = params_seq(n, 1)[0]
     r = {"longest_segment_bins": int(max(len(s) for s in segs))}
     es = hip.HipEStep(n, mode=hip.MODE_FAST, wide_fast=2 if n > 256 else 1, wide_decode=1, **GAP_OPTS)
@@ -315,8 +322,8 @@ def decode_part(hip, segs, n, repeats, full_post, exact, ckpt=False):
     r["wide_estep_ms"] = _spread(ms)
     ti = table_info(es)
     r.update(wide_gap_tiles=int(bool(GAP_OPTS)), wide_ckpt=int(ckpt), x_table=ti, x_table_bytes=ti["bytes"] if ti else None)
-    decode_calls(es, segs, n, full_post)   # warm-up
-    passes = [decode_calls(es, segs, n, full_post) for _ in range(repeats)]
+    decode_calls(es, segs, n, full_post, mean)   # warm-up
+    passes = [decode_calls(es, segs, n, full_post, mean) for _ in range(repeats)]
     r["wide_decode_ms"] = {k: _spread([p[k] for p in passes]) for k in passes[0]}
     es.close()
     print(json.dumps({"n%d" % n: r}), file=sys.stderr, flush=True)
@@ -324,7 +331,7 @@ def decode_part(hip, segs, n, repeats, full_post, exact, ckpt=False):
         ex = hip.HipEStep(n, mode=hip.MODE_EXACT)
         ex.load_segments(segs)
         t = time.perf_counter(); ex.estep(a, e, a0); r["exact_estep_ms"] = (time.perf_counter() - t) * 1e3
-        r["exact_decode_ms"] = decode_calls(ex, segs, n, full_post)
+        r["exact_decode_ms"] = decode_calls(ex, segs, n, full_post, mean)
         ex.close()
         print(json.dumps({"n%d" % n: {k: r[k] for k in ("exact_estep_ms", "exact_decode_ms")}}), file=sys.stderr, flush=True)
     return r
@@ -368,6 +375,7 @@ def main():
     ap.add_argument("--states", default="149,200,256")
     ap.add_argument("--cli", action="store_true")
     ap.add_argument("--decode", action="store_true", help="time the decoding calls on the wide fast tables (and on the exact ones) instead of (a), (b)")
+    ap.add_argument("--mean", action="store_true", help="with --decode: also psmc_hip_post_mean (two columns) and psmc_hip_posterior's rows alone, each over all segments (profiles/post_mean.txt)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--full-post", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="(e): the bootstrap batch of this many replicates on the wide fast path instead of (a), (b)")
@@ -407,7 +415,7 @@ def main():
         elif args.batch > 0:
             out["n%d" % n] = batch_part(hip, segs, n, args.batch, args.batch_leg, args.ckpt)
         elif args.decode:
-            out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0, args.ckpt)
+            out["n%d" % n] = decode_part(hip, segs, n, args.repeats, args.full_post, args.exact_steps > 0, args.ckpt, args.mean)
         else:
             out["n%d" % n] = library_part(hip, segs, n, args.steps, args.exact_steps, args.ckpt)
     if args.cli:
