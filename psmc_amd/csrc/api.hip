@@ -403,7 +403,9 @@ bool fill_params(const psmc_hip_ctx *c, const double *a, const double *e, const 
 			pe[k] = e[k]; pe[128 + k] = e[n + k];
 			pa0[k] = a0[k];
 		}
-		for (int k = 0; k < 128; ++k) pe[256 + k] = 1.0; // khmm.c:21
+		// khmm.c:21.  Fast mode: on the model's states only, like the two rows above -- the backward start vector of a tile is this row when bin q is
+		// missing (bwd_struct_body), and a padded state must not carry weight there; a step multiplies a padded state's zero either way
+		for (int k = 0; k < (c->mode == PSMC_HIP_MODE_FAST ? n : 128); ++k) pe[256 + k] = 1.0;
 		if (c->mode == PSMC_HIP_MODE_FAST) {
 			double *pre = pa + psmc_hip_ctx::RE128_OFF;
 			for (int i = 0; i < 384; ++i) pre[i] = pe[i] > 0.0 ? 1.0 / pe[i] : 0.0;
@@ -420,7 +422,7 @@ bool fill_params(const psmc_hip_ctx *c, const double *a, const double *e, const 
 		pe[k] = e[k]; pe[64 + k] = e[n + k];
 		pa0[k] = a0[k];
 	}
-	for (int k = 0; k < 64; ++k) pe[128 + k] = 1.0; // khmm.c:21
+	for (int k = 0; k < (c->mode == PSMC_HIP_MODE_FAST ? n : 64); ++k) pe[128 + k] = 1.0; // khmm.c:21 (fast mode: the model's states only, see above)
 	for (int i = 0; i < 192; ++i) pre[i] = pe[i] > 0.0 ? 1.0 / pe[i] : 0.0; // fast-mode expect divides the emission back out
 	for (int b = 0; b < 3; ++b)
 		for (int l = 0; l < 64; ++l)

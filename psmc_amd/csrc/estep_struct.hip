@@ -509,7 +509,12 @@ __device__ __forceinline__ void bwd_struct_body(int block, const double *__restr
 		p_first = cur.top;
 	} else {
 		const int q = min(c.hi + chunk_warm_b(c, W) + 1, L); // B_q := 1
-		ev_load<NPL, LPT>(lds_e + ((int)o[q - 1] & 3) * S, k0, x);
+		const int sq = (int)o[q - 1] & 3;
+		// a missing bin: the table's own row, 1 on the model's states and 0 on the padded ones (fill_params) -- the LDS rows of fill_lds_e hold 1
+		// everywhere, which is right for a step (a padded state receives nothing) and wrong for a START vector: the ones stayed in bentry,
+		// in the first normalisation's sum and among the "positive entries" whose column exponents the chain reads
+		if (sq < 2) ev_load<NPL, LPT>(lds_e + sq * S, k0, x);
+		else loadN<NPL>(e + 2 * S + k0, x);
 		p_first = q - 1;
 	}
 	// highest block.  A tile that holds only position L (not valid: it owns no transition) has p_first = L - 1, which is 0 for a
@@ -682,7 +687,8 @@ __global__ __launch_bounds__(64) void k_walk1_struct(const double *__restrict__ 
 		const uint8_t *o = obs + c.off;
 		StructPar1 s1; s1.mS = sp[192 + lane]; s1.wS = sp[64 + lane]; s1.mP = sp[128 + lane]; s1.wP = sp[lane]; s1.dd = sp[256 + lane];
 		const int q = min(c.hi + chunk_warm_b(c, W) + 1, L); // B_q := 1
-		double x = walk_ev((int)o[q - 1] & 3, e0, e1);
+		const int sq = (int)o[q - 1] & 3;
+		double x = sq < 2 ? walk_ev(sq, e0, e1) : e[128 + lane]; // (a missing bin: 0 on the padded states, as in bwd_struct_body)
 		const int p_first = q - 1;
 		const int g_first = (p_first - 1) >> 2, g_last = (p_low - 1) >> 2;
 		unsigned w = *reinterpret_cast<const unsigned *>(o + 4 * g_first);

@@ -45,9 +45,15 @@ def _relmax(x, y):
     return np.abs(x - y).max() / np.abs(y).max()
 
 
-def estep_fast_model(a, e, a0, segs, T=4096, W=2048, tol=None, stats=None):
-    """tol=None: pure warm-up tiling (no verification).  tol=float: speculate with W, verify, repair."""
+def estep_fast_model(a, e, a0, segs, T=4096, W=2048, tol=None, stats=None, struct=False):
+    """tol=None: pure warm-up tiling (no verification).  tol=float: speculate with W, verify, repair.
+    struct=True: the products a^T x and a bt of both sweeps go through the O(N) two-scan steps of factor_structure(a) (below), as the
+    structured kernels form them -- the model then shares the 64 ulp per entry of a the factorisation criterion admits; where the
+    criterion refuses the matrix the dense products stay.  The counts read a itself either way (A = a .* C)."""
     n = a.shape[0]
+    f = factor_structure(a) if struct else None
+    fwd = (lambda x: x @ a) if f is None else (lambda x: struct_step_forward(f, x))
+    bwd = (lambda z: a @ z) if f is None else (lambda z: struct_step_backward(f, z))
     A = np.zeros((n, n)); E = np.zeros((3, n)); LL = 0.0
     work = dict(fwd_steps=0, bwd_steps=0, fwd_rounds=0, bwd_rounds=0, bins=0)
     for seg in segs:
@@ -61,7 +67,7 @@ def estep_fast_model(a, e, a0, segs, T=4096, W=2048, tol=None, stats=None):
 
         def fstep(x, p):
             dp = x.sum() if p % NORM_EVERY == 0 else 1.0
-            g = (x * e[o[p]]) if p == 1 else e[o[p]] * (x @ a)
+            g = (x * e[o[p]]) if p == 1 else e[o[p]] * fwd(x)
             return g / dp, dp
 
         # ---------------- forward: speculative pass
@@ -100,7 +106,7 @@ def estep_fast_model(a, e, a0, segs, T=4096, W=2048, tol=None, stats=None):
 
         def bstep(btn, p):  # consumes bt_{p+1}; returns bt_p and the scale it applied
             sp = 1.0 / btn.sum() if p % NORM_EVERY == 0 else 1.0
-            return e[o[p]] * (a @ btn) * sp, sp
+            return e[o[p]] * bwd(btn) * sp, sp
 
         bentry = [None] * nc; bexit = [None] * nc
         for c, (lo, hi) in enumerate(tiles):
@@ -199,3 +205,49 @@ def struct_step_forward(f, x):
 def struct_step_backward(f, z):
     """(a z)_k = R_k SUF_k(z.c) + P_k PRE_k(z.qa) + dd_k z_k."""
     return f["R"] * np.cumsum((z * f["c"])[::-1])[::-1] + f["P"] * np.cumsum(z * f["qa"]) + f["dd"] * z
+
+
+# ---------------------------------------------------------------------------------------------
+# The reference figure of the per-cell gates (tests/test_gpu_fast_cells.py): how far two float64 evaluations of the same E-step are apart.
+CELL_FLOOR = 2.0 ** -900   # an oracle value above this is compared relatively, whatever its size against the largest
+ULP64 = 64 * 2.0 ** -53    # the factorisation criterion's allowance per entry of a
+
+
+def cell_error(x, ref):
+    """(worst relative error over the entries of ref above CELL_FLOOR, the index of that entry); (0.0, None) when there is none"""
+    x, ref = np.asarray(x, float), np.asarray(ref, float)
+    big = ref > CELL_FLOOR
+    if not big.any():
+        return 0.0, None
+    err = np.where(big, np.abs(x - ref) / np.where(big, ref, 1.0), 0.0)
+    i = np.unravel_index(int(np.argmax(err)), err.shape)
+    return float(err[i]), tuple(int(j) for j in i)
+
+
+def tri_sums(A):
+    """SL, SU, DG, CL, CU (5, n) of a count matrix (psmc_amd/parity.py tri_sums)"""
+    A = np.asarray(A, float)
+    lo, up = np.tril(A, -1), np.triu(A, 1)
+    return np.stack([lo.sum(1), up.sum(1), np.diag(A).copy(), lo.sum(0), up.sum(0)])
+
+
+def reference_error(a, e, a0, segs, o):
+    """E_ref of an input: o is the oracle's result on it.  The untiled model (one tile per segment, nothing speculated) with the dense
+    products and with the structured ones, each against the oracle; of the two the larger worst relative error
+      cell: over every cell of A and every entry of E[0], E[1] above CELL_FLOOR,
+      tri:  over every entry of the five triangular sums of A above CELL_FLOOR,
+    and the models' relative distance in LL.  dict(cell, tri, LL, dense = (cell, tri), struct = (cell, tri))."""
+    out = {}
+    for key, st in (("dense", False), ("struct", True)):
+        m = estep_fast_model(a, e, a0, segs, T=1 << 30, W=0, struct=st)
+        out[key] = (max(cell_error(m["A"], o["A"])[0], cell_error(m["E"], o["E"])[0]), cell_error(tri_sums(m["A"]), tri_sums(o["A"]))[0])
+        out[key + "_LL"] = abs(m["LL"] - o["LL"]) / abs(o["LL"])
+    out["cell"] = max(out["dense"][0], out["struct"][0])
+    out["tri"] = max(out["dense"][1], out["struct"][1])
+    out["LL"] = max(out["dense_LL"], out["struct_LL"])
+    return out
+
+
+def cell_bound(e_ref, margin=32):
+    """B of the per-cell gates: margin x max(E_ref, 64 ulp)"""
+    return margin * max(e_ref, ULP64)

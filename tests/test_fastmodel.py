@@ -73,6 +73,71 @@ def test_structured_factorisation(golden):
     assert fastmodel.factor_structure(b) is None
 
 
+def test_struct_option_of_the_model(golden, oracle):
+    """estep_fast_model(struct=True): both sweeps through the two-scan steps.  Not the dense model's bits (the factorisation is good to 64 ulp
+    per entry, not exact), the oracle's numbers per cell; and the dense model's bits where the criterion refuses the matrix."""
+    p = golden.params("n64_curve")
+    segs = golden.segs_small[:9]
+    ref = oracle.estep(p["a"], p["e"], p["a0"], segs)
+    dense = fastmodel.estep_fast_model(p["a"], p["e"], p["a0"], segs, T=1 << 30, W=0)
+    st = fastmodel.estep_fast_model(p["a"], p["e"], p["a0"], segs, T=1 << 30, W=0, struct=True)
+    assert not np.array_equal(st["A"], dense["A"])
+    for m in (dense, st):
+        assert fastmodel.cell_error(m["A"], ref["A"])[0] <= 1e-12 and fastmodel.cell_error(m["E"], ref["E"])[0] <= 1e-12
+        assert abs(m["LL"] - ref["LL"]) <= 1e-14 * abs(ref["LL"])
+    a = p["a"].copy()   # capped: not of the form
+    a[:, 40] = a[:, 40:].sum(1); a[:, 41:] = 0.0
+    assert fastmodel.factor_structure(a) is None
+    d2 = fastmodel.estep_fast_model(a, p["e"], p["a0"], segs, T=64, W=4096)
+    s2 = fastmodel.estep_fast_model(a, p["e"], p["a0"], segs, T=64, W=4096, struct=True)
+    assert np.array_equal(d2["A"], s2["A"]) and np.array_equal(d2["E"], s2["E"]) and d2["LL"] == s2["LL"]
+    # cell_error: no floor relative to the largest cell, and the index of the worst
+    x = np.array([[1.0, 1e-200], [0.0, 3.0]])
+    assert fastmodel.cell_error(x * np.array([[1.0, 1.0 + 1e-9], [1.0, 1.0]]), x) == (pytest.approx(1e-9, rel=1e-6), (0, 1))
+    assert fastmodel.cell_error(np.zeros(3), np.zeros(3)) == (0.0, None)
+    assert fastmodel.cell_bound(3e-15) == 32 * 64 * 2.0 ** -53 and fastmodel.cell_bound(1e-13) == 32e-13
+
+
+# ---------------------------------------------------------------------------------------------
+# The CPU side of tests/test_gpu_fast_cells.py (the fast E-step up to 128 states, cell by cell in the anchored regime).
+def test_fast_cells_case_table():
+    """The literal tables of the GPU file against the host model: which (model, n) pairs are HMMs at all -- the four drop-outs, no others --
+    and which of the cases the factorisation criterion refuses (what the GPU file asserts against fast_diag()["structured"])."""
+    import test_gpu_fast_cells as cells
+    import test_gpu_wide_fast_edges as edges
+    assert cells.MODELS is edges.MODELS and len(cells.MODELS) == 13
+    assert cells.SIZES == (2, 3, 63, 64, 65, 127, 128) and set(cells.NOT_HMM) <= set(cells.MODELS)
+    table = [(n, name) for n in cells.SIZES for name in cells.MODELS if cells.is_hmm(cells.host_model(name, n))]
+    assert table == cells.CASES and len(table) == 70
+    assert cells.STRUCT_REFUSED <= set(cells.CASES)
+    for n, name in cells.CASES:
+        a, e, a0 = cells.host_model(name, n)
+        assert a.shape == (n, n) and e.shape == (3, n) and a0.shape == (n,)
+        assert (fastmodel.factor_structure(a) is None) == ((n, name) in cells.STRUCT_REFUSED), (n, name)
+    assert not any(n > 64 for n, _ in cells.STRUCT_REFUSED)   # (the exact fallback beyond 64 states has no case here)
+
+
+@pytest.mark.parametrize("n", [2, 3, 63, 64, 65, 127, 128])
+def test_fast_cells_reference_error(golden, oracle, n):
+    """A condition on the inputs of tests/test_gpu_fast_cells.py, not a measurement of the device: on every case the oracle's A, E and LL
+    are finite and non-negative, and E_ref -- the untiled numpy model, dense and structured, against the oracle over EVERY cell above
+    2^-900 -- is at most 1e-12, over the five triangular sums as well.  Observed: <= 4.4e-13 (rho0 = 1e-6 at 128 states, structured;
+    dense <= 2.1e-13, theta0 = 0.3 at 128 states), typically 2e-14 .. 1e-13; LL within 6e-16 relative."""
+    import test_gpu_fast_cells as cells
+    segs = cells.cells_segs(golden)
+    for m, name in cells.CASES:
+        if m != n:
+            continue
+        par, o, r = cells.reference(oracle, golden, n, name)
+        assert cells.is_hmm(par)
+        assert np.isfinite(o["A"]).all() and np.isfinite(o["E"]).all() and np.isfinite(o["LL"]) and (o["A"] >= 0).all() and (o["E"] >= 0).all()
+        print("E_ref n %3d %-26s cell %.2e (dense %.2e struct %.2e) sums %.2e LL %.1e; B %.2e" % (
+            n, name, r["cell"], r["dense"][0], r["struct"][0], r["tri"], r["LL"], fastmodel.cell_bound(r["cell"])))
+        assert r["cell"] <= 1e-12 and r["tri"] <= 1e-12 and r["LL"] <= 1e-14, (n, name, r)
+        assert (o["A"] > fastmodel.CELL_FLOOR).all() and (o["E"] > fastmodel.CELL_FLOOR).all()   # the gate covers all n^2 + 2n cells
+    assert sum(len(s) for s in segs) == 4827
+
+
 # ---------------------------------------------------------------------------------------------
 # The CPU side of tests/test_gpu_wide_fast_edges.py (the wide fast E-step, 129 .. 256 states).
 def test_factorisation_criterion_on_the_extreme_models():
