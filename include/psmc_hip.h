@@ -271,6 +271,9 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *  "wide_mix_mb"   2048     cap, in MB (10^6 bytes), on the matrices of the mix tiles; 1 .. 262144, anything else: PSMC_HIP_EINVAL.  A
  *                           condition, not a tuned number: at 1024 states a tile's two matrices are 16.8 MB and the default holds about
  *                           120 tiles; at 200 states (256 padded) they are 0.8 MB and it holds about 2500
+ *  "vit_tile"      2048     bins per backtrace tile of psmc_hip_viterbi: 16 .. 16777216, anything else: PSMC_HIP_EINVAL.  Paths and scores do
+ *                           not depend on it: it sets how long the longest chain of dependent loads is (one tile) and how many maps of
+ *                           2 x (padded states) bytes there are (profiles/viterbi.txt)
  *  "two_phase"     auto     2: the fused back half runs as two launches, odd tiles of the second list start from the exit
  *                           vector of the tile above instead of speculating backward; 0: every tile speculates, one
  *                           launch when the tiles fit one round.  auto: 2 with two rounds, 0 with one
@@ -547,6 +550,30 @@ int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
  * the calls with one. */
 #define PSMC_HIP_MAX_MEAN_COLS 4
 int psmc_hip_post_mean(psmc_hip_ctx *ctx, int seg, const double *w, int32_t n_w, double *mean);
+
+/* Viterbi path of every loaded segment (khmm.c:83-141), in load order; psmc_hip_select is not read.
+ * path: sum of L entries, segment i at offset L[0]+..+L[i-1]; score: n_seg doubles (hmm_Viterbi's return value).
+ * Either may be NULL; with path == NULL no back-pointer table is allocated.
+ * The jointly most probable state sequence, not the per-bin argmax of psmc_hip_decode; bins are numbered as psmc_hip_decode numbers
+ * them.  The arithmetic is the reference's, bit for bit, on any context -- both modes run the same kernels (estep_viterbi.hip), 1..1024
+ * states, any matrix:
+ *   la[k][l] = log(a[l][k]), le[b][k] = log(e[b][k]) (b = 0, 1), le[2][k] = 0, l0[k] = log(a0[k]): on the host, one libm log() each
+ *   (log(0) = -inf is allowed);
+ *   V_1[k] = le[o_1][k] + l0[k];  at u = 2..L, for every k: m = -1e300, arg = -1, for l = 0..n-1: c = V_{u-1}[l] + la[k][l], if (m < c)
+ *   m = c, arg = l -- the first maximum wins, a NaN never does -- then V_u[k] = le[o_u][k] + m, bp_u[k] = arg;
+ *   the same rule over V_L gives the last state and the score; s_{u-1} = bp_u[s_u]; path[u-1] = s_u.
+ * Every candidate is one IEEE addition, and "the maximum, the lowest index among equal maxima" is exact and associative, so the
+ * kernels split the range of l over lanes and waves and still return the reference's bits.
+ * The call reads the observations only: every table, plan, learned state and selection of the context stays as it was (an E-step or
+ * a decoding call after it returns the bits it returns without it), and the device memory it allocates -- the back-pointer table,
+ * 1 byte per (bin, state padded to a multiple of 64) up to 256 states and 2 bytes beyond (1.9 GB for 30 M bins x 64 states), the
+ * tiles' maps, the path -- is released before it returns.  The backtrace runs tile by tile ("vit_tile"): per tile every state is
+ * followed down to the tile below, the maps are composed per segment, and every tile writes its piece of the path.
+ * PSMC_HIP_ESTATE: no segments loaded.  PSMC_HIP_EINVAL: a NULL parameter; both outputs NULL; a state of some segment has no
+ * predecessor of finite probability (where the reference's assert(max_l >= 0) fires -- the message names the segment, the outputs are
+ * unspecified, the context stays usable).  PSMC_HIP_ENOMEM: the message holds the table's size. */
+int psmc_hip_viterbi(psmc_hip_ctx *ctx, const double *a, const double *e, const double *a0,
+                     int32_t *path, double *score);
 
 /* Decoding on a FAST context (up to 128 states): psmc_hip_decode, _posterior, _post_counts, _scales and _post_mean read what the last
  * single E-step (psmc_hip_estep / _estep_device) left:

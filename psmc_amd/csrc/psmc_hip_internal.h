@@ -250,6 +250,36 @@ int launch_post_mean_fast(hipStream_t st, const double *f, const double *b, cons
                           int ns, const double *w, int n_w, double *mean); // estep_post_fast.hip
 int launch_post_mean_exact(hipStream_t st, const double *f, const double *b, const double *s, int64_t off, int L, int n, int S,
                            const double *w, int n_w, double *mean);        // estep_post_mean.hip: the exact tables, any width
+// estep_viterbi.hip: psmc_hip_viterbi (api_viterbi.hip).  S = the states padded to a multiple of 64; the log tables are the host's:
+// la [S][S] with la[l * S + k] = log a[l][k] (the transition matrix's own layout, so that consecutive target states k are consecutive
+// doubles), le [3][S], l0 [S], all -inf in the padding (le[2] too: a padded state can never win).
+struct VitSeg {      // one segment of the sweep's launch, longest first
+	int64_t obs_off; // its first bin in the observations
+	int64_t row_off; // ... and in the back-pointer table and the path: the bins of the segments before it in load order
+	int32_t L, seg;
+};
+struct VitTile {     // one backtrace tile: positions lo..hi (1-based) of the segment whose rows start at row_off
+	int64_t row_off;
+	int32_t lo, hi;
+};
+struct VitLaunch {
+	hipStream_t stream;
+	int n, S, wide_bp;                 // wide_bp: the table holds 2 bytes per entry (S > 256)
+	const double *la, *le, *l0;
+	const uint8_t *obs;
+	const VitSeg *segs; int n_seg;
+	void *bp;                          // [bins][S] back-pointers (row u - 1: the predecessor of every state at position u), or null: scores only
+	double *score; int32_t *end_state; // [n_seg] by segment id
+	int32_t *bad;                      // [n_seg] zeroed; 1 = a state without a finite predecessor (khmm.c's assert)
+	// the backtrace (bp != null)
+	const VitTile *tiles; int n_tiles;
+	const int32_t *seg_tile0, *seg_nt; // [n_seg] first tile and number of tiles of every segment
+	uint16_t *map;                     // [n_tiles][S] state at the tile's last bin -> state at the last bin of the tile below
+	int32_t *tile_end;                 // [n_tiles] the path's state at the tile's last bin
+	int32_t *path;                     // [bins]
+	hipEvent_t ev[5];                  // optional time stamps: start, sweep, pass A, pass B, pass C (null: none)
+};
+int launch_viterbi(const VitLaunch &v);
 int run_selftest(hipStream_t stream, unsigned *d_flags);
 int run_microbench(hipStream_t stream, double *d_out);
 int run_pipe_probe(hipStream_t stream, double *d_out, int n_waves, unsigned mask, int rounds);

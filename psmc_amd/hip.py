@@ -28,7 +28,7 @@ EXPORTS = [
     "psmc_hip_last_error", "psmc_hip_set_option", "psmc_hip_load_segments",
     "psmc_hip_load_segments_device", "psmc_hip_select", "psmc_hip_estep",
     "psmc_hip_estep_segments", "psmc_hip_estep_batch", "psmc_hip_estep_batch_cb", "psmc_hip_reserve_batch_tables", "psmc_hip_batch_info", "psmc_hip_estep_device", "psmc_hip_fast_diag", "psmc_hip_fast_repairs", "psmc_hip_fast_info", "psmc_hip_estep_factored",
-    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales", "psmc_hip_post_mean",
+    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales", "psmc_hip_post_mean", "psmc_hip_viterbi",
     "psmc_hip_group_selfcheck", "psmc_hip_fast_plan",
     "psmc_hip_group_create", "psmc_hip_group_destroy", "psmc_hip_group_last_error", "psmc_hip_group_set_option",
     "psmc_hip_group_load_segments", "psmc_hip_group_estep", "psmc_hip_group_estep_factored", "psmc_hip_group_info",
@@ -514,6 +514,23 @@ class HipEStep:
         self.lib.psmc_hip_post_mean.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int32, _dp]
         self._chk(self.lib.psmc_hip_post_mean(self.h, int(seg), _p(w), w.shape[0], _p(mean)), "post_mean")
         return mean
+
+    def viterbi(self, a, e, a0, want_path=True):
+        """(paths, scores): the Viterbi path of every loaded segment in load order (a list of int32 arrays) and hmm_Viterbi's
+        return value per segment (khmm.c:83-141, psmc_hip_viterbi) -- the reference's bits in either mode.  want_path=False:
+        paths is None and no back-pointer table is allocated.  Reads the observations only; HipError (invalid argument, the
+        message names the segment) when a segment has no path of finite probability."""
+        a, e, a0 = self._params(a, e, a0)
+        lens = [int(x) for x in self.lens]
+        path = np.zeros(sum(lens), dtype=np.int32) if want_path else None
+        score = np.zeros(len(lens))
+        self.lib.psmc_hip_viterbi.argtypes = [C.c_void_p, _dp, _dp, _dp, _i32p, _dp]
+        self._chk(self.lib.psmc_hip_viterbi(self.h, _p(a), _p(e), _p(a0), path.ctypes.data_as(_i32p) if want_path else None,
+                                            _p(score)), "viterbi")
+        if not want_path:
+            return None, score
+        ends = np.cumsum(lens)
+        return [path[end - L:end] for end, L in zip(ends, lens)], score
 
     def timing(self):
         ms = np.zeros(7)

@@ -18,6 +18,8 @@ typedef struct {
 	int wide, wide_decode;
 	/* the note about the full-count E-steps on the wide fast path, until the first E-step has run (psmc_hipbe_note_counts) */
 	char *note;
+	/* what hb_error answers after a failed hb_viterbi on a group: the shard context's message (in msg); cleared by the next call */
+	const char *verr;
 } hip_be;
 
 /* the per-segment readers go to the context that holds the segment's tables: the exact twin's after a fallback */
@@ -34,6 +36,7 @@ static int route(hip_be *h, int seg, psmc_hip_ctx **c, int *local)
 static const char *hb_error(void *self)
 {
 	hip_be *h = (hip_be *)self;
+	if (h->verr) return h->verr;
 	if (h->on_twin) return h->x_grp ? psmc_hip_group_last_error(h->x_grp) : psmc_hip_last_error(h->x_ctx);
 	return h->grp ? psmc_hip_group_last_error(h->grp) : psmc_hip_last_error(h->ctx);
 }
@@ -111,7 +114,7 @@ static int hb_estep(void *self, const double *a, const double *e, const double *
 		if (!h->pa || !h->pe || !h->pa0) return PSMC_HIP_ENOMEM;
 		memcpy(h->pa, a, sizeof(double) * n * n); memcpy(h->pe, e, sizeof(double) * 2 * n); memcpy(h->pa0, a0, sizeof(double) * n);
 	}
-	h->on_twin = 0;
+	h->on_twin = 0; h->verr = 0;
 	int rc;
 	if (h->decoding && h->wide_decode) {
 		/* the decoding E-step of the wide fast path: psmc_hip_estep would run the exact full-counts kernels beyond 128 states, and the
@@ -207,6 +210,48 @@ static int hb_post_counts(void *self, int seg, const int32_t *cnt1, int32_t l1, 
 static int hb_scales(void *self, int seg, double *s) { HB_DECODE_CALL(psmc_hip_scales(c, l, s)) }
 static int hb_post_mean(void *self, int seg, const double *w, int32_t n_w, double *mean) { HB_DECODE_CALL(psmc_hip_post_mean(c, l, w, n_w, mean)) }
 #undef HB_DECODE_CALL
+/* The Viterbi path of all segments in input order.  One context: psmc_hip_viterbi as it is.  A group: one call per shard context
+ * (psmc_hip_group_route names every segment's context and its index there), the shard's results scattered to input order.  The call
+ * reads observations only, so it goes to the run's own contexts whatever the exact twin holds. */
+static int hb_viterbi(void *self, const double *a, const double *e, const double *a0, int32_t *path, double *score)
+{
+	hip_be *h = (hip_be *)self;
+	h->verr = 0;
+	if (!h->grp) return psmc_hip_viterbi(h->ctx, a, e, a0, path, score);
+	const int n = h->n_seg;
+	psmc_hip_ctx **cx = (psmc_hip_ctx **)malloc(sizeof(void *) * (size_t)n);
+	int *loc = (int *)malloc(sizeof(int) * (size_t)n), *glob = (int *)malloc(sizeof(int) * (size_t)n);
+	int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+	int32_t *sp = 0; double *ss = 0;
+	int rc = cx && loc && glob && off ? 0 : PSMC_HIP_ENOMEM;
+	if (rc == 0) off[0] = 0;
+	for (int i = 0; rc == 0 && i < n; ++i) {
+		off[i + 1] = off[i] + h->L[i];
+		rc = psmc_hip_group_route(h->grp, i, &cx[i], &loc[i]);
+	}
+	for (int i = 0; rc == 0 && i < n; ++i) {
+		int seen = 0, m = 0;
+		int64_t bins = 0;
+		for (int j = 0; j < i && !seen; ++j) seen = cx[j] == cx[i];
+		if (seen) continue;
+		for (int j = i; j < n; ++j) /* the shard's segments by their index there: 0 .. m-1 */
+			if (cx[j] == cx[i]) { ++m; bins += h->L[j]; }
+		for (int j = i; j < n; ++j)
+			if (cx[j] == cx[i]) { if (loc[j] < 0 || loc[j] >= m) rc = PSMC_HIP_EINVAL; else glob[loc[j]] = j; }
+		if (rc) break;
+		sp = (int32_t *)realloc(sp, sizeof(int32_t) * (size_t)bins); ss = (double *)realloc(ss, sizeof(double) * (size_t)m);
+		if (!sp || !ss) { rc = PSMC_HIP_ENOMEM; break; }
+		rc = psmc_hip_viterbi(cx[i], a, e, a0, path ? sp : 0, score ? ss : 0);
+		if (rc) { snprintf(h->msg, sizeof h->msg, "%s (a shard's index; its first segment is segment %d of the input)", psmc_hip_last_error(cx[i]), glob[0]); h->verr = h->msg; break; }
+		int64_t so = 0;
+		for (int l = 0; l < m; so += h->L[glob[l]], ++l) {
+			if (path) memcpy(path + off[glob[l]], sp + so, sizeof(int32_t) * (size_t)h->L[glob[l]]);
+			if (score) score[glob[l]] = ss[l];
+		}
+	}
+	free(cx); free(loc); free(glob); free(off); free(sp); free(ss);
+	return rc;
+}
 static void hb_destroy(void *self)
 {
 	hip_be *h = (hip_be *)self;
@@ -252,7 +297,7 @@ int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_fa
 	be->self = h; be->load = hb_load; be->estep = hb_estep; be->tables = hb_tables; be->decode = hb_decode;
 	be->estep_factored = use_factored ? hb_estep_factored : 0; be->error = hb_error; be->destroy = hb_destroy;
 	be->posterior = hb_posterior; be->post_counts = hb_post_counts; be->prepare_decode = hb_prepare_decode; be->scales = hb_scales;
-	be->post_mean = hb_post_mean;
+	be->post_mean = hb_post_mean; be->viterbi = hb_viterbi;
 	return 0;
 }
 

@@ -107,10 +107,18 @@ typedef struct psmc_estep_backend {
 	int  (*prepare_decode)(void *self);
 	/* optional (may be NULL): the scaling factors s[L] of one segment (the PR line of -s, aux.c:159-164) without the tables */
 	int  (*scales)(void *self, int seg, double *s);
-	/* optional (may be NULL; last, so that an aggregate initialiser without it says no): per-bin posterior expectations
+	/* optional (may be NULL; an aggregate initialiser without it says no): per-bin posterior expectations
 	 * mean[(u-1)*n_w + j] = sum_k post[u][k] * w[j*n + k] of one segment, n_w <= 4 (psmc_hip_post_mean; the PSMC_TMRCA track) */
 	int  (*post_mean)(void *self, int seg, const double *w, int32_t n_w, double *mean);
+	/* optional (may be NULL; last, so that an aggregate initialiser without it says no): the Viterbi path of ALL loaded segments in
+	 * input order (khmm.c:83-141; psmc_hip_viterbi; the PSMC_VITERBI track): path holds sum of L entries, segment i at offset
+	 * L[0] + .. + L[i-1], 0-based states; score one double per segment (hmm_Viterbi's return value).  Non-zero when a segment has no
+	 * path of finite probability.  A backend without it gets psmc_viterbi_host */
+	int  (*viterbi)(void *self, const double *a, const double *e, const double *a0, int32_t *path, double *score);
 } psmc_estep_backend;
+/* the dense Viterbi recursion on the host, one segment: log tables by libm's log(), every candidate one addition, the first maximum
+ * wins (the arithmetic include/psmc_hip.h pins).  path[L], *score; returns 0, 1 = no path of finite probability, 2 = out of memory */
+int psmc_viterbi_host(int n, const double *a, const double *e, const double *a0, const uint8_t *sym, int32_t L, int32_t *path, double *score);
 
 /* ---- run state + driver (main.c, em.c, aux.c) */
 typedef struct {
