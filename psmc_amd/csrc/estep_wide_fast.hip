@@ -8,8 +8,9 @@
 // totals of the scans, the sums behind the scale factors, I of a tile, the mismatch of a boundary, the logarithms of k_wf_ll --
 // goes through the exchange of wide_prims.h (Xchg) in a fixed order, and at W = 1 that exchange does nothing: no LDS, no barrier.
 // The five structure vectors and the two emission rows stay in registers.  Padded states have zero matrix entries and zero
-// emissions, so they stay zero.  The hang rule of wide_prims.h holds in every kernel here; the comments "(the same in every wave)"
-// mark the branches it bears on.
+// emissions, so they stay zero -- but for the emission of a missing bin, which emis() (wide_prims.h) answers with 1 on every lane: the
+// one start vector made of an emission alone, k_wf_bwarm's bt_q = e[o_q], is zeroed on the states n .. where it is stored.  The hang rule of
+// wide_prims.h holds in every kernel here; the comments "(the same in every wave)" mark the branches it bears on.
 //
 // One work-group per tile and direction:
 //   k_wf_fwd    speculative forward sweep (warm-up from a0, the stationary vector, `wf` bins before the tile; a segment's first tile
@@ -204,6 +205,15 @@ __global__ __launch_bounds__(64 * W) void k_wf_bwarm(const double *__restrict__ 
 			if (j == 3) bstep<NPL, W, true>(sc, wm, sym, e0, e1, x, xc); else bstep<NPL, W, false>(sc, wm, sym, e0, e1, x, xc);
 		}
 	}
+	// The start vector leaves with zeros on the padded states n ..: a missing bin's emission is 1 on every lane (emis), and where no step
+	// follows the seed (q = top + 1: a segment's last tile) it would go out as it stands, into the first scaling of every sweep that starts
+	// from bentry and into V's padded columns.  A step clears the padded states, so behind one this changes nothing -- which is why the
+	// zeros are put here and not at the seed: there they would change the factor of a warm-up's first scaled step when bin q is missing,
+	// a factor that any positive number can be, and with it the last bits of every speculated start vector at the sizes with padded states.
+	// A padded state is one whose row of the matrix is zero -- P, R and dd, which the loop above holds in registers (a state of an HMM has
+	// a row that sums to 1) -- so the kernel needs neither n nor another register.
+#pragma unroll
+	for (int i = 0; i < NPL; ++i) x[i] = sc.wP[i] != 0.0 || sc.wS[i] != 0.0 || sc.dd[i] != 0.0 ? x[i] : 0.0;
 	st<NPL>(bentry + (int64_t)b * S + k0, x);
 }
 

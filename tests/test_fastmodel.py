@@ -158,13 +158,86 @@ def test_factorisation_criterion_on_the_extreme_models():
                 x = np.linspace(0.1, 1.0, n) ** 3
                 assert relmax(fastmodel.struct_step_forward(f, x), a.T @ x) < 1e-13
                 assert relmax(fastmodel.struct_step_backward(f, x), a @ x) < 1e-13
-            elif "corner" in edges.REFUSED[name]:
-                assert a[0, n - 1] == 0.0 and not a[n - 1, 0] > 1e-280, (name, n)
-            else:   # the off-diagonal entries do factor; the remainder of the diagonal is negative
-                assert fastmodel.factor_structure(a, ulps=1e30) is None and a.min() < 0, (name, n)
-                P, qa, R, c = a[:, 0].copy(), a[n - 1] / a[n - 1, 0], a[:, n - 1].copy(), a[0] / a[0, n - 1]
-                P[0] = R[n - 1] = 0.0; qa[n - 1] = c[0] = 0.0
-                assert (np.diag(a) - P * qa - R * c).min() < 0, (name, n)
+            else:
+                _refused_for_the_listed_reason(edges, name, a)
+
+
+def _refused_for_the_listed_reason(edges, name, a):
+    """a, which the criterion refuses, is refused for the reason edges.REFUSED[name] gives"""
+    n = a.shape[0]
+    assert fastmodel.factor_structure(a) is None, (name, n)
+    if "corner" in edges.REFUSED[name]:
+        assert a[0, n - 1] == 0.0 and not a[n - 1, 0] > 1e-280, (name, n)
+    else:   # the off-diagonal entries do factor; the remainder of the diagonal is negative
+        assert fastmodel.factor_structure(a, ulps=1e30) is None and a.min() < 0, (name, n)
+        P, qa, R, c = a[:, 0].copy(), a[n - 1] / a[n - 1, 0], a[:, n - 1].copy(), a[0] / a[0, n - 1]
+        P[0] = R[n - 1] = 0.0; qa[n - 1] = c[0] = 0.0
+        assert (np.diag(a) - P * qa - R * c).min() < 0, (name, n)
+
+
+# ---------------------------------------------------------------------------------------------
+# The CPU side of tests/test_gpu_wide_cells.py (the wide fast path at 129 .. 1024 states, cell by cell in the anchored regime).
+def test_wide_cells_case_table():
+    """The literal table of the GPU file against the host model and the criterion, at all ten sizes and all thirteen models: a pair is either an
+    HMM (a, e, a0 finite, a >= 0) that factor_structure accepts, or it is in REFUSED -- no HMM, refused, and refused for the reason
+    tests/test_gpu_wide_fast_edges.py lists.  The four models of the sizes beyond 256 states are accepted everywhere."""
+    import test_gpu_wide_cells as wc
+    import test_gpu_wide_fast_edges as edges
+    assert wc.MODELS is edges.MODELS and len(wc.MODELS) == 13 and set(wc.REFUSED) == set(edges.REFUSED)
+    assert wc.SIZES == (129, 192, 193, 256, 257, 512, 513, 768, 769, 1024)
+    assert len(wc.CASES) == 4 * 13 + 6 * 4 and not set(wc.LARGE_MODELS) & set(wc.REFUSED)
+    assert all(name in wc.LARGE_MODELS for n, name in wc.CASES if n > 256)
+    for n in wc.SIZES:
+        for name in wc.MODELS:
+            a, e, a0 = wc.host_model(name, n)
+            assert a.shape == (n, n) and e.shape == (3, n) and a0.shape == (n,)
+            refused = n in wc.REFUSED.get(name, ())
+            assert wc.is_hmm((a, e, a0)) == (not refused), (n, name)
+            assert (fastmodel.factor_structure(a) is None) == refused, (n, name)
+            if refused:
+                _refused_for_the_listed_reason(edges, name, a)
+
+
+@pytest.mark.parametrize("n", [129, 257, 1024])
+def test_wide_cells_criterion_refuses_what_it_must(n):
+    """Around the accepted models of the large sizes: one off-diagonal entry off by 1e-13 relative (450 ulp: beyond the 64 the criterion admits),
+    a capped matrix (aux.c:115-127), a corner at zero and a diagonal entry below P.qa + R.c are all refused; 32 ulp on one entry is not."""
+    import test_gpu_wide_cells as wc
+    for name in wc.LARGE_MODELS:
+        a = wc.host_model(name, n)[0]
+        assert fastmodel.factor_structure(a) is not None
+        k, l = 4 + int(np.argmax(a[4:n - 1, 3])), 3   # an entry inside the lower triangle, off the rows and columns the factors are read from
+        assert a[k, l] > 1e-200
+        b = a.copy(); b[k, l] *= 1.0 + 1e-13
+        assert fastmodel.factor_structure(b) is None, (name, n)
+        b = a.copy(); b[k, l] *= 1.0 + 32 * 2.0 ** -52
+        assert fastmodel.factor_structure(b) is not None, (name, n)
+        b = a.copy(); b[:, 40] = b[:, 40:].sum(1); b[:, 41:] = 0.0
+        assert fastmodel.factor_structure(b) is None, (name, n)
+        b = a.copy(); b[0, n - 1] = 0.0
+        assert fastmodel.factor_structure(b) is None, (name, n)
+        b = a.copy(); b[n // 2, n // 2] = 0.0
+        assert fastmodel.factor_structure(b) is None, (name, n)
+
+
+@pytest.mark.parametrize("n", [129, 256, 257, 1024])
+def test_wide_cells_reference_error(golden, oracle, n):
+    """A condition on the inputs of tests/test_gpu_wide_cells.py, not a measurement of the device: for the four models of the large sizes on the
+    small input (1127 bins) the oracle's A, E and LL are finite and non-negative, and E_ref -- the untiled numpy model, dense and structured,
+    against the oracle over EVERY cell above 2^-900 -- is at most 1e-12, over the five triangular sums as well.  Observed: <= 2.1e-13 (1024
+    states), so B = 32 max(E_ref, 64 ulp) stays below 7e-12."""
+    import test_gpu_wide_cells as wc
+    segs = wc.small_segs(golden)
+    assert sum(len(s) for s in segs) == 1127
+    for name in wc.LARGE_MODELS:
+        a, e, a0 = wc.host_model(name, n)
+        o = oracle.estep(a, e, a0, segs)
+        assert np.isfinite(o["A"]).all() and np.isfinite(o["E"]).all() and np.isfinite(o["LL"]) and (o["A"] >= 0).all() and (o["E"] >= 0).all()
+        r = fastmodel.reference_error(a, e, a0, segs, o)
+        print("E_ref n %4d %-26s cell %.2e (dense %.2e struct %.2e) sums %.2e LL %.1e; B %.2e; cells above 2^-900: %d of %d" % (
+            n, name, r["cell"], r["dense"][0], r["struct"][0], r["tri"], r["LL"], fastmodel.cell_bound(r["cell"]),
+            int((o["A"] > fastmodel.CELL_FLOOR).sum()), n * n))
+        assert r["cell"] <= 1e-12 and r["tri"] <= 1e-12 and r["LL"] <= 1e-14, (n, name, r)
 
 
 def test_untiled_matches_oracle_per_cell_at_200_states(golden, oracle):
