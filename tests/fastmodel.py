@@ -251,3 +251,165 @@ def reference_error(a, e, a0, segs, o):
 def cell_bound(e_ref, margin=32):
     """B of the per-cell gates: margin x max(E_ref, 64 ulp)"""
     return margin * max(e_ref, ULP64)
+
+
+# ---------------------------------------------------------------------------------------------
+# Decoding from the fast tables (psmc_amd/csrc/estep_post_fast.hip, estep_wide_post.hip): the formulas of that file's header, untiled, and the
+# reference figure of the per-entry gates of tests/test_gpu_decode_cells.py.
+DECODE_OUTPUTS = ("post", "maxp", "recomb", "scales", "counts", "mean")
+N_CNT = (1, 5, 9)          # count columns of the post_counts calls: nine cross both PCNT_J = 8 and CB = 4
+
+
+def decode_model(a, e, a0, seg, struct=False):
+    """Every decoding output of one segment from the tables of an untiled fast E-step (one tile, nothing speculated; the conventions of
+    estep_fast_model: lag-4 normalisation of both sweeps, position L on its own formula).  dict(
+      post   (L, n)  gamma_p = X_p bt_p / e[o_p] / G_p for p < L, gamma_L = X_L / sum X_L,
+      recomb (L,)    1 - sb_p sum_l X_p(l) a_ll bt_{p+1}(l) / G_p, 0 at p = L,
+      path, maxp     the first maximum of every row and its value,
+      scales (L,)    s_1 = sum a0 e[o_1], s_p = sum X_p / sum X_{p-1} * d_p).
+    struct=True: the products of both sweeps through the two-scan steps of factor_structure(a); None where the criterion refuses a."""
+    n = a.shape[0]
+    f = factor_structure(a) if struct else None
+    if struct and f is None:
+        return None
+    fwd = (lambda x: x @ a) if f is None else (lambda x: struct_step_forward(f, x))
+    bwd = (lambda z: a @ z) if f is None else (lambda z: struct_step_backward(f, z))
+    seg = np.asarray(seg, dtype=np.int64)
+    L = len(seg)
+    o = np.concatenate([[2], seg, [2]])  # o[p], p=1..L
+    X = np.zeros((L + 2, n)); d = np.ones(L + 2); bt = np.zeros((L + 2, n)); sb = np.ones(L + 2)
+    x = a0
+    for p in range(1, L + 1):
+        dp = x.sum() if p % NORM_EVERY == 0 else 1.0
+        x = ((x * e[o[p]]) if p == 1 else e[o[p]] * fwd(x)) / dp
+        X[p] = x; d[p] = dp
+    bt[L] = e[o[L]] * np.ones(n)
+    for p in range(L - 1, 0, -1):
+        sb[p] = 1.0 / bt[p + 1].sum() if p % NORM_EVERY == 0 else 1.0
+        bt[p] = e[o[p]] * bwd(bt[p + 1]) * sb[p]
+    post = np.zeros((L, n)); recomb = np.zeros(L); scales = np.zeros(L)
+    if L > 1:
+        re = np.where(e > 0, 1.0 / np.where(e > 0, e, 1.0), 0.0)
+        g = X[1:L] * bt[1:L] * re[seg[:L - 1]]
+        G = g.sum(1)
+        post[:L - 1] = g / G[:, None]
+        recomb[:L - 1] = 1.0 - sb[1:L] * (X[1:L] * np.diag(a) * bt[2:L + 1]).sum(1) / G
+    post[L - 1] = X[L] / X[L].sum()
+    sx = X[1:L + 1].sum(1)
+    scales[0] = (a0 * e[o[1]]).sum()
+    scales[1:] = sx[1:] / sx[:-1] * d[2:L + 1]
+    return dict(post=post, recomb=recomb, path=post.argmax(1).astype(np.int32), maxp=post.max(1), scales=scales)
+
+
+def decode_weights(n, t_max, alpha=0.1):
+    """(4, n) non-negative post_mean weights: the host model's t_k = alpha (exp(k / n ln(1 + t_max / alpha)) - 1) (the interval boundaries of
+    lh3/psmc core.c:70-72), t_k^2, the indicator k >= n // 2, all ones"""
+    k = np.arange(n, dtype=np.float64)
+    t = alpha * (np.exp(k / n * np.log(1.0 + t_max / alpha)) - 1.0)
+    return np.ascontiguousarray(np.stack([t, t * t, (np.arange(n) >= n // 2).astype(np.float64), np.ones(n)]))
+
+
+def count_lengths(segs):
+    """l of every segment's count record: L, except
+      segment 1: L - 3 and segment 2: L + 5 (as compare_decoding of tests/test_gpu_fast_decode.py has them; on segments of 2 and 3 bins: an
+                 empty record, for which the call returns before any launch, and one longer than a single tile),
+      segment 7: L - 3 and segment 8: L + 5 (the 129-bin segment and the 1000- or 300-bin one: records shorter and longer than a segment of
+                 several tiles; 126 ends inside a tile at chunk 37, 64 and 256 and inside a block of eight rows, and with chunk 64 the last tile,
+                 which holds position L alone, counts nothing),
+      the last segment: L // 2 + 1 (151 of 300: mid-tile and mid-block again, and every later tile counts nothing),
+      a segment of more than 2048 bins: 2051 (three positions into the second block of PCNT_BLK = 2048)."""
+    out = []
+    for i, s in enumerate(segs):
+        L = len(s)
+        l = L - 3 if i in (1, 7) else L + 5 if i in (2, 8) else L // 2 + 1 if i == len(segs) - 1 and i > 8 else 2051 if L > 2048 else L
+        out.append(max(0, l))
+    return out
+
+
+def count_tables(segs, seed=1):
+    """{n_cnt: [cnt1 of every segment]} for n_cnt of N_CNT: rng.integers(0, 50), (l, n_cnt) int32 with l of count_lengths(segs)"""
+    rng = np.random.default_rng(seed)
+    return {j: [rng.integers(0, 50, size=(l, j), dtype=np.int32) for l in count_lengths(segs)] for j in N_CNT}
+
+
+def add_counts(cnt, post, cnt1):
+    """cnt (n, n_cnt) += sum over the first min(L, l) positions of post_p (x) cnt1_p (aux.c:202-219)"""
+    m = min(len(post), len(cnt1))
+    cnt += post[:m].T @ cnt1[:m].astype(np.float64)
+    return cnt
+
+
+def long_mean(post, w):
+    """(L, n_w): post @ w^T in numpy.longdouble, rounded to double once"""
+    return (post.astype(np.longdouble) @ np.asarray(w).astype(np.longdouble).T).astype(np.float64)
+
+
+def top_two_gap(post):
+    """per row of post: (largest - second largest) / largest; 1 for a single state"""
+    if post.shape[1] < 2:
+        return np.ones(len(post))
+    top = np.partition(post, post.shape[1] - 2, axis=1)[:, -2:]
+    return (top[:, 1] - top[:, 0]) / top[:, 1]
+
+
+def decode_oracle(a, e, a0, segs, oracle, w, tables):
+    """The oracle's decoding outputs of every segment: dict(post, recomb, path, maxp, scales, mean: lists per segment; counts: {n_cnt: (n,
+    n_cnt)} running totals over all segments of `tables` (count_tables), counts_seg: {n_cnt: [(n, n_cnt) of every segment alone]}; gap: the smallest relative top-two gap of any posterior row)"""
+    n = a.shape[0]
+    out = dict(post=[], recomb=[], path=[], maxp=[], scales=[], mean=[], counts={j: np.zeros((n, j)) for j in tables},
+               counts_seg={j: [] for j in tables}, gap=1.0)
+    for i, seg in enumerate(segs):
+        f, b, s, lk, chk = oracle.fwd_bwd(a, e, a0, seg)
+        post, rec = oracle.post_full(a, e, seg, f, b, s)
+        path, mp = oracle.post_decode(f, b, s)
+        out["post"].append(post[1:].copy()); out["recomb"].append(rec[1:].copy()); out["path"].append(path[1:].copy())
+        out["maxp"].append(mp[1:].copy()); out["scales"].append(s[1:].copy()); out["mean"].append(long_mean(post[1:], w))
+        for j in tables:
+            oracle.post_counts(f, b, s, tables[j][i], out["counts"][j])
+            out["counts_seg"][j].append(oracle.post_counts(f, b, s, tables[j][i], np.zeros((n, j))))
+        out["gap"] = min(out["gap"], float(top_two_gap(post[1:]).min()))
+    return out
+
+
+def decode_reference_error(a, e, a0, segs, oracle, w=None, ref=None):
+    """E_ref of the decoding outputs, the counterpart of reference_error: decode_model with the dense and with the structured products
+    (skipped where factor_structure refuses a), each against the oracle; of the two the larger of
+      post    worst relative error over the entries whose oracle value is above CELL_FLOOR,
+      maxp, scales  relative,
+      recomb  ABSOLUTE (it is 1 - x with x near 1: its error is that of x),
+      counts  relative over the cells of orc.post_counts above CELL_FLOOR, for count_tables(segs): of every segment alone and of the running
+              totals over all segments,
+      mean    relative, per column, against post_oracle @ w in numpy.longdouble (w: decode_weights(n, 15) unless given),
+    and: ties = positions where a model's path differs from the oracle's, gap = the smallest relative top-two gap of the oracle's posterior,
+    rowsum = the largest |sum of a model row - 1|, below = the largest model entry where the oracle is at or below CELL_FLOOR.
+    ref: decode_oracle's result when the caller has it already."""
+    n = a.shape[0]
+    w = decode_weights(n, 15.0) if w is None else w
+    tables = count_tables(segs)
+    ref = decode_oracle(a, e, a0, segs, oracle, w, tables) if ref is None else ref
+    out = dict(ties=0, gap=ref["gap"], rowsum=0.0, below=0.0)
+    for key, st in (("dense", False), ("struct", True)):
+        if st and factor_structure(a) is None:
+            continue
+        err = dict.fromkeys(DECODE_OUTPUTS, 0.0)
+        cnt = {j: np.zeros((n, j)) for j in tables}
+        for i, seg in enumerate(segs):
+            m = decode_model(a, e, a0, seg, struct=st)
+            err["post"] = max(err["post"], cell_error(m["post"], ref["post"][i])[0])
+            err["maxp"] = max(err["maxp"], cell_error(m["maxp"], ref["maxp"][i])[0])
+            err["scales"] = max(err["scales"], cell_error(m["scales"], ref["scales"][i])[0])
+            err["recomb"] = max(err["recomb"], float(np.abs(m["recomb"] - ref["recomb"][i]).max()))
+            err["mean"] = max(err["mean"], cell_error(m["post"] @ w.T, ref["mean"][i])[0])
+            out["ties"] += int((m["path"] != ref["path"][i]).sum())
+            out["rowsum"] = max(out["rowsum"], float(np.abs(m["post"].sum(1) - 1.0).max()))
+            small = ref["post"][i] <= CELL_FLOOR
+            if small.any():
+                out["below"] = max(out["below"], float(m["post"][small].max()))
+            for j in tables:
+                add_counts(cnt[j], m["post"], tables[j][i])
+                err["counts"] = max(err["counts"], cell_error(add_counts(np.zeros((n, j)), m["post"], tables[j][i]), ref["counts_seg"][j][i])[0])
+        err["counts"] = max([err["counts"]] + [cell_error(cnt[j], ref["counts"][j])[0] for j in tables])
+        out[key] = err
+    for k in DECODE_OUTPUTS:
+        out[k] = max(out[key][k] for key in ("dense", "struct") if key in out)
+    return out

@@ -240,6 +240,183 @@ def test_wide_cells_reference_error(golden, oracle, n):
         assert r["cell"] <= 1e-12 and r["tri"] <= 1e-12 and r["LL"] <= 1e-14, (n, name, r)
 
 
+# ---------------------------------------------------------------------------------------------
+# The CPU side of tests/test_gpu_decode_cells.py (decoding from the fast tables, entry by entry in the anchored regime).
+def test_decode_cells_case_table():
+    """The case tables of the GPU file are those of the two cell files: every pair it runs is an HMM (NOT_HMM / REFUSED list the others, and
+    none of those is run), the pairs that run the dense sweeps are STRUCT_REFUSED -- which the numpy criterion refuses, and no other -- and the
+    paths of a size are the ones its kernels have."""
+    import test_gpu_decode_cells as dc
+    import test_gpu_fast_cells as cells
+    import test_gpu_wide_cells as wc
+    small = [c for c in dc.CASES if c[0] <= 128]
+    wide = [c for c in dc.CASES if c[0] > 128]
+    assert small == cells.CASES and len(small) == 70 and len(wide) == 10 * 4 + 4 * 6 and len(set(dc.CASES)) == len(dc.CASES)
+    assert {n for n, _ in small} == set(cells.SIZES) and {n for n, _ in wide} == set(wc.SIZES)
+    assert not any(n in cells.NOT_HMM.get(name, ()) for n, name in small) and not any(n in wc.REFUSED.get(name, ()) for n, name in wide)
+    assert set(wide) == {(n, name) for n, name in wc.CASES if n not in wc.REFUSED.get(name, ())}
+    assert {name for n, name in wide if n > 256} == set(wc.LARGE_MODELS)
+    for n, name in dc.CASES:
+        par = dc.host_model(name, n)
+        assert cells.is_hmm(par) and par[0].shape == (n, n), (n, name)
+        refused = fastmodel.factor_structure(par[0]) is None
+        assert refused == ((n, name) in cells.STRUCT_REFUSED), (n, name)
+        tags = [p[0] for p in dc.paths(n, refused)]
+        assert tags == (["D1", "D2"] if n <= 64 else ["D1"] if n <= 128 else ["D3", "D4"]), (n, tags)
+        assert [p[4] for p in dc.paths(n, refused)] == ([not refused, False] if n <= 64 else [True] * len(tags)), (n, name)
+    assert dc.D0_CASES <= set(dc.CASES) and len(dc.D0_CASES) == 8
+    assert all(-n % 64 for n in dc.D0_SIZES)           # sizes that leave padded states
+
+
+def _decode_cpu_cases(n):
+    import test_gpu_decode_cells as dc
+    return [name for m, name in dc.CASES if m == n]
+
+
+@pytest.mark.parametrize("n", [3, 65, 129])
+def test_decode_model_reference_error(golden, oracle, n):
+    """decode_model, dense and structured, against the oracle on small_segs (1127 bins) over every HMM model of the size: a condition on the
+    formulas and on the inputs of tests/test_gpu_decode_cells.py, not a measurement of the device.  Every E_ref below 1e-12 (so every B of the
+    GPU file stays below 3.2e-11), rows sum to 1 within 1e-13, the model's path is the oracle's at every position, nothing the oracle puts at or
+    below 2^-900 is above 2^-899 in the model.  Observed: post <= 1.3e-13, maxp <= 7.6e-14, recomb <= 1.6e-14 absolute, scales <= 1.4e-14,
+    counts <= 7.9e-14, mean <= 3.0e-14; the smallest relative top-two gap 1.5e-7 (129 states, rho0 = 0.1).  On the longer input of the GPU file
+    up to 256 states (cells_segs, 4827 bins) and at the sizes beyond, every E_ref stays below 7.2e-13 (post, rho0 = 1e-6 at 256 states)."""
+    import test_gpu_decode_cells as dc
+    import test_gpu_wide_cells as wc
+    segs = wc.small_segs(golden)
+    names = _decode_cpu_cases(n)
+    assert len(names) == 10
+    for name in names:
+        a, e, a0 = dc.host_model(name, n)
+        w = fastmodel.decode_weights(n, dc.MODELS[name](4)[2])
+        assert w.shape == (4, n) and (w >= 0).all() and (w[3] == 1).all() and w[2].sum() == n - n // 2 and w[0, 0] == 0 and (np.diff(w[0]) > 0).all()
+        r = fastmodel.decode_reference_error(a, e, a0, segs, oracle, w=w)
+        print("E_ref n %3d %-26s %s ties %d gap %.1e rowsum %.1e" % (
+            n, name, " ".join("%s %.1e" % (k, r[k]) for k in fastmodel.DECODE_OUTPUTS), r["ties"], r["gap"], r["rowsum"]))
+        assert ("struct" in r) == ((n, name) not in dc.cells.STRUCT_REFUSED)
+        assert all(r[k] < 1e-12 for k in fastmodel.DECODE_OUTPUTS), (n, name, r)
+        assert r["rowsum"] <= 1e-13 and r["ties"] == 0 and r["below"] <= 2.0 ** -899, (n, name, r)
+        assert r["gap"] > 2 * fastmodel.cell_bound(r["post"]), (n, name, r)   # no position of the case is excused from the path gate
+
+
+class _ModelContext:
+    """The decoding calls of HipEStep answered by decode_model: what decode_all of the GPU file is driven with on the CPU.  wrong: {output: a
+    function that spoils it in place}."""
+
+    def __init__(self, par, segs, wrong=None):
+        self.n, self.wrong = par[0].shape[0], wrong or {}
+        self.m = [fastmodel.decode_model(par[0], par[1], par[2], s) for s in segs]
+
+    def _out(self, k, s, x):
+        x = x.copy()
+        if k in self.wrong:
+            self.wrong[k](s, x)
+        return x
+
+    def posterior(self, s, want_post=True, want_recomb=True):
+        return (self._out("post", s, self.m[s]["post"]) if want_post else None, self._out("recomb", s, self.m[s]["recomb"]) if want_recomb else None)
+
+    def decode(self, s):
+        return self._out("path", s, self.m[s]["path"]), self._out("maxp", s, self.m[s]["maxp"])
+
+    def scales(self, s):
+        return self._out("scales", s, self.m[s]["scales"])
+
+    def post_counts(self, s, cnt1, cnt):
+        add = fastmodel.add_counts(np.zeros_like(cnt), self.m[s]["post"], cnt1)
+        cnt += self._out("counts", s, add)
+        return cnt
+
+    def post_mean(self, s, w):
+        return self._out("mean", s, self.m[s]["post"] @ np.atleast_2d(w).T)
+
+
+def test_decode_cells_gates_refuse_what_the_old_tolerances_accept(golden, oracle):
+    """Errors injected into the outputs, not into a kernel: decode_all of tests/test_gpu_decode_cells.py, driven by the numpy model, passes every
+    gate as it is, and names the gate when one small posterior entry is off by 1e-9 relative (1e-9 absolute accepts anything there), when a
+    row, maxp, recomb, a scale, one segment's counts or a mean is off by 1e-10, when recomb at position L is not exactly 0, when the all-ones mean is
+    not 1, and when the path leaves the oracle's at one position."""
+    import test_gpu_decode_cells as dc
+    n, name = 3, "rho_1e-6"
+    segs = dc.data(golden, n)
+    R = dc.reference(oracle, golden, n, name)
+    assert max(R["B"].values()) < 1e-11 and all(c.all() for c in R["clear"])
+    out, bad = dc.Outputs(), []
+    assert dc.decode_all(_ModelContext(R["par"], segs), segs, R, out, bad, "model") == 0 and bad == [], bad[:3]
+    assert all(out.err[k][0] <= R["eref"][k] for k in dc.OUTPUTS)
+
+    def small_entry(s, x):
+        if s == 9:
+            k = int(np.argmin(x[1500]))
+            assert x[1500, k] < 0.5
+            x[1500, k] *= 1.0 + 1e-9
+
+    def at(seg, i, f):
+        def spoil(s, x):
+            if s == seg:
+                x[i] = f(x[i])
+        return spoil
+
+    cases = [("post", small_entry, "(P1) post"),
+             ("post", at(7, 5, lambda r: r * (1.0 + 1e-10)), "(P1) a row sums"),
+             ("maxp", at(8, 17, lambda v: v * (1.0 + 1e-10)), "(P2) maxp"),
+             ("recomb", at(8, 400, lambda v: v + 1e-10), "(P3) recomb:"),
+             ("recomb", at(3, -1, lambda v: 2.0 ** -1000), "(P3) recomb at position L"),
+             ("scales", at(9, 2048, lambda v: v * (1.0 + 1e-10)), "(P4) scales"),
+             ("path", at(12, 150, lambda v: (v + 1) % 3), "(P5) path"),
+             ("counts", at(9, slice(None), lambda v: v * (1.0 + 1e-10)), "(P6) post_counts, 9 columns, running totals"),
+             ("counts", at(0, slice(None), lambda v: v * (1.0 + 1e-10)), "segment 0 (P6) post_counts"),      # one bin of 4827: no total sees it
+             ("counts", at(1, (0, 0), lambda v: 1e-300), "segment 1 (P6) post_counts, 1 columns: a cell the oracle leaves at 0"),
+             ("mean", at(4, (10, 0), lambda v: v * (1.0 + 1e-10)), "(P6) post_mean")]
+    for k, spoil, gate in cases:
+        bad = []
+        dc.decode_all(_ModelContext(R["par"], segs, {k: spoil}), segs, R, dc.Outputs(), bad, "spoiled")
+        assert any(gate in b for b in bad), (k, gate, bad[:3])
+    bad = []
+    ones = lambda s, x: x.__setitem__((slice(None), 3), 1.0 + 1e-10) if x.shape[1] == 4 else None
+    dc.decode_all(_ModelContext(R["par"], segs, dict(mean=ones)), segs, R, dc.Outputs(), bad, "spoiled")
+    assert any("all-ones column" in b for b in bad) and any("(P7) post_mean" in b for b in bad), bad[:3]
+
+
+def test_decode_model_pieces(golden, oracle):
+    """decode_model's conventions on one segment: position L on its own formula, recomb 0 there, the scales are the oracle's s, the first
+    maximum wins a tie; count_tables has records shorter and longer than their segments; and the gates' yardstick sees one entry of 1e-200
+    that is off by 1e-9 relative -- which 1e-9 absolute does not."""
+    p = golden.params("n64_curve")
+    seg = golden.segs_small[7]
+    m = fastmodel.decode_model(p["a"], p["e"], p["a0"], seg)
+    ms = fastmodel.decode_model(p["a"], p["e"], p["a0"], seg, struct=True)
+    f, b, s, lk, chk = oracle.fwd_bwd(p["a"], p["e"], p["a0"], seg)
+    post, rec = oracle.post_full(p["a"], p["e"], seg, f, b, s)
+    for x in (m, ms):
+        assert x["post"].shape == (len(seg), 64) and x["recomb"][-1] == 0.0 and np.array_equal(x["path"], x["post"].argmax(1))
+        assert fastmodel.cell_error(x["post"], post[1:])[0] < 1e-12 and fastmodel.cell_error(x["scales"], s[1:])[0] < 1e-13
+        assert np.abs(x["recomb"] - rec[1:]).max() < 1e-13 and fastmodel.cell_error(x["post"][-1], f[-1] / f[-1].sum())[0] < 1e-13
+    assert not np.array_equal(m["post"], ms["post"])
+    capped = p["a"].copy(); capped[:, 40] = capped[:, 40:].sum(1); capped[:, 41:] = 0.0
+    assert fastmodel.decode_model(capped, p["e"], p["a0"], seg, struct=True) is None
+    one = fastmodel.decode_model(p["a"], p["e"], p["a0"], seg[:1])
+    assert one["post"].shape == (1, 64) and one["recomb"][0] == 0.0 and one["scales"][0] == (p["a0"] * p["e"][seg[0]]).sum()
+    segs = golden.segs_small[:4]
+    t = fastmodel.count_tables(segs)
+    assert sorted(t) == [1, 5, 9] and [len(x) for x in t[9]] == [1, 0, 8, 63] and all(x.dtype == np.int32 and x.shape[1] == 9 for x in t[9])
+    import test_gpu_fast_cells as cells
+    import test_gpu_wide_cells as wc
+    # the records of the GPU file's two inputs: shorter and longer than a segment of several tiles, ending inside a tile and a block of eight rows
+    assert fastmodel.count_lengths(cells.cells_segs(golden)) == [1, 0, 8, 63, 64, 65, 127, 126, 1005, 2051, 3, 70, 151]
+    assert fastmodel.count_lengths(wc.small_segs(golden)) == [1, 0, 8, 63, 64, 65, 127, 126, 305, 3, 70, 151]
+    assert all(l % T > 1 and l % 8 > 1 for l in (126, 151) for T in (37, 64, 256))   # neither the last nor the first row of a tile or block
+    assert 2051 - 2048 == 3 and 129 % 64 == 1                      # into the second block of PCNT_BLK; position L alone in a tile at chunk 64
+    assert all(np.array_equal(x, y) for x, y in zip(t[5], fastmodel.count_tables(segs)[5]))
+    cnt = fastmodel.add_counts(np.zeros((64, 9)), m["post"][:3], t[9][2])      # a record longer than its segment: the first L rows count
+    assert np.allclose(cnt, m["post"][:3].T @ t[9][2][:3].astype(float), rtol=1e-15, atol=0)
+    assert fastmodel.top_two_gap(np.array([[0.5, 0.25, 0.25], [0.25, 0.5, 0.25 + 2.0 ** -30]])).tolist() == [0.5, 0.5 - 2.0 ** -29]
+    x = np.array([[1.0 - 1e-200, 1e-200]])
+    y = x * np.array([[1.0, 1.0 + 1e-9]])
+    assert np.abs(y - x).max() < 1e-9 and fastmodel.cell_error(y, x) == (pytest.approx(1e-9, rel=1e-6), (0, 1))
+    assert fastmodel.long_mean(np.array([[0.25, 0.75]]), np.array([[1.0, 1.0], [0.0, 2.0]])).tolist() == [[1.0, 1.5]]
+
+
 def test_untiled_matches_oracle_per_cell_at_200_states(golden, oracle):
     """Before the per-vector gates of the wide fast path (tests/test_gpu_wide_fast.py gate_factored, FAST_TOL_CELL = 1e-9) are
     relied on: the algorithm itself -- this file's numpy model, untiled, in double -- agrees with the oracle on every gated cell
