@@ -273,7 +273,12 @@ const char *psmc_hip_last_error(const psmc_hip_ctx *ctx);
  *                           120 tiles; at 200 states (256 padded) they are 0.8 MB and it holds about 2500
  *  "vit_tile"      2048     bins per backtrace tile of psmc_hip_viterbi: 16 .. 16777216, anything else: PSMC_HIP_EINVAL.  Paths and scores do
  *                           not depend on it: it sets how long the longest chain of dependent loads is (one tile) and how many maps of
- *                           2 x (padded states) bytes there are (profiles/viterbi.txt)
+ *                           2 x (padded states) bytes there are (profiles/viterbi.txt).  psmc_hip_sample_paths tiles its backtraces by it
+ *                           as well; the samples do not depend on it either
+ *  "samp_group"    0        samples per sweep of psmc_hip_sample_paths: one map table per sample of the group is held on the device, and
+ *                           one forward sweep serves the whole group.  0 (auto): as many as the free device memory holds, at most 8;
+ *                           1 .. 64: that many (fewer when n_samp is smaller or the memory does not hold them); anything else:
+ *                           PSMC_HIP_EINVAL.  The samples do not depend on it
  *  "two_phase"     auto     2: the fused back half runs as two launches, odd tiles of the second list start from the exit
  *                           vector of the tile above instead of speculating backward; 0: every tile speculates, one
  *                           launch when the tiles fit one round.  auto: 2 with two rounds, 0 with one
@@ -574,6 +579,35 @@ int psmc_hip_post_mean(psmc_hip_ctx *ctx, int seg, const double *w, int32_t n_w,
  * unspecified, the context stays usable).  PSMC_HIP_ENOMEM: the message holds the table's size. */
 int psmc_hip_viterbi(psmc_hip_ctx *ctx, const double *a, const double *e, const double *a0,
                      int32_t *path, double *score);
+
+/* State paths drawn from the posterior P(path | data, parameters) of every loaded segment, in load order (forward filtering, backward
+ * sampling); psmc_hip_select is not read.  path: n_samp * sum of L entries, sample j (0-based), segment i at offset
+ * j * (sum of L) + L[0]+..+L[i-1], 0-based states, bins numbered as psmc_hip_decode numbers them.  stream: n_seg ids, one per segment,
+ * or NULL: the load index (a caller that holds a shard of a larger input passes the segments' global indices).
+ * The result is pinned bit for bit and depends on (a, e, a0, the observations, seed, j, the segment's stream id q) alone -- not on the
+ * device, the mode, "vit_tile", "samp_group", n_samp or anything done on the context before -- 1..1024 states, any matrix; both modes
+ * run the same kernels (estep_sample.hip):
+ *   forward vectors: hmm_forward's (khmm.c:170-185), every product rounded once, no FMA: f_1 = a0 o e(o_1); at u = 2..L, for every k:
+ *   tmp = 0.0, for l = 0..n-1: tmp += f_{u-1}[l] * a[l][k], then f_u[k] = e(o_u)[k] * tmp; each f_u is divided (IEEE division) by the
+ *   sum of its entries in ascending k; the missing symbol has emission 1 (the doubles psmc_hip_get_tables returns as f in exact mode);
+ *   random numbers, counter based, on 64-bit unsigned integers: mix(z): z ^= z >> 30, z *= 0xbf58476d1ce4e5b9, z ^= z >> 27,
+ *   z *= 0x94d049bb133111eb, z ^= z >> 31;  G = 0x9e3779b97f4a7c15;  key = mix(mix(seed + G*(j+1)) + G*(q+1));  at position u = 1..L:
+ *   z = mix(key + G*u), r = ((z >> 11) + 1) * 2^-53, in (0, 1];
+ *   the draw from weights w_0..w_{n-1}: c_l = the running sum from 0.0 in ascending l, x = r * c_{n-1} (one rounded product), the index
+ *   is the number of l < n with c_l < x: never a leading run of zero weights (r > 0), never beyond n - 1 (r <= 1).  A total c_{n-1} of 0
+ *   or NaN gives index 0, and a count of n -- only weights below zero can produce it -- gives n - 1: there is no error path;
+ *   the path of sample j: s_L is drawn with r(., L) from w = f_L; for u = L-1 down to 1, s_u is drawn with r(., u) from
+ *   w_l = f_u[l] * a[l][s_{u+1}], each product rounded once (the running sum whose last value is tmp of the forward step for column
+ *   s_{u+1}); path[u-1] = s_u.
+ * The draw at u is a map from the state at u + 1 to the state at u that does not depend on the sample's history: the sweep stores it
+ * for every state, 1 byte per (bin, state padded to a multiple of 64) up to 256 states and 2 bytes beyond, one such table per sample of
+ * a group ("samp_group"), and psmc_hip_viterbi's tiled backtrace ("vit_tile") composes the maps of each sample.
+ * The call reads the observations only: every table, plan, learned state and selection of the context stays as it was, and the
+ * device memory it allocates is released before it returns.
+ * PSMC_HIP_EINVAL: a NULL parameter or path, n_samp < 1.  PSMC_HIP_ESTATE: no segments loaded.  PSMC_HIP_ENOMEM: one sample's table does
+ * not fit; the message holds its size. */
+int psmc_hip_sample_paths(psmc_hip_ctx *ctx, const double *a, const double *e, const double *a0,
+                          uint64_t seed, int32_t n_samp, const uint64_t *stream, int32_t *path);
 
 /* Decoding on a FAST context (up to 128 states): psmc_hip_decode, _posterior, _post_counts, _scales and _post_mean read what the last
  * single E-step (psmc_hip_estep / _estep_device) left:

@@ -196,7 +196,8 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	if (!c || !key) return PSMC_HIP_EINVAL;
 	std::string k(key);
 	if (k == "batch_first") { if (v < 0 || v > 1e6) return PSMC_HIP_EINVAL; c->batch_first = (int)v; return PSMC_HIP_OK; } // (names a replicate context: they all stay)
-	if (k == "vit_tile") { if (!(v >= 16 && v <= 16777216.0) || v != (double)(int)v) return PSMC_HIP_EINVAL; c->vit_tile = (int)v; return PSMC_HIP_OK; } // (read by psmc_hip_viterbi alone)
+	if (k == "vit_tile") { if (!(v >= 16 && v <= 16777216.0) || v != (double)(int)v) return PSMC_HIP_EINVAL; c->vit_tile = (int)v; return PSMC_HIP_OK; } // (read by psmc_hip_viterbi and psmc_hip_sample_paths alone)
+	if (k == "samp_group") { if (!(v >= 0 && v <= 64) || v != (double)(int)v) return PSMC_HIP_EINVAL; c->samp_group = (int)v; return PSMC_HIP_OK; } // (read by psmc_hip_sample_paths alone)
 	destroy_kids(c); // replicate contexts of a batch copied the options when they were made: start them afresh
 	if (k == "chunk") { if (v < 0) return PSMC_HIP_EINVAL; c->chunk = (int)v; c->plan_dirty = true; }
 	else if (k == "warmup") { if (v < 0) return PSMC_HIP_EINVAL; c->warmup = (int)v; c->warmup_set = true; c->plan_dirty = true; }

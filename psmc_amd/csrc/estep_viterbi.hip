@@ -31,24 +31,6 @@ namespace {
 constexpr int VIT_STAGE_BYTES = 32768; // LDS a backtrace work-group stages rows in
 constexpr int VIT_WAIT_VMCNT0 = 0x0F70; // s_waitcnt vmcnt(0) alone on gfx9: vmcnt = 0 (bits 3:0 and 15:14), expcnt = 7, lgkmcnt = 15
 
-// Eight bins of a segment per 64-bit word; the observations of a segment start at a multiple of 64 and are padded to one.
-struct ObsAhead {
-	const uint64_t *w;
-	uint64_t cur, next;
-	int n_words, i;
-	__device__ ObsAhead(const uint8_t *obs, int L) : w((const uint64_t *)obs), n_words((L + 7) >> 3), i(0)
-	{
-		cur = w[0];
-		next = n_words > 1 ? w[1] : 0;
-	}
-	__device__ void advance() // to the next word; the one after it is on its way while this one is used
-	{
-		++i;
-		cur = next;
-		if (i + 1 < n_words) next = w[i + 1];
-	}
-};
-
 // the end of a sweep (one thread): khmm.c's rule over V_L, the lowest state among equal maxima
 __device__ void vit_finish(const double *V, int S, int seg, bool bad, double *score, int32_t *end_state, int32_t *bad_out)
 {
@@ -278,6 +260,21 @@ __global__ __launch_bounds__(256) void k_vit_path(const BP *__restrict__ bp, con
 	}
 }
 
+// the backtrace over one table of [bins][S] entries: passes A, B, C from v.end_state to v.path
+template <typename BP> int launch_backtrace_t(const VitLaunch &v)
+{
+	const int S = v.S;
+	const BP *bp = (const BP *)v.bp;
+	const int R = VIT_STAGE_BYTES / (S * (int)sizeof(BP)); // 16 rows at 1024 states, 512 at 64
+	k_vit_maps<BP><<<v.n_tiles, S, VIT_STAGE_BYTES, v.stream>>>(bp, v.tiles, S, R, v.map);
+	if (v.ev[2]) (void)hipEventRecord(v.ev[2], v.stream);
+	k_vit_compose<<<(v.n_seg + 63) / 64, 64, 0, v.stream>>>(v.seg_tile0, v.seg_nt, v.end_state, v.map, v.n_seg, S, v.tile_end);
+	if (v.ev[3]) (void)hipEventRecord(v.ev[3], v.stream);
+	k_vit_path<BP><<<v.n_tiles, 256, VIT_STAGE_BYTES + sizeof(int32_t) * R, v.stream>>>(bp, v.tiles, v.tile_end, S, R, v.path);
+	if (v.ev[4]) (void)hipEventRecord(v.ev[4], v.stream);
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 template <typename BP> int launch_viterbi_t(const VitLaunch &v)
 {
 	const int S = v.S;
@@ -294,15 +291,7 @@ template <typename BP> int launch_viterbi_t(const VitLaunch &v)
 	}
 #undef VIT_ARGS
 	if (v.ev[1]) (void)hipEventRecord(v.ev[1], v.stream);
-	if (bp) {
-		const int R = VIT_STAGE_BYTES / (S * (int)sizeof(BP)); // 16 rows at 1024 states, 512 at 64
-		k_vit_maps<BP><<<v.n_tiles, S, VIT_STAGE_BYTES, v.stream>>>(bp, v.tiles, S, R, v.map);
-		if (v.ev[2]) (void)hipEventRecord(v.ev[2], v.stream);
-		k_vit_compose<<<(v.n_seg + 63) / 64, 64, 0, v.stream>>>(v.seg_tile0, v.seg_nt, v.end_state, v.map, v.n_seg, S, v.tile_end);
-		if (v.ev[3]) (void)hipEventRecord(v.ev[3], v.stream);
-		k_vit_path<BP><<<v.n_tiles, 256, VIT_STAGE_BYTES + sizeof(int32_t) * R, v.stream>>>(bp, v.tiles, v.tile_end, S, R, v.path);
-		if (v.ev[4]) (void)hipEventRecord(v.ev[4], v.stream);
-	}
+	if (bp) return launch_backtrace_t<BP>(v);
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -311,6 +300,11 @@ template <typename BP> int launch_viterbi_t(const VitLaunch &v)
 int launch_viterbi(const VitLaunch &v)
 {
 	return v.wide_bp ? launch_viterbi_t<uint16_t>(v) : launch_viterbi_t<uint8_t>(v);
+}
+
+int launch_vit_backtrace(const VitLaunch &v)
+{
+	return v.wide_bp ? launch_backtrace_t<uint16_t>(v) : launch_backtrace_t<uint8_t>(v);
 }
 
 } // namespace psmc

@@ -4,6 +4,7 @@
 //   api_wide_fast.hip  fast mode at 129..256 states ("wide_fast") and 257..1024 states ("wide_fast" = 2): plan, rounds and launch of the factored E-step; the full counts of that path ("wide_counts")
 //   api_decode.hip psmc_hip_decode / _posterior / _post_counts / _scales from the exact, the fast or the wide fast tables (one wave per tile or 2..4)
 //   api_viterbi.hip psmc_hip_viterbi: the Viterbi path of every segment (reads the observations only)
+//   api_sample.hip psmc_hip_sample_paths: state paths drawn from the posterior, forward filtering and backward sampling (reads the observations only)
 //   api_batch.hip  psmc_hip_estep_batch (bootstrap replicates): exact launch groups, fast per-replicate plans
 //   api_probes.hip device self-test, microbenchmarks and probes (diagnostics)
 // Everything is built with -ffp-contract=off: no host or device expression is ever fused.
@@ -350,6 +351,8 @@ struct psmc_hip_ctx {
 	int wg_cap = 0;
 	// "vit_tile": bins per backtrace tile of psmc_hip_viterbi (api_viterbi.hip); results do not depend on it
 	int vit_tile = 2048;
+	// "samp_group": samples per sweep of psmc_hip_sample_paths (api_sample.hip); 0 = as many as the free device memory holds, at most 8
+	int samp_group = 0;
 };
 // the padded width of the wide fast path's own tables (api_wide_fast.hip writes them, api_decode.hip reads them): c->ns (192 or 256)
 // up to 256 states, beyond them the next multiple of 256 -- one wave of the tile per 256 states (c->ns stays what the wide exact

@@ -258,6 +258,24 @@ struct VitSeg {      // one segment of the sweep's launch, longest first
 	int64_t row_off; // ... and in the back-pointer table and the path: the bins of the segments before it in load order
 	int32_t L, seg;
 };
+// (read by the sweeps of estep_viterbi.hip and estep_sample.hip)
+// Eight bins of a segment per 64-bit word; the observations of a segment start at a multiple of 64 and are padded to one.
+struct ObsAhead {
+	const uint64_t *w;
+	uint64_t cur, next;
+	int n_words, i;
+	__device__ ObsAhead(const uint8_t *obs, int L) : w((const uint64_t *)obs), n_words((L + 7) >> 3), i(0)
+	{
+		cur = w[0];
+		next = n_words > 1 ? w[1] : 0;
+	}
+	__device__ void advance() // to the next word; the one after it is on its way while this one is used
+	{
+		++i;
+		cur = next;
+		if (i + 1 < n_words) next = w[i + 1];
+	}
+};
 struct VitTile {     // one backtrace tile: positions lo..hi (1-based) of the segment whose rows start at row_off
 	int64_t row_off;
 	int32_t lo, hi;
@@ -280,6 +298,25 @@ struct VitLaunch {
 	hipEvent_t ev[5];                  // optional time stamps: start, sweep, pass A, pass B, pass C (null: none)
 };
 int launch_viterbi(const VitLaunch &v);
+// the backtrace alone (passes A, B, C) over any table of "the state below, given the state here": reads stream, S, wide_bp, bp, n_seg,
+// end_state, tiles, n_tiles, seg_tile0, seg_nt, map, tile_end, path and ev[2..4] of v
+int launch_vit_backtrace(const VitLaunch &v);
+// estep_sample.hip: psmc_hip_sample_paths (api_sample.hip).  a [S][S] with a[l * S + k] = a[l][k], e [3][S] (row 2 all ones), a0 [S], all
+// zero in the padding.  One launch sweeps every segment once for the `group` samples first .. first + group - 1.
+constexpr int SAMP_MAX_GROUP = 64;
+struct SampLaunch {
+	hipStream_t stream;
+	int n, S, wide_bp;                 // wide_bp: 2 bytes per map entry (S > 256)
+	const double *a, *e, *a0;
+	const uint8_t *obs;
+	const VitSeg *segs; int n_seg;     // longest first
+	const uint64_t *sid;               // [n_seg] by segment id: the stream id q
+	uint64_t seed;
+	int first, group;                  // samples first .. first + group - 1, group <= SAMP_MAX_GROUP
+	void *map; size_t map_stride;      // table g at map + g * map_stride bytes: [bins][S] entries, row u - 1 = the state at u - 1 given the state at u
+	int32_t *end_state;                // [group][n_seg]: s_L of every sample and segment
+};
+int launch_sample_sweep(const SampLaunch &p);
 int run_selftest(hipStream_t stream, unsigned *d_flags);
 int run_microbench(hipStream_t stream, double *d_out);
 int run_pipe_probe(hipStream_t stream, double *d_out, int n_waves, unsigned mask, int rounds);

@@ -28,7 +28,7 @@ EXPORTS = [
     "psmc_hip_last_error", "psmc_hip_set_option", "psmc_hip_load_segments",
     "psmc_hip_load_segments_device", "psmc_hip_select", "psmc_hip_estep",
     "psmc_hip_estep_segments", "psmc_hip_estep_batch", "psmc_hip_estep_batch_cb", "psmc_hip_reserve_batch_tables", "psmc_hip_batch_info", "psmc_hip_estep_device", "psmc_hip_fast_diag", "psmc_hip_fast_repairs", "psmc_hip_fast_info", "psmc_hip_estep_factored",
-    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales", "psmc_hip_post_mean", "psmc_hip_viterbi",
+    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales", "psmc_hip_post_mean", "psmc_hip_viterbi", "psmc_hip_sample_paths",
     "psmc_hip_group_selfcheck", "psmc_hip_fast_plan",
     "psmc_hip_group_create", "psmc_hip_group_destroy", "psmc_hip_group_last_error", "psmc_hip_group_set_option",
     "psmc_hip_group_load_segments", "psmc_hip_group_estep", "psmc_hip_group_estep_factored", "psmc_hip_group_info",
@@ -531,6 +531,25 @@ class HipEStep:
             return None, score
         ends = np.cumsum(lens)
         return [path[end - L:end] for end, L in zip(ends, lens)], score
+
+    def sample_paths(self, a, e, a0, seed, n_samp=1, stream=None):
+        """paths[j][i]: sample j (0-based) of segment i in load order, int32 arrays -- state paths drawn from the posterior by
+        forward filtering and backward sampling (psmc_hip_sample_paths).  Pinned bit for bit by (a, e, a0, observations, seed, j, the
+        segment's stream id): `stream` gives one id per segment (None: the load index); mode, "vit_tile" and "samp_group" change nothing.
+        Reads the observations only."""
+        a, e, a0 = self._params(a, e, a0)
+        lens = [int(x) for x in self.lens]
+        n_samp = int(n_samp)
+        path = np.zeros(max(n_samp, 0) * sum(lens), dtype=np.int32)
+        sid = None if stream is None else np.ascontiguousarray(stream, dtype=np.uint64)
+        assert sid is None or sid.shape == (len(lens),), sid.shape
+        self.lib.psmc_hip_sample_paths.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64), _i32p]
+        self._chk(self.lib.psmc_hip_sample_paths(self.h, _p(a), _p(e), _p(a0), int(seed) & (2 ** 64 - 1), n_samp,
+                                                 None if sid is None else sid.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 path.ctypes.data_as(_i32p)), "sample_paths")
+        ends = np.cumsum(lens)
+        per = path.reshape(n_samp, -1)
+        return [[per[j, end - L:end] for end, L in zip(ends, lens)] for j in range(n_samp)]
 
     def timing(self):
         ms = np.zeros(7)

@@ -252,6 +252,52 @@ static int hb_viterbi(void *self, const double *a, const double *e, const double
 	free(cx); free(loc); free(glob); free(off); free(sp); free(ss);
 	return rc;
 }
+/* State paths drawn from the posterior, all segments in input order.  One context: psmc_hip_sample_paths as it is.  A group: one call
+ * per shard context with the shard's segments' INPUT indices (or the caller's ids of them) as stream ids -- the samples do not depend
+ * on how the input is dealt out -- scattered to input order as hb_viterbi does. */
+static int hb_sample_paths(void *self, const double *a, const double *e, const double *a0, uint64_t seed, int32_t n_samp, const uint64_t *stream,
+                           int32_t *path)
+{
+	hip_be *h = (hip_be *)self;
+	h->verr = 0;
+	if (!h->grp) return psmc_hip_sample_paths(h->ctx, a, e, a0, seed, n_samp, stream, path);
+	if (n_samp < 1 || !path) return PSMC_HIP_EINVAL;
+	const int n = h->n_seg;
+	psmc_hip_ctx **cx = (psmc_hip_ctx **)malloc(sizeof(void *) * (size_t)n);
+	int *loc = (int *)malloc(sizeof(int) * (size_t)n), *glob = (int *)malloc(sizeof(int) * (size_t)n);
+	int64_t *off = (int64_t *)malloc(sizeof(int64_t) * ((size_t)n + 1));
+	uint64_t *sid = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)n);
+	int32_t *sp = 0;
+	int rc = cx && loc && glob && off && sid ? 0 : PSMC_HIP_ENOMEM;
+	if (rc == 0) off[0] = 0;
+	for (int i = 0; rc == 0 && i < n; ++i) {
+		off[i + 1] = off[i] + h->L[i];
+		rc = psmc_hip_group_route(h->grp, i, &cx[i], &loc[i]);
+	}
+	for (int i = 0; rc == 0 && i < n; ++i) {
+		int seen = 0, m = 0;
+		int64_t bins = 0;
+		for (int j = 0; j < i && !seen; ++j) seen = cx[j] == cx[i];
+		if (seen) continue;
+		for (int j = i; j < n; ++j) /* the shard's segments by their index there: 0 .. m-1 */
+			if (cx[j] == cx[i]) { ++m; bins += h->L[j]; }
+		for (int j = i; j < n; ++j)
+			if (cx[j] == cx[i]) { if (loc[j] < 0 || loc[j] >= m) rc = PSMC_HIP_EINVAL; else glob[loc[j]] = j; }
+		if (rc) break;
+		for (int l = 0; l < m; ++l) sid[l] = stream ? stream[glob[l]] : (uint64_t)glob[l];
+		sp = (int32_t *)realloc(sp, sizeof(int32_t) * (size_t)bins * (size_t)n_samp);
+		if (!sp) { rc = PSMC_HIP_ENOMEM; break; }
+		rc = psmc_hip_sample_paths(cx[i], a, e, a0, seed, n_samp, sid, sp);
+		if (rc) { snprintf(h->msg, sizeof h->msg, "%s (a shard; its first segment is segment %d of the input)", psmc_hip_last_error(cx[i]), glob[0]); h->verr = h->msg; break; }
+		for (int32_t j = 0; j < n_samp; ++j) {
+			int64_t so = 0;
+			for (int l = 0; l < m; so += h->L[glob[l]], ++l)
+				memcpy(path + (size_t)j * off[n] + off[glob[l]], sp + (size_t)j * bins + so, sizeof(int32_t) * (size_t)h->L[glob[l]]);
+		}
+	}
+	free(cx); free(loc); free(glob); free(off); free(sid); free(sp);
+	return rc;
+}
 static void hb_destroy(void *self)
 {
 	hip_be *h = (hip_be *)self;
@@ -297,7 +343,7 @@ int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_fa
 	be->self = h; be->load = hb_load; be->estep = hb_estep; be->tables = hb_tables; be->decode = hb_decode;
 	be->estep_factored = use_factored ? hb_estep_factored : 0; be->error = hb_error; be->destroy = hb_destroy;
 	be->posterior = hb_posterior; be->post_counts = hb_post_counts; be->prepare_decode = hb_prepare_decode; be->scales = hb_scales;
-	be->post_mean = hb_post_mean; be->viterbi = hb_viterbi;
+	be->post_mean = hb_post_mean; be->viterbi = hb_viterbi; be->sample_paths = hb_sample_paths;
 	return 0;
 }
 

@@ -115,10 +115,22 @@ typedef struct psmc_estep_backend {
 	 * L[0] + .. + L[i-1], 0-based states; score one double per segment (hmm_Viterbi's return value).  Non-zero when a segment has no
 	 * path of finite probability.  A backend without it gets psmc_viterbi_host */
 	int  (*viterbi)(void *self, const double *a, const double *e, const double *a0, int32_t *path, double *score);
+	/* optional (may be NULL; last, so that an aggregate initialiser without it says no): n_samp state paths of ALL loaded segments drawn
+	 * from the posterior (psmc_hip_sample_paths; the PSMC_SAMPLE track): path holds n_samp * sum of L entries, sample j, segment i at
+	 * j * (sum of L) + L[0] + .. + L[i-1]; stream: one id per segment, or NULL: the input index.  A backend without it gets
+	 * psmc_sample_host */
+	int  (*sample_paths)(void *self, const double *a, const double *e, const double *a0, uint64_t seed, int32_t n_samp,
+	                     const uint64_t *stream, int32_t *path);
 } psmc_estep_backend;
 /* the dense Viterbi recursion on the host, one segment: log tables by libm's log(), every candidate one addition, the first maximum
  * wins (the arithmetic include/psmc_hip.h pins).  path[L], *score; returns 0, 1 = no path of finite probability, 2 = out of memory */
 int psmc_viterbi_host(int n, const double *a, const double *e, const double *a0, const uint8_t *sym, int32_t L, int32_t *path, double *score);
+
+/* forward filtering, backward sampling on the host, one segment: the definition include/psmc_hip.h pins, in plain C -- the forward
+ * vectors of hmm_forward are stored, then every sample walks down from L.  path[j*L + u-1] = the state of sample j at position u;
+ * stream_id: the segment's q.  Returns 0, or 2 = out of memory */
+int psmc_sample_host(int n, const double *a, const double *e, const double *a0, const uint8_t *sym, int32_t L, uint64_t seed, uint64_t stream_id,
+                     int32_t n_samp, int32_t *path);
 
 /* ---- run state + driver (main.c, em.c, aux.c) */
 typedef struct {

@@ -7,6 +7,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_dp = C.POINTER(C.c_double)
 
 
 class _Pattern(C.Structure):
@@ -35,8 +36,28 @@ def load():
         lib.psmc_model_new.argtypes = [C.POINTER(_Pattern), C.c_char_p, C.c_double, C.c_int]
         lib.psmc_model_update.argtypes = [C.POINTER(_Model)]
         lib.psmc_model_free.argtypes = [C.POINTER(_Model)]
+        lib.psmc_sample_host.argtypes = [C.c_int, _dp, _dp, _dp, C.POINTER(C.c_uint8), C.c_int32, C.c_uint64, C.c_uint64, C.c_int32,
+                                         C.POINTER(C.c_int32)]
         _LIB = lib
     return _LIB
+
+
+def sample_host(a, e, a0, seq, seed, stream_id, n_samp=1):
+    """paths (n_samp, L) int32: psmc_sample_host, the plain C statement of the sampling definition of include/psmc_hip.h (forward
+    filtering, backward sampling) for one segment; e is (2, n) or (3, n), rows hom, het."""
+    lib = load()
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    e = np.ascontiguousarray(np.asarray(e, dtype=np.float64)[:2])
+    a0 = np.ascontiguousarray(a0, dtype=np.float64)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    n = a0.shape[0]
+    assert a.shape == (n, n) and e.shape == (2, n) and seq.ndim == 1 and len(seq) >= 1 and n_samp >= 1
+    path = np.zeros((int(n_samp), len(seq)), dtype=np.int32)
+    rc = lib.psmc_sample_host(n, a.ctypes.data_as(_dp), e.ctypes.data_as(_dp), a0.ctypes.data_as(_dp), seq.ctypes.data_as(C.POINTER(C.c_uint8)),
+                              len(seq), int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), int(n_samp), path.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc:
+        raise MemoryError("psmc_sample_host: %d" % rc)
+    return path
 
 
 def hmm_params(pattern, params, alpha=0.1):
