@@ -556,6 +556,41 @@ int psmc_hip_scales(psmc_hip_ctx *ctx, int seg, double *s);
 #define PSMC_HIP_MAX_MEAN_COLS 4
 int psmc_hip_post_mean(psmc_hip_ctx *ctx, int seg, const double *w, int32_t n_w, double *mean);
 
+/* Per-bin posterior quantiles of one segment on the device: the median and a credible band of the local TMRCA (the posterior over
+ * the states is skewed and often bimodal near a breakpoint, so mean +- sd is no band).  q holds n_q values in [0, 1],
+ * 1 <= n_q <= PSMC_HIP_MAX_QUANT_COLS, and
+ *   state[(u-1)*n_q + j] = the 0-based state at the q[j] quantile of the posterior of bin u,   u = 1..L, j = 0..n_q-1,
+ * bins numbered as psmc_hip_decode numbers them.  4*n_q bytes per bin leave the GPU instead of the 8*n of the rows.  The sixth sibling
+ * of _decode / _posterior / _post_counts / _scales / _post_mean: the state rules are exactly those of _post_mean ("Decoding on a
+ * FAST context": which tables are read, ESTATE, ENOTSUP, "wide_decode", "wide_decode_ckpt", selection and reload); it reads tables
+ * only, and its device scratch is freed before it returns.  PSMC_HIP_EINVAL for a NULL q or state, for n_q outside
+ * 1..PSMC_HIP_MAX_QUANT_COLS and for any q[j] that is NaN or outside [0, 1].
+ * The rule is the one psmc_hip_sample_paths uses for a draw: the number of states whose running sum lies below q times the total.
+ * Per source:
+ *   - the exact tables (exact mode, the exact fallbacks of a fast context, beyond 128 states without "wide_decode"):
+ *     gamma_u(k) = f*b*s multiplied left to right; c_0 = gamma_u(0), c_k = c_{k-1} + gamma_u(k), one rounded addition each in
+ *     ascending k (no FMA); x_j = q[j] * c_{n-1}, one rounded product; state = min(n-1, #{k < n : c_k < x_j}).  A NaN total gives 0
+ *     (every comparison is false).  Bit for bit what a C loop over the rows of psmc_hip_posterior gives (estep_post_quantile.hip); so
+ *     q = 0 gives state 0, and q = 1 the first state at which the running sum reaches its final value;
+ *   - the fast tables up to 128 states: the same count, #{k < n : c_k < q[j] G} clipped to n-1, over the kernel's own prefix sums
+ *     of the unnormalised g_u(k) = X_u(k) bt_u(k) / e_k(o_u) (a wave scan; any association, FMAs) and its own total G_u
+ *     (estep_post_fast.hip); padded states (k >= n) are left out by a test of their index, not by their g being zero;
+ *   - the wide fast tables (full or checkpoints): the same count over the prefix sums of the sweep's g_p(k) = X_p(k) y(k) and
+ *     G_p (estep_wide_post.hip): the prefix of a state is its thread's running sum plus the sums of the lanes and of the waves
+ *     below it.  Beyond 256 states the wave that holds the quantile is found from the waves' totals alone -- the lowest wave w*
+ *     whose inclusive prefix is not below q[j] G -- and the state is min(n, the states of the waves below w*) + the count within
+ *     w*, clipped to n-1.  From checkpoints the bits of the full table.
+ * On every source the result is deterministic -- it depends on the tables and q alone -- and every column is computed on its own: a
+ * call with several columns returns, column by column, the bits of the calls with one.
+ * Guarantees for the fast sources (the exact ones are bit-pinned above), with C_k the cdf of a posterior row summed in state order
+ * without rounding (C_{-1} = -inf) and i the returned state:  (i == 0 or C_{i-1} < q + d) and (i == n-1 or C_i >= q - d), where
+ *   (Q2) against the rows psmc_hip_posterior returns on the same context in the same call state: d = 2 * (n + 8) * 2^-52 -- C_i is a
+ *        _post_mean with an indicator column, whose bound for |w| <= 1 is (n + 8) * 2^-52; doubled for forming q G and comparing
+ *        unnormalised;
+ *   (Q3) against the rows of an exact context given the same parameters: d = 1e-9 * n (the posterior's 1e-9 absolute per state). */
+#define PSMC_HIP_MAX_QUANT_COLS 4
+int psmc_hip_post_quantile(psmc_hip_ctx *ctx, int seg, const double *q, int32_t n_q, int32_t *state);
+
 /* Viterbi path of every loaded segment (khmm.c:83-141), in load order; psmc_hip_select is not read.
  * path: sum of L entries, segment i at offset L[0]+..+L[i-1]; score: n_seg doubles (hmm_Viterbi's return value).
  * Either may be NULL; with path == NULL no back-pointer table is allocated.
@@ -609,7 +644,7 @@ int psmc_hip_viterbi(psmc_hip_ctx *ctx, const double *a, const double *e, const 
 int psmc_hip_sample_paths(psmc_hip_ctx *ctx, const double *a, const double *e, const double *a0,
                           uint64_t seed, int32_t n_samp, const uint64_t *stream, int32_t *path);
 
-/* Decoding on a FAST context (up to 128 states): psmc_hip_decode, _posterior, _post_counts, _scales and _post_mean read what the last
+/* Decoding on a FAST context (up to 128 states): psmc_hip_decode, _posterior, _post_counts, _scales, _post_mean and _post_quantile read what the last
  * single E-step (psmc_hip_estep / _estep_device) left:
  *   - the fast tables X and bt -- the dense sweeps (any matrix, <= 64 states) or the structured ones with the unfused back half
  *     ("fuse" = 0 up to 64 states, "fuse128" = 0 for 65..128): scale-free kernels (estep_post_fast.hip) compute

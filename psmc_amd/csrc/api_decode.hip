@@ -1,6 +1,7 @@
-// api_decode.hip -- the decoding entry points psmc_hip_decode / _posterior / _post_counts / _scales / _post_mean: one segment of the
-// last single E-step, from whichever tables that E-step left (decode_source):
-//   DEC_EXACT  f, b and s of the exact kernels (estep_exact.hip, estep_wide.hip beyond 128 states; _post_mean: estep_post_mean.hip)
+// api_decode.hip -- the decoding entry points psmc_hip_decode / _posterior / _post_counts / _scales / _post_mean / _post_quantile: one
+// segment of the last single E-step, from whichever tables that E-step left (decode_source):
+//   DEC_EXACT  f, b and s of the exact kernels (estep_exact.hip, estep_wide.hip beyond 128 states; _post_mean: estep_post_mean.hip;
+//              _post_quantile: estep_post_quantile.hip)
 //   DEC_FAST   X and bt of a fast E-step with the unfused back half, up to 128 states (estep_post_fast.hip)
 //   DEC_WIDE   X, 1/d, entry and bentry of a wide fast E-step with "wide_decode": 129..256 states (estep_wide_post.hip), and
 //              257..1024 states with "wide_fast" = 2 (the same file; the tables are 512, 768 or 1024 states wide).  After a
@@ -254,6 +255,47 @@ extern "C" int psmc_hip_post_mean(psmc_hip_ctx *c, int seg, const double *w, int
 	hipError_t e2 = hipStreamSynchronize(c->stream); // (hw lives until here: the upload has been consumed)
 	if (rc || e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess)
 		return fail(c, PSMC_HIP_EDEVICE, src == DEC_WIDE ? "post_mean (wide fast tables)" : "post_mean");
+	return PSMC_HIP_OK;
+}
+
+static_assert(QUANT_COLS == PSMC_HIP_MAX_QUANT_COLS, "the kernels' column count is the header's");
+
+extern "C" int psmc_hip_post_quantile(psmc_hip_ctx *c, int seg, const double *q, int32_t n_q, int32_t *state)
+{
+	if (!c || seg < 0 || seg >= c->n_seg || !q || !state || n_q < 1 || n_q > PSMC_HIP_MAX_QUANT_COLS) return fail(c, PSMC_HIP_EINVAL, "post_quantile: bad argument");
+	QuantQ qq = {};
+	for (int j = 0; j < n_q; ++j) {
+		if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(c, PSMC_HIP_EINVAL, "post_quantile: every q must lie in [0, 1]"); // (a NaN fails both)
+		qq.q[j] = q[j];
+	}
+	int t0 = 0, nt = 0;
+	const int src = decode_source(c, seg, "post_quantile", &t0, &nt);
+	if (src < 0) return src;
+	if (src == DEC_EXACT && (!c->d_f || !c->have_b || c->tables_batch)) return fail(c, PSMC_HIP_ESTATE, "post_quantile: no single E-step yet");
+	HIPCHK(c, hipSetDevice(c->device));
+	const int L = c->L[seg], n = c->n;
+	Scratch sc;
+	int32_t *dq = sc.get<int32_t>((size_t)L * n_q);
+	if (!sc.ok) return fail(c, PSMC_HIP_ENOMEM, "hipMalloc");
+	int rc; // (nothing to upload: the thresholds travel with the launch)
+	switch (src) {
+	case DEC_WIDE: {
+		WidePost wp;
+		wide_post_common(c, wp, WP_QUANT, t0, nt);
+		wp.q = qq; wp.n_q = n_q; wp.qstate = dq;
+		rc = launch_wide_post(wp);
+		break;
+	}
+	case DEC_FAST:
+		rc = launch_post_quantile_fast(c->stream, c->d_f, c->d_b, par_re(c), c->d_obs, c->off[seg], L, n, c->ns, qq, n_q, dq);
+		break;
+	default:
+		rc = launch_post_quantile_exact(c->stream, c->d_f, c->d_b, c->d_s, c->off[seg], L, n, c->ns, qq, n_q, dq);
+	}
+	hipError_t e1 = hipMemcpyAsync(state, dq, sizeof(int32_t) * (size_t)L * n_q, hipMemcpyDeviceToHost, c->stream);
+	hipError_t e2 = hipStreamSynchronize(c->stream);
+	if (rc || e1 != hipSuccess || e2 != hipSuccess)
+		return fail(c, PSMC_HIP_EDEVICE, src == DEC_WIDE ? "post_quantile (wide fast tables)" : "post_quantile");
 	return PSMC_HIP_OK;
 }
 

@@ -1,5 +1,5 @@
 // estep_post_fast.hip -- posterior decoding from the tables of a FAST-mode E-step (psmc_hip_decode / _posterior /
-// _post_counts / _scales / _post_mean on a fast context whose last single E-step left both X and bt: the dense sweeps, or the
+// _post_counts / _scales / _post_mean / _post_quantile on a fast context whose last single E-step left both X and bt: the dense sweeps, or the
 // structured sweeps with the unfused back half, "fuse=0" / "fuse128=0").
 //
 // Conventions of the tables (estep_fast.hip, estep_struct.hip; g = seg_off + u - 1):
@@ -16,6 +16,7 @@
 // taken from lane 0 so that every lane divides by the same double.
 #include <hip/hip_runtime.h>
 #include "wave_prims.h"
+#include "struct_prims.h"
 #include "psmc_hip_internal.h"
 
 namespace psmc {
@@ -135,6 +136,41 @@ __global__ __launch_bounds__(64) void k_post_mean_fast(const double *__restrict_
 	}
 }
 
+// psmc_hip_post_quantile: state[(u-1)*n_q + j] = min(n - 1, #{k < n : c_k < q_j G}) over the prefix sums c_k of the row's
+// unnormalised gam and its total G (post_row's; no division).  A lane holds the states lane + 64 j, so the prefix over the states
+// is the inclusive wave scan of gam[j] plus the totals of the lower j (lane 63 of their scans); the count is a ballot per j, and
+// the padded states (k >= n) are left out by the test itself.  A NaN total: every comparison is false, state 0.
+template <int S>
+__global__ __launch_bounds__(64) void k_post_quantile_fast(const double *__restrict__ f, const double *__restrict__ b,
+                                                             const double *__restrict__ re, const uint8_t *__restrict__ obs, int64_t off,
+                                                             int L, int n, QuantQ qq, int n_q, int32_t *__restrict__ state)
+{
+	constexpr int PER = S / 64;
+	const int lane = threadIdx.x;
+	const int u0 = blockIdx.x * POST_BLK + 1, u1 = min(L, u0 + POST_BLK - 1);
+	for (int u = u0; u <= u1; ++u) {
+		const int64_t g = off + u - 1;
+		PostRow<S> r;
+		post_row<S>(f, b, re, (int)obs[g], g, u, L, lane, r);
+		double c[PER], base = 0.0;
+#pragma unroll
+		for (int j = 0; j < PER; ++j) {
+			c[j] = wave_prefix_incl_bc(r.gam[j]);
+			if (j) c[j] += base;
+			if (j + 1 < PER) base = readlane_f64(c[j], 63);
+		}
+#pragma unroll
+		for (int col = 0; col < QUANT_COLS; ++col)
+			if (col < n_q) { // (a kernel argument: the same in every lane)
+				const double x = qq.q[col] * r.G;
+				int cnt = 0;
+#pragma unroll
+				for (int j = 0; j < PER; ++j) cnt += __popcll(__ballot(lane + 64 * j < n && c[j] < x));
+				if (lane == 0) state[(int64_t)(u - 1) * n_q + col] = min(cnt, n - 1);
+			}
+	}
+}
+
 // -s: the reference's scaling factors s_u (hmm_forward, khmm.c:170-186).  Tiles of the segment: T bins each, the first
 // one is tile `first` of the plan (its start vectors in entry).
 template <int S>
@@ -239,6 +275,15 @@ int launch_post_mean_fast(hipStream_t st, const double *f, const double *b, cons
 	const dim3 grid((L + POST_BLK - 1) / POST_BLK);
 	if (ns == 128) hipLaunchKernelGGL(k_post_mean_fast<128>, grid, dim3(64), 0, st, f, b, re, obs, off, L, w, n_w, mean);
 	else hipLaunchKernelGGL(k_post_mean_fast<64>, grid, dim3(64), 0, st, f, b, re, obs, off, L, w, n_w, mean);
+	return (int)hipGetLastError();
+}
+
+int launch_post_quantile_fast(hipStream_t st, const double *f, const double *b, const double *re, const uint8_t *obs, int64_t off, int L,
+                              int n, int ns, const QuantQ &q, int n_q, int32_t *state)
+{
+	const dim3 grid((L + POST_BLK - 1) / POST_BLK);
+	if (ns == 128) hipLaunchKernelGGL(k_post_quantile_fast<128>, grid, dim3(64), 0, st, f, b, re, obs, off, L, n, q, n_q, state);
+	else hipLaunchKernelGGL(k_post_quantile_fast<64>, grid, dim3(64), 0, st, f, b, re, obs, off, L, n, q, n_q, state);
 	return (int)hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // estep_wide_post.hip -- decoding on the wide fast path (129..1024 states, options "wide_fast" + "wide_decode"; api_decode.hip
-// drives it): psmc_hip_decode / _posterior / _post_counts / _scales / _post_mean from what the last wide fast E-step left, without a backward table.
+// drives it): psmc_hip_decode / _posterior / _post_counts / _scales / _post_mean / _post_quantile from what the last wide fast E-step left, without a backward table.
 //
 // The E-step keeps the lag-normalised forward table X (and 1/d_p at p % 4 == 0), every tile's forward start vector `entry` and its
 // backward start vector bentry = bt_{top+1}, converged to "warm_tol" by the verify / repair rounds.  One more backward sweep per
@@ -20,6 +20,9 @@
 //                MEAN (psmc_hip_post_mean): instead of rows, up to four posterior expectations sum_k gamma_p(k) w_j(k) per position.  A
 //                thread keeps the NPL x n_w weights of its states in registers; a wave's share of sum_k g_p(k) w_j(k) rides in slot
 //                1 + j of the exchange that carries G (WX_SLOTS = 6: G and four columns), and mean_j = that sum * iG, stored by thread 0
+//                QUANT (psmc_hip_post_quantile): instead of rows, per position the state at up to four posterior quantiles, from the
+//                prefix sums of g and G alone -- no division and NO further exchange: the waves' totals that make G also tell every
+//                wave which wave holds the quantile (see emit)
 //   k_wp_cnt_add the tiles' partials added in tile order (deterministic)
 //   k_wp_scales  s_p = sum X_p / sum X_{p-1} / inv_p from X alone (X_{lo-1}: the tile's own `entry`), s_1 = sum_k a0_k e_k(o_1).
 //                ONE wave per tile at every width adds the W blocks of 64 NPL states of a row, lowest block first: no LDS, no barrier
@@ -46,7 +49,9 @@
 //   k_wp_dec  counts, CKPT                  116 10752 4      148 14336 3      150 28864 3      156 43296 3      160 57728 2
 //   k_wp_dec  mean                          126     0 4      158     0 3      154   192 3      158   288 3      162   384 3
 //   k_wp_dec  mean, CKPT                    124 10752 4      156 14336 3      150 28864 3      156 43296 3      160 57728 2
-//   k_wp_scales (64 threads)                 16     0 8       16     0 8       22     0 8       30     0 8       40     0 8
+//   k_wp_dec  quantiles                      94     0 5      118     0 4      124   192 4      126   288 4      130   384 3
+//   k_wp_dec  quantiles, CKPT                92 10752 4      116 14336 3      118 28864 3      124 43296 3      128 57728 2
+//   k_wp_scales (64 threads)                16     0 8       16     0 8       22     0 8       30     0 8       40     0 8
 //   k_wp_scales_ck                           80     0 6      102     0 4      106   192 4      110   288 4      112   384 4
 //   k_wp_cnt_add                         8 VGPRs at every width, no LDS
 // With CKPT the staged rows bound a compute unit at 15 tiles (S = 192), 11 (256), five (512), three (768) or two (1024) of its
@@ -66,15 +71,32 @@ constexpr int CB = 4; // count columns one sweep of k_wp_dec carries (CB x NPL a
 // maximum, across waves the lowest wave whose maximum equals the tile's -- the lowest state wins (a NaN: wave 0's, lane 0's).
 // MEAN (psmc_hip_post_mean): wt = the weights of the thread's states, column by column; the wave's share of sum_k g(k) w_j(k) rides
 // in slot 1 + j of the same exchange (PATH, which uses the slots 1 and 2, is never on with it), and mean_j = that sum * iG.
-template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool MEAN>
+// QUANT (psmc_hip_post_quantile; never on with PATH or MEAN): state_j = min(n - 1, #{k < n : c_k < x_j}), x_j = q_j G, over the prefix
+// sums c_k = (the totals of the waves below + the sums of the lanes below) + the lane's running sum up to k.  With P_w = the totals
+// of the waves 0 .. w added lowest first (what below(0) of wave w + 1 is), every wave finds from the exchanged totals alone
+// w* = the lowest wave whose P_w is not below x_j (the last wave when there is none), and wave w* stores
+//   min(n, 64 NPL w*) + #{k of wave w*, k < n : c_k < x_j}:
+// every state of a wave below w* counts (its prefix is at most P_{w*-1} < x_j up to the rounding of the sums) and none above.  One
+// wave stores each column, from exchanged values and its own registers: unique, and the same on every run.  A NaN total: P_0 is not
+// below it, wave 0 stores its count, 0.  Padded states are left out by the test k < n itself.
+template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool MEAN, bool QUANT>
 __device__ __forceinline__ void emit(int p, int tid, int n, const double (&g)[NPL], double r, bool last, Xchg<W> &xc,
                                      double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
                                      double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0, int min_l,
-                                     double (&acc)[CB][NPL], const double (&wt)[MEAN_COLS][NPL], int n_w, double *__restrict__ mean)
+                                     double (&acc)[CB][NPL], const double (&wt)[MEAN_COLS][NPL], int n_w, double *__restrict__ mean,
+                                     const QuantQ &qq, int n_q, int32_t *__restrict__ qstate)
 {
 	static_assert(!(MEAN && PATH) && 1 + MEAN_COLS <= WX_SLOTS, "G takes slot 0 and every column of weights one more slot");
+	static_assert(!(QUANT && (PATH || MEAN)), "the quantiles are a sweep of their own");
 	const int k0 = NPL * tid;
 	xc.put(0, wave_total(lsum<NPL>(g)));
+	double run[NPL], lanes_below = 0.0; // QUANT: the lane's running sums (run[NPL - 1] is lsum's own sequence) and the sum of the lanes below
+	if (QUANT) {
+		run[0] = g[0];
+#pragma unroll
+		for (int i = 1; i < NPL; ++i) run[i] = run[i - 1] + g[i];
+		lanes_below = wave_excl_prefix(run[NPL - 1]);
+	}
 	if (MEAN) { // (n_w is a kernel argument: the same in every wave)
 #pragma unroll
 		for (int j = 0; j < MEAN_COLS; ++j)
@@ -111,6 +133,32 @@ __device__ __forceinline__ void emit(int p, int tid, int n, const double (&g)[NP
 	if (MEAN) { // from exchanged values only: the same bits in every wave
 #pragma unroll
 		for (int j = 0; j < MEAN_COLS; ++j) mj[j] = j < n_w ? xc.sum(1 + j) * iG : 0.0;
+	}
+	if (QUANT) { // (n_q is a kernel argument; the stores sit under wave == w*, the exchange is behind us)
+		const double G = xc.sum(0);
+		double base = lanes_below;
+		int wave = 0;
+		if constexpr (W > 1) { base += xc.below(0); wave = xc.wave; }
+#pragma unroll
+		for (int j = 0; j < QUANT_COLS; ++j)
+			if (j < n_q) {
+				const double x = qq.q[j] * G;
+				int ws = W - 1;
+				if constexpr (W > 1) {
+					double P = xc.get(0, 0);
+					bool found = !(P < x);
+					ws = found ? 0 : W - 1;
+#pragma unroll
+					for (int w = 1; w < W - 1; ++w) {
+						P += xc.get(0, w);
+						if (!found && !(P < x)) { found = true; ws = w; }
+					}
+				}
+				int cnt = 0;
+#pragma unroll
+				for (int i = 0; i < NPL; ++i) cnt += __popcll(__ballot(k0 + i < n && base + run[i] < x));
+				if (wave == ws && xc.lane == 0) qstate[(int64_t)(p - 1) * n_q + j] = min(min(n, 64 * NPL * ws) + cnt, n - 1);
+			}
 	}
 	xc.next();
 	if (POST) {
@@ -167,7 +215,7 @@ __device__ __forceinline__ void dstep(const StructParN<NPL> &sc, const WaveScanM
 // The hang rule: the branches that enclose an exchange are `c.hi == c.L` and `top >= lo` (the tile descriptor), the bounds of the
 // loops (top, lo, the block bounds q, pb, pe), `p > top || p < lo`, `q >= lo`, `lo > 1` and `p & 3` (the loop counters) and the
 // template flags -- the same in every wave.
-template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool CKPT, bool MEAN>
+template <int NPL, int W, bool POST, bool REC, bool PATH, bool CNT, bool CKPT, bool MEAN, bool QUANT>
 __global__ __launch_bounds__(64 * W) void k_wp_dec(const double *__restrict__ par, const uint8_t *__restrict__ obs,
                                                      const Chunk *__restrict__ chunks, int t0, const double *__restrict__ X,
                                                      const double *__restrict__ inv, const double *__restrict__ entry,
@@ -175,7 +223,7 @@ __global__ __launch_bounds__(64 * W) void k_wp_dec(const double *__restrict__ pa
                                                      double *__restrict__ post, double *__restrict__ recomb, int32_t *__restrict__ path,
                                                      double *__restrict__ maxp, const int32_t *__restrict__ cnt1, int n_cnt, int j0,
                                                      int min_l, double *__restrict__ part, const double *__restrict__ wts, int n_w,
-                                                     double *__restrict__ mean)
+                                                     double *__restrict__ mean, QuantQ qq, int n_q, int32_t *__restrict__ qstate)
 {
 	constexpr int S = 64 * NPL * W;
 	__shared__ double xs[2 * WX_SLOTS * W];
@@ -202,7 +250,8 @@ __global__ __launch_bounds__(64 * W) void k_wp_dec(const double *__restrict__ pa
 	const uint8_t *o = obs + c.off;
 	const double *fo = X + c.off * S + k0;
 #define WP_EMIT(p, g, r, last) \
-	emit<NPL, W, POST, REC, PATH, CNT, MEAN>(p, tid, n, g, r, last, xc, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc, wt, n_w, mean)
+	emit<NPL, W, POST, REC, PATH, CNT, MEAN, QUANT>(p, tid, n, g, r, last, xc, post, recomb, path, maxp, cnt1, n_cnt, j0, min_l, acc, wt, n_w, mean, \
+	                                                qq, n_q, qstate)
 	if (c.hi == c.L) { // position L: beta_L = 1
 		double g[NPL];
 		if (CKPT) ld<NPL>(xhi + (int64_t)b * S + k0, g); else ld<NPL>(fo + (int64_t)(c.L - 1) * S, g);
@@ -371,20 +420,24 @@ template <int NPL, int W, bool CKPT> static int launch_post(const WidePost &w)
 {
 	const dim3 grid(w.n_tiles), blk(64 * W);
 	hipStream_t st = w.stream;
-#define WP_DEC(POST, REC, PATH, CNT, MEAN, j0) \
-	hipLaunchKernelGGL((k_wp_dec<NPL, W, POST, REC, PATH, CNT, CKPT, MEAN>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.inv, w.entry, w.xhi, \
-	                   w.bentry, w.n_states, w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part, w.wts, w.n_w, w.mean)
+#define WP_DEC(POST, REC, PATH, CNT, MEAN, QUANT, j0) \
+	hipLaunchKernelGGL((k_wp_dec<NPL, W, POST, REC, PATH, CNT, CKPT, MEAN, QUANT>), grid, blk, 0, st, w.par, w.obs, w.chunks, w.t0, w.X, w.inv, w.entry, w.xhi, \
+	                   w.bentry, w.n_states, w.post, w.recomb, w.path, w.maxp, w.cnt1, w.n_cnt, j0, w.min_l, w.part, w.wts, w.n_w, w.mean, w.q, w.n_q, w.qstate)
 	switch (w.what) {
-	case WP_PATH: WP_DEC(false, false, true, false, false, 0); break;
-	case WP_POST: WP_DEC(true, false, false, false, false, 0); break;
-	case WP_REC: WP_DEC(false, true, false, false, false, 0); break;
-	case WP_POST_REC: WP_DEC(true, true, false, false, false, 0); break;
+	case WP_PATH: WP_DEC(false, false, true, false, false, false, 0); break;
+	case WP_POST: WP_DEC(true, false, false, false, false, false, 0); break;
+	case WP_REC: WP_DEC(false, true, false, false, false, false, 0); break;
+	case WP_POST_REC: WP_DEC(true, true, false, false, false, false, 0); break;
 	case WP_MEAN:
 		if (w.n_w < 1 || w.n_w > MEAN_COLS || !w.wts || !w.mean) return -1;
-		WP_DEC(false, false, false, false, true, 0);
+		WP_DEC(false, false, false, false, true, false, 0);
+		break;
+	case WP_QUANT:
+		if (w.n_q < 1 || w.n_q > QUANT_COLS || !w.qstate) return -1;
+		WP_DEC(false, false, false, false, false, true, 0);
 		break;
 	case WP_COUNTS:
-		for (int j0 = 0; j0 < w.n_cnt; j0 += CB) WP_DEC(false, false, false, true, false, j0);
+		for (int j0 = 0; j0 < w.n_cnt; j0 += CB) WP_DEC(false, false, false, true, false, false, j0);
 		if (hipGetLastError() != hipSuccess) return -1;
 		return launch_wide_post_cnt_add(w);
 	case WP_SCALES:

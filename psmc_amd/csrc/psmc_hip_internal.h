@@ -250,6 +250,13 @@ int launch_post_mean_fast(hipStream_t st, const double *f, const double *b, cons
                           int ns, const double *w, int n_w, double *mean); // estep_post_fast.hip
 int launch_post_mean_exact(hipStream_t st, const double *f, const double *b, const double *s, int64_t off, int L, int n, int S,
                            const double *w, int n_w, double *mean);        // estep_post_mean.hip: the exact tables, any width
+// psmc_hip_post_quantile: the thresholds go to the kernels by value (wave-uniform: scalar registers); state is [L][n_q]
+constexpr int QUANT_COLS = 4; // PSMC_HIP_MAX_QUANT_COLS (api_decode.hip asserts it)
+struct QuantQ { double q[QUANT_COLS]; };
+int launch_post_quantile_fast(hipStream_t st, const double *f, const double *b, const double *re, const uint8_t *obs, int64_t off, int L,
+                              int n, int ns, const QuantQ &q, int n_q, int32_t *state); // estep_post_fast.hip
+int launch_post_quantile_exact(hipStream_t st, const double *f, const double *b, const double *s, int64_t off, int L, int n, int S,
+                               const QuantQ &q, int n_q, int32_t *state);               // estep_post_quantile.hip: the exact tables, any width
 // estep_viterbi.hip: psmc_hip_viterbi (api_viterbi.hip).  S = the states padded to a multiple of 64; the log tables are the host's:
 // la [S][S] with la[l * S + k] = log a[l][k] (the transition matrix's own layout, so that consecutive target states k are consecutive
 // doubles), le [3][S], l0 [S], all -inf in the padding (le[2] too: a padded state can never win).

@@ -74,7 +74,7 @@ struct WideGap {
 int launch_wide_gap(const WideGap &w, int what); // estep_wide_gap.hip; -1: ns and waves do not go together
 
 // decoding of ONE segment: its tiles are t0 .. t0 + n_tiles - 1 of the plan; every output pointer is the segment's own buffer
-enum { WP_PATH, WP_POST, WP_REC, WP_POST_REC, WP_COUNTS, WP_SCALES, WP_MEAN };
+enum { WP_PATH, WP_POST, WP_REC, WP_POST_REC, WP_COUNTS, WP_SCALES, WP_MEAN, WP_QUANT };
 
 struct WidePost {
 	hipStream_t stream;
@@ -93,6 +93,8 @@ struct WidePost {
 	double *part, *cnt;               // [n_tiles][n_cnt][ns] per-tile partials; [n_states][n_cnt] running totals (in / out)
 	const double *wts; int n_w;       // WP_MEAN: [n_w][ns] per-state weights, zeros beyond n_states; 1 <= n_w <= MEAN_COLS
 	double *mean;                     // ... and [L][n_w] the posterior means (psmc_hip_post_mean)
+	QuantQ q; int n_q;                // WP_QUANT: the thresholds q_j in [0, 1]; 1 <= n_q <= QUANT_COLS
+	int32_t *qstate;                  // ... and [L][n_q] the states at those posterior quantiles (psmc_hip_post_quantile)
 };
 
 int launch_wide_post(const WidePost &w);         // estep_wide_post.hip; refuses as launch_wide_fast

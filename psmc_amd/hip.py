@@ -28,7 +28,7 @@ EXPORTS = [
     "psmc_hip_last_error", "psmc_hip_set_option", "psmc_hip_load_segments",
     "psmc_hip_load_segments_device", "psmc_hip_select", "psmc_hip_estep",
     "psmc_hip_estep_segments", "psmc_hip_estep_batch", "psmc_hip_estep_batch_cb", "psmc_hip_reserve_batch_tables", "psmc_hip_batch_info", "psmc_hip_estep_device", "psmc_hip_fast_diag", "psmc_hip_fast_repairs", "psmc_hip_fast_info", "psmc_hip_estep_factored",
-    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales", "psmc_hip_post_mean", "psmc_hip_viterbi", "psmc_hip_sample_paths",
+    "psmc_hip_get_tables", "psmc_hip_decode", "psmc_hip_posterior", "psmc_hip_post_counts", "psmc_hip_scales", "psmc_hip_post_mean", "psmc_hip_post_quantile", "psmc_hip_viterbi", "psmc_hip_sample_paths",
     "psmc_hip_group_selfcheck", "psmc_hip_fast_plan",
     "psmc_hip_group_create", "psmc_hip_group_destroy", "psmc_hip_group_last_error", "psmc_hip_group_set_option",
     "psmc_hip_group_load_segments", "psmc_hip_group_estep", "psmc_hip_group_estep_factored", "psmc_hip_group_info",
@@ -514,6 +514,19 @@ class HipEStep:
         self.lib.psmc_hip_post_mean.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int32, _dp]
         self._chk(self.lib.psmc_hip_post_mean(self.h, int(seg), _p(w), w.shape[0], _p(mean)), "post_mean")
         return mean
+
+    def post_quantile(self, seg, q):
+        """state (L, n_q) int32: per bin the 0-based state at the posterior quantiles q of segment `seg` (psmc_hip_post_quantile); q
+        is a scalar or up to four values in [0, 1] -- (0.025, 0.5, 0.975): the median and a 95 % band of the local TMRCA.  The
+        number of states whose running sum of the posterior row lies below q times its total.  Exact tables: bit for bit that
+        count over the rows of posterior(); fast tables: within the guarantees of include/psmc_hip.h."""
+        q = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        assert q.ndim == 1, q.shape
+        L = int(self.lens[seg])
+        state = np.zeros((L, max(q.shape[0], 1)), dtype=np.int32)
+        self.lib.psmc_hip_post_quantile.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int32, _i32p]
+        self._chk(self.lib.psmc_hip_post_quantile(self.h, int(seg), _p(q), q.shape[0], state.ctypes.data_as(_i32p)), "post_quantile")
+        return state
 
     def viterbi(self, a, e, a0, want_path=True):
         """(paths, scores): the Viterbi path of every loaded segment in load order (a list of int32 arrays) and hmm_Viterbi's

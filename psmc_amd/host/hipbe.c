@@ -209,6 +209,7 @@ static int hb_posterior(void *self, int seg, double *post, double *recomb) { HB_
 static int hb_post_counts(void *self, int seg, const int32_t *cnt1, int32_t l1, int32_t n_cnt, double *cnt) { HB_DECODE_CALL(psmc_hip_post_counts(c, l, cnt1, l1, n_cnt, cnt)) }
 static int hb_scales(void *self, int seg, double *s) { HB_DECODE_CALL(psmc_hip_scales(c, l, s)) }
 static int hb_post_mean(void *self, int seg, const double *w, int32_t n_w, double *mean) { HB_DECODE_CALL(psmc_hip_post_mean(c, l, w, n_w, mean)) }
+static int hb_post_quantile(void *self, int seg, const double *q, int32_t n_q, int32_t *state) { HB_DECODE_CALL(psmc_hip_post_quantile(c, l, q, n_q, state)) }
 #undef HB_DECODE_CALL
 /* The Viterbi path of all segments in input order.  One context: psmc_hip_viterbi as it is.  A group: one call per shard context
  * (psmc_hip_group_route names every segment's context and its index there), the shard's results scattered to input order.  The call
@@ -343,7 +344,7 @@ int psmc_hipbe_create(psmc_estep_backend *be, int n_states, int mode, int use_fa
 	be->self = h; be->load = hb_load; be->estep = hb_estep; be->tables = hb_tables; be->decode = hb_decode;
 	be->estep_factored = use_factored ? hb_estep_factored : 0; be->error = hb_error; be->destroy = hb_destroy;
 	be->posterior = hb_posterior; be->post_counts = hb_post_counts; be->prepare_decode = hb_prepare_decode; be->scales = hb_scales;
-	be->post_mean = hb_post_mean; be->viterbi = hb_viterbi; be->sample_paths = hb_sample_paths;
+	be->post_mean = hb_post_mean; be->post_quantile = hb_post_quantile; be->viterbi = hb_viterbi; be->sample_paths = hb_sample_paths;
 	return 0;
 }
 

@@ -121,6 +121,11 @@ typedef struct psmc_estep_backend {
 	 * psmc_sample_host */
 	int  (*sample_paths)(void *self, const double *a, const double *e, const double *a0, uint64_t seed, int32_t n_samp,
 	                     const uint64_t *stream, int32_t *path);
+	/* optional (may be NULL; last, so that an aggregate initialiser without it says no): per bin the 0-based state at n_q <= 4 posterior
+	 * quantiles q[j] in [0, 1] of one segment, state[(u-1)*n_q + j] = min(n-1, #{k : c_k < q[j] * c_{n-1}}) over the running sums c of
+	 * the posterior row (psmc_hip_post_quantile; the PSMC_TMRCA_BAND track).  A backend without it gets the host's loop over its
+	 * posterior rows or its tables */
+	int  (*post_quantile)(void *self, int seg, const double *q, int32_t n_q, int32_t *state);
 } psmc_estep_backend;
 /* the dense Viterbi recursion on the host, one segment: log tables by libm's log(), every candidate one addition, the first maximum
  * wins (the arithmetic include/psmc_hip.h pins).  path[L], *score; returns 0, 1 = no path of finite probability, 2 = out of memory */
