@@ -11,7 +11,7 @@ from test_gpu_viterbi import DEFAULT_TILE, TILES, banded_hmm, block_data, ctx, s
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = [1, 2, 3, 23, 63, 64, 65, 128, 129, 192, 193, 256, 257, 512, 513, 1024]
+WIDTHS = [1, 2, 3, 23, 63, 64, 65, 127, 128, 129, 192, 193, 224, 225, 256, 257, 512, 513, 1024]
 SEED = 20261020
 N_SAMP = 3
 

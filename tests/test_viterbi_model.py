@@ -1,5 +1,6 @@
 """The numpy restatement of the Viterbi arithmetic (tests/viterbi_model.py) against the reference's hmm_Viterbi: every
-golden of tests/golden/viterbi.npz bit for bit, and -- where oracle/_ref is built -- the live reference on a fresh case."""
+golden of tests/golden/viterbi.npz and of tests/golden/viterbi_extremes.npz (the extreme PSMC models at 64, 65 and 200 states) bit
+for bit, and -- where oracle/_ref is built -- the live reference on a fresh case."""
 import os
 import sys
 import numpy as np
@@ -44,6 +45,65 @@ def test_model_reproduces_goldens(gold, name):
         assert np.float64(score).view(np.uint64) == gold["%s.%s.score" % (name, sname)].view(np.uint64), (name, sname)
         n_runs = max(n_runs, len(vm.runs(path)))
     assert n_runs >= 4  # the goldens are paths, not constants
+
+
+def extreme_cases():
+    """[(case, n, model)] of tests/golden/viterbi_extremes.npz, from the file's own list"""
+    cases = [str(c) for c in np.load(os.path.join(GOLD, "viterbi_extremes.npz"))["cases"]]
+    return [(c, int(c.split(".", 1)[0][1:]), c.split(".", 1)[1]) for c in cases]
+
+
+def extreme_golden(gold_x, case, segs):
+    """(paths [int16 views of the file's array], scores) of one case, cut by the segments' lengths"""
+    path, score = gold_x[case + ".path"], gold_x[case + ".score"]
+    ends = np.cumsum([len(s) for s in segs.values()])
+    assert path.dtype == np.int16 and len(path) == ends[-1] and score.shape == (len(segs),) and score.dtype == np.float64
+    return [path[end - len(s):end] for end, s in zip(ends, segs.values())], score
+
+
+def test_extreme_goldens_are_the_expected_cases():
+    """11 of the 13 models at each of 64, 65 and 200 states: all but the two whose matrix holds NaN, on which the reference's assert fires"""
+    import path_extremes as px
+    gold_x = np.load(os.path.join(GOLD, "viterbi_extremes.npz"))
+    want = ["n%d.%s" % (n, name) for n in px.GOLDEN_SIZES for name in px.model_names() if name not in px.NAN_MODELS]
+    assert [c for c, _, _ in extreme_cases()] == want and len(want) == 33
+    assert [str(s) for s in gold_x["segments"]] == list(px.golden_segments())
+    segs = px.golden_segments()
+    for n in px.GOLDEN_SIZES:   # the goldens are paths, not constants
+        n_runs = {name: len(vm.runs(extreme_golden(gold_x, "n%d.%s" % (n, name), segs)[0][-1])) for c, m, name in extreme_cases() if m == n}
+        assert sum(r >= 4 for r in n_runs.values()) >= 8 and all(r >= 2 for name, r in n_runs.items() if name != "tmax_0.5"), n_runs
+
+
+@pytest.mark.parametrize("case,n,name", extreme_cases())
+def test_model_reproduces_extreme_goldens(case, n, name):
+    """The restatement against the real hmm_Viterbi at the model extremes, paths and score bits, as the goldens stand.  rho_0.5 has
+    negative entries in a: libm's log gives NaN there, viterbi_model._log gives -inf, and the golden -- made with libm's NaN -- is
+    reproduced all the same: neither a NaN candidate nor a -inf one ever passes `m < c`."""
+    import path_extremes as px
+    a, e, a0 = px.extreme_model(name, n)
+    if name == "rho_0.5":
+        assert (a < 0).any() and np.isfinite(a).all()
+    gold_x = np.load(os.path.join(GOLD, "viterbi_extremes.npz"))
+    segs = px.golden_segments()
+    want_paths, want_scores = extreme_golden(gold_x, case, segs)
+    tables = vm.log_tables(a, e, a0)
+    for i, (sname, seq) in enumerate(segs.items()):
+        path, score = vm.viterbi(tables, seq)
+        assert np.array_equal(path, want_paths[i]), (case, sname)
+        assert np.float64(score).view(np.uint64) == want_scores[i].view(np.uint64), (case, sname)
+
+
+@pytest.mark.parametrize("n", [64, 65, 200])
+def test_nan_models_have_no_finite_path(n):
+    """the two cases per size the goldens leave out: no state at position 2 has a predecessor (a segment of one bin still has a path)"""
+    import path_extremes as px
+    for name in px.NAN_MODELS:
+        a, e, a0 = px.extreme_model(name, n)
+        assert np.isnan(a).any()
+        tables = vm.log_tables(a, e, a0)
+        with pytest.raises(vm.NoFinitePath, match="position 2"):
+            vm.viterbi(tables, np.array([0, 0, 1, 0], dtype=np.uint8))
+        vm.viterbi(tables, np.array([0], dtype=np.uint8))
 
 
 def test_no_finite_path_raises():
