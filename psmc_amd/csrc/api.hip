@@ -96,11 +96,10 @@ extern "C" int psmc_hip_create(psmc_hip_ctx **out, int n_states, int device, int
 	c->par_len = c->ns > 128 ? 2 * (size_t)c->ns * c->ns + 4 * (size_t)c->ns : psmc_hip_ctx::PAR_LEN;
 	if (make_streams(c) != 0) { psmc_hip_destroy(c); return PSMC_HIP_EDEVICE; }
 	for (int i = 0; i < 14; ++i)
-		if (hipEventCreate(&c->evx[i]) != hipSuccess) { delete c; return PSMC_HIP_EDEVICE; }
+		if (hipEventCreate(&c->evx[i]) != hipSuccess) { psmc_hip_destroy(c); return PSMC_HIP_EDEVICE; }
 	for (int i = 0; i < 10; ++i)
-		if (hipEventCreate(&c->ev[i]) != hipSuccess) { delete c; return PSMC_HIP_EDEVICE; }
-	if (hipHostMalloc((void **)&c->h_par, c->par_len * sizeof(double), hipHostMallocDefault) != hipSuccess ||
-	    hipMalloc((void **)&c->d_par, c->par_len * sizeof(double)) != hipSuccess) {
+		if (hipEventCreate(&c->ev[i]) != hipSuccess) { psmc_hip_destroy(c); return PSMC_HIP_EDEVICE; }
+	if (c->h_par.try_alloc(c->par_len) != hipSuccess || c->d_par.try_alloc(c->par_len) != hipSuccess) { // (as ever: no poison fill of the parameter block)
 		psmc_hip_destroy(c);
 		return PSMC_HIP_ENOMEM;
 	}
@@ -140,54 +139,16 @@ static void destroy_kids(psmc_hip_ctx *c)
 	c->share_T = 0; // the shared learning goes with the plans it was made for
 }
 
+// What a context holds releases itself (psmc_hip_ctx.h): the buffers it owns, then -- a root context -- its events and streams.  A batch
+// child owns its plan and borrows the rest from its parent: psmc_hip_opts is copied; the streams and events, h_par, d_par and d_obs
+// are borrowed in batch_child (api_batch.hip), d_f, d_b, d_s and d_sb in ensure_tables; the exact twin borrows d_obs.
 extern "C" void psmc_hip_destroy(psmc_hip_ctx *c)
 {
 	if (!c) return;
 	(void)hipSetDevice(c->device);
 	destroy_kids(c);
-	if (c->parent) { // a batch child owns its plan only: streams, events, staging, observations and tables are the parent's
-		// (d_seg*: a child that took the exact fallback of psmc_hip_estep -- 65..128 states, a matrix without the PSMC form)
-		void *mine[] = {c->d_seg_off, c->d_seg_len, c->d_work, c->d_chunks, c->d_entry, c->d_bexit, c->d_Cpart, c->d_Epart, c->d_LLpart,
-		                c->d_stage, c->d_stats, c->d_warm, c->d_bentry, c->d_dirty, c->d_cnt, c->d_gate, c->d_queue, c->d_touch, c->d_items, c->d_ftiles, c->d_Kcol,
-		                c->d_segA, c->d_segE, c->d_segA0, c->d_chk};
-		for (void *p : mine) if (p) (void)hipFree(p);
-		if (c->h_cnt) (void)hipHostFree(c->h_cnt);
-		if (c->h_ritems) (void)hipHostFree(c->h_ritems);
-		if (c->h_mlen) (void)hipHostFree(c->h_mlen);
-		if (c->h_chunks) (void)hipHostFree(c->h_chunks);
-		if (c->h_mis) (void)hipHostFree(c->h_mis);
-		if (c->d_prevx) (void)hipFree(c->d_prevx);
-		if (c->d_finv) (void)hipFree(c->d_finv);
-		delete c;
-		return;
-	}
-	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	free_wide_fast(c);
-	if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-	if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-	if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-	if (c->stream5) (void)hipStreamSynchronize(c->stream5);
-	if (!c->obs_borrowed && c->d_obs) (void)hipFree(c->d_obs);
-	void *ptrs[] = {c->d_seg_off, c->d_seg_len, c->d_work, c->d_par, c->d_f, c->d_b, c->d_s, c->d_segA, c->d_segE,
-	                c->d_segA0, c->d_chk, c->d_chunks, c->d_entry, c->d_bexit, c->d_Cpart, c->d_Epart, c->d_LLpart,
-	                c->d_stage, c->d_stats, c->d_warm, c->d_bentry, c->d_dirty, c->d_cnt, c->d_gate, c->d_queue, c->d_touch, c->d_sb, c->d_items, c->d_ftiles, c->d_Kcol,
-	                c->d_bw_seg, c->d_bw_par, c->d_bw_tab, c->d_bpar, c->d_s_all, c->d_cu_mask, c->d_lkp, c->d_lkoff, c->d_b2};
-	for (void *p : ptrs) if (p) (void)hipFree(p);
-	if (c->h_par) (void)hipHostFree(c->h_par);
-	if (c->h_cnt) (void)hipHostFree(c->h_cnt);
-	if (c->h_ritems) (void)hipHostFree(c->h_ritems);
-	if (c->h_mlen) (void)hipHostFree(c->h_mlen);
-	if (c->h_chunks) (void)hipHostFree(c->h_chunks);
-	if (c->h_mis) (void)hipHostFree(c->h_mis);
-	if (c->d_prevx) (void)hipFree(c->d_prevx);
-	if (c->d_finv) (void)hipFree(c->d_finv);
-	for (int i = 0; i < 10; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-	for (int i = 0; i < 14; ++i) if (c->evx[i]) (void)hipEventDestroy(c->evx[i]);
-	if (c->stream4) (void)hipStreamDestroy(c->stream4);
-	if (c->stream5) (void)hipStreamDestroy(c->stream5);
-	if (c->stream2) (void)hipStreamDestroy(c->stream2);
-	if (c->stream3) (void)hipStreamDestroy(c->stream3);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
+	if (c->runtime_owned)
+		for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream4, c->stream5}) if (st) (void)hipStreamSynchronize(st);
 	delete c;
 }
 
@@ -225,7 +186,7 @@ extern "C" int psmc_hip_set_option(psmc_hip_ctx *c, const char *key, double v)
 	else if (k == "fuse128") { if (v != 0 && v != 2) return PSMC_HIP_EINVAL; c->fuse128 = (int)v; c->plan_dirty = true; c->items_dirty = true; }
 	else if (k == "group_cap") { if (v < 0) return PSMC_HIP_EINVAL; c->group_cap = (int)v; c->items_dirty = true; }
 	else if (k == "share_learn") { c->share_learn = v != 0 ? 1 : 0; }
-	else if (k == "exact_refwd") { if (v < -1 || v > 2) return PSMC_HIP_EINVAL; c->exact_refwd = (int)v; c->reserved_refwd = -1; c->reserved_cap = 0; if (c->d_b2) { (void)hipFree(c->d_b2); c->d_b2 = nullptr; c->b2_bins = c->b2_alloc = 0; } }
+	else if (k == "exact_refwd") { if (v < -1 || v > 2) return PSMC_HIP_EINVAL; c->exact_refwd = (int)v; c->reserved_refwd = -1; c->reserved_cap = 0; c->d_b2.reset(); c->b2_bins = c->b2_alloc = 0; }
 	else if (k == "batch_sort") { c->batch_sort = v != 0 ? 1 : 0; }
 	else if (k == "batch_tailfill") c->batch_tailfill = v != 0;
 	else if (k == "batch_major") c->batch_major = v != 0;
@@ -255,12 +216,12 @@ int set_segments_common(psmc_hip_ctx *c, int n_seg, const int32_t *L)
 {
 	destroy_kids(c); // batch children hold plans over the previous segments
 	c->reserved_refwd = -1; c->reserved_cap = 0;
-	if (c->d_b2) { (void)hipFree(c->d_b2); c->d_b2 = nullptr; c->b2_bins = c->b2_alloc = 0; }
+	c->d_b2.reset(); c->b2_bins = c->b2_alloc = 0;
 	c->n_seg = n_seg;
 	c->L.assign(L, L + n_seg);
 	int rc;
-	if ((rc = dev_alloc(c, &c->d_seg_off, (size_t)n_seg))) return rc;
-	if ((rc = dev_alloc(c, &c->d_seg_len, (size_t)n_seg))) return rc;
+	if ((rc = c->d_seg_off.alloc(c, (size_t)n_seg))) return rc;
+	if ((rc = c->d_seg_len.alloc(c, (size_t)n_seg))) return rc;
 	HIPCHK(c, hipMemcpy(c->d_seg_off, c->off.data(), sizeof(int64_t) * n_seg, hipMemcpyHostToDevice));
 	HIPCHK(c, hipMemcpy(c->d_seg_len, c->L.data(), sizeof(int32_t) * n_seg, hipMemcpyHostToDevice));
 	std::vector<int32_t> all(n_seg);
@@ -286,10 +247,8 @@ extern "C" int psmc_hip_load_segments(psmc_hip_ctx *c, int n_seg, const uint8_t 
 			if (seq[i][j] > 2) return fail(c, PSMC_HIP_EINVAL, "load_segments: symbol outside {0,1,2}");
 		memcpy(host.data() + c->off[i], seq[i], (size_t)L[i]);
 	}
-	if (!c->obs_borrowed && c->d_obs) { (void)hipFree(c->d_obs); }
-	c->d_obs = nullptr; c->obs_borrowed = false;
 	int rc;
-	if ((rc = dev_alloc(c, &c->d_obs, host.size()))) return rc;
+	if ((rc = c->d_obs.alloc(c, host.size()))) return rc;
 	HIPCHK(c, hipMemcpy(c->d_obs, host.data(), host.size(), hipMemcpyHostToDevice));
 	return set_segments_common(c, n_seg, L);
 }
@@ -304,8 +263,7 @@ extern "C" int psmc_hip_load_segments_device(psmc_hip_ctx *c, int n_seg, const v
 		if (L[i] < 1 || (off[i] & 63) || off[i] < end) return fail(c, PSMC_HIP_EINVAL, "load_segments_device: bad layout");
 		end = off[i] + (((int64_t)L[i] + 63) & ~(int64_t)63);
 	}
-	if (!c->obs_borrowed && c->d_obs) (void)hipFree(c->d_obs);
-	c->d_obs = (uint8_t *)d_obs; c->obs_borrowed = true;
+	c->d_obs.borrow((uint8_t *)d_obs);
 	c->off.assign(off, off + n_seg);
 	c->total = end;
 	return set_segments_common(c, n_seg, L);
@@ -326,7 +284,7 @@ extern "C" int psmc_hip_select(psmc_hip_ctx *c, int n_sel, const int32_t *idx)
 	}
 	HIPCHK(c, hipSetDevice(c->device));
 	int rc;
-	if ((rc = dev_alloc(c, &c->d_work, c->work.size()))) return rc;
+	if ((rc = c->d_work.alloc(c, c->work.size()))) return rc;
 	HIPCHK(c, hipMemcpy(c->d_work, c->work.data(), sizeof(int32_t) * c->work.size(), hipMemcpyHostToDevice));
 	c->plan_dirty = true;
 	++c->sel_serial;
@@ -446,19 +404,18 @@ static int ensure_tables_once(psmc_hip_ctx *c, bool need_b, int64_t bins, bool n
 {
 	int rc;
 	if (c->tab_bins < bins) { // grow: everything goes, and comes back as needed
-		if (c->d_f) { (void)hipFree(c->d_f); c->d_f = nullptr; }
-		if (c->d_b) { (void)hipFree(c->d_b); c->d_b = nullptr; }
-		if (c->d_b2) { (void)hipFree(c->d_b2); c->d_b2 = nullptr; c->b2_bins = c->b2_alloc = 0; c->reserved_cap = 0; }
+		c->d_f.reset(); c->d_b.reset();
+		if (c->d_b2) { c->d_b2.reset(); c->b2_bins = c->b2_alloc = 0; c->reserved_cap = 0; }
 		c->have_b = false;
-		if ((rc = dev_alloc(c, &c->d_s, (size_t)bins))) { c->tab_bins = 0; return rc; }
-		if (c->mode == PSMC_HIP_MODE_FAST && (rc = dev_alloc(c, &c->d_sb, (size_t)bins))) { c->tab_bins = 0; return rc; }
+		if ((rc = c->d_s.alloc(c, (size_t)bins))) { c->tab_bins = 0; return rc; }
+		if (c->mode == PSMC_HIP_MODE_FAST && (rc = c->d_sb.alloc(c, (size_t)bins))) { c->tab_bins = 0; return rc; }
 		c->tab_bins = bins;
 	}
 	// the exact batch with the recomputed forward sweep keeps no f table: give its memory to the replicates
-	if (!need_f && c->d_f) { (void)hipFree(c->d_f); c->d_f = nullptr; }
-	if (need_f && !c->d_f && (rc = dev_alloc(c, &c->d_f, (size_t)c->tab_bins * c->ns))) return rc;
+	if (!need_f) c->d_f.reset();
+	if (need_f && !c->d_f && (rc = c->d_f.alloc(c, (size_t)c->tab_bins * c->ns))) return rc;
 	if (need_b && !c->have_b) {
-		if ((rc = dev_alloc(c, &c->d_b, (size_t)c->tab_bins * c->ns))) return rc;
+		if ((rc = c->d_b.alloc(c, (size_t)c->tab_bins * c->ns))) return rc;
 		c->have_b = true;
 	}
 	return 0;
@@ -468,7 +425,7 @@ int ensure_tables(psmc_hip_ctx *c, bool need_b, int64_t want_bins, bool need_f)
 {
 	if (c->parent) { // a batch child works in its parent's tables (same segments, one E-step at a time)
 		int rc = ensure_tables(c->parent, need_b);
-		c->d_f = c->parent->d_f; c->d_b = c->parent->d_b; c->d_s = c->parent->d_s; c->d_sb = c->parent->d_sb;
+		c->d_f.borrow(c->parent->d_f); c->d_b.borrow(c->parent->d_b); c->d_s.borrow(c->parent->d_s); c->d_sb.borrow(c->parent->d_sb);
 		c->tab_bins = c->parent->tab_bins; c->have_b = c->parent->have_b;
 		return rc;
 	}
@@ -479,11 +436,8 @@ int ensure_tables(psmc_hip_ctx *c, bool need_b, int64_t want_bins, bool need_f)
 		// The tables were sized for another layout -- an exact batch without the f table holds twice the bins of one with it -- and the
 		// table this call adds does not fit beside them at that size (a single E-step, decode or get_tables after such a
 		// batch).  Start over at what THIS call needs.
-		if (c->d_f) { (void)hipFree(c->d_f); c->d_f = nullptr; }
-		if (c->d_b) { (void)hipFree(c->d_b); c->d_b = nullptr; }
-		if (c->d_b2) { (void)hipFree(c->d_b2); c->d_b2 = nullptr; c->b2_bins = c->b2_alloc = 0; }
-		if (c->d_s) { (void)hipFree(c->d_s); c->d_s = nullptr; }
-		if (c->d_sb) { (void)hipFree(c->d_sb); c->d_sb = nullptr; }
+		c->d_f.reset(); c->d_b.reset(); c->d_s.reset(); c->d_sb.reset();
+		c->d_b2.reset(); c->b2_bins = c->b2_alloc = 0;
 		c->have_b = false; c->tab_bins = 0; c->reserved_refwd = -1; c->reserved_cap = 0;
 		(void)hipGetLastError();
 		rc = ensure_tables_once(c, need_b, bins, need_f);
@@ -583,10 +537,10 @@ int ensure_seg_outputs(psmc_hip_ctx *c, int nw)
 	if (c->seg_cap >= nw) return 0;
 	const size_t S = (size_t)c->ns;
 	int rc;
-	if ((rc = dev_alloc(c, &c->d_segA, (size_t)nw * S * S))) return rc;
-	if ((rc = dev_alloc(c, &c->d_segE, (size_t)nw * 3 * S))) return rc;
-	if ((rc = dev_alloc(c, &c->d_segA0, (size_t)nw * S))) return rc;
-	if ((rc = dev_alloc(c, &c->d_chk, (size_t)nw))) return rc;
+	if ((rc = c->d_segA.alloc(c, (size_t)nw * S * S))) return rc;
+	if ((rc = c->d_segE.alloc(c, (size_t)nw * 3 * S))) return rc;
+	if ((rc = c->d_segA0.alloc(c, (size_t)nw * S))) return rc;
+	if ((rc = c->d_chk.alloc(c, (size_t)nw))) return rc;
 	c->seg_cap = nw;
 	return 0;
 }

@@ -46,7 +46,7 @@ static int batch_capacity(psmc_hip_ctx *c, int64_t *cap, bool refwd, int64_t all
 	const double held = (double)c->tab_bins * (S * 8.0 * ((c->have_b ? 1.0 : 0.0) + (c->d_f ? 1.0 : 0.0)) + 8.0 + (c->d_sb ? 8.0 : 0.0)) + (double)c->b2_alloc * S * 8.0;
 	// (the call-wide scale-factor table stays allocated between calls: count it as free, or the second call would see a smaller
 	// capacity than the first and cut other launches)
-	double budget = ((double)fr + held + (double)c->s_all_cap * 8.0) * 0.9;
+	double budget = ((double)fr + held + (double)c->d_s_all.cap * 8.0) * 0.9;
 	*cap = (int64_t)(budget / per_bin) - 256;
 	if (refwd && (all_bins <= 0 || all_bins > *cap)) { // several launches: room for the call-wide scale factors
 		const double s_all = all_bins > 0 ? (double)all_bins * 8.0 : budget / 65.0; // unknown size: what four launches need
@@ -98,21 +98,20 @@ extern "C" int psmc_hip_reserve_batch_tables(psmc_hip_ctx *c, int64_t max_bins)
 		int64_t extra = (int64_t)((double)fr * 0.9 / ((double)c->ns * 8.0)) - slack - 256;
 		if (max_bins > 0) extra = std::min(extra, max_bins - cap1);
 		if (extra < std::max<int64_t>(4096, cap1 / 64)) return PSMC_HIP_OK; // (not worth a launch)
-		double *p2 = nullptr;
-		if (hipMalloc((void **)&p2, (size_t)(extra + slack + 8) * c->ns * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return PSMC_HIP_OK; } // (as before, then)
-		c->d_b2 = p2; c->b2_alloc = extra + slack + 8; c->b2_bins = extra + slack;
+		if (c->d_b2.try_alloc((size_t)(extra + slack + 8) * c->ns) != hipSuccess) { (void)hipGetLastError(); return PSMC_HIP_OK; } // (as before, then)
+		c->b2_alloc = extra + slack + 8; c->b2_bins = extra + slack;
 		c->reserved_cap = cap1 + extra;
 		return PSMC_HIP_OK;
 	}
 	int64_t cap = 0;
 	bool refwd = false;
 	c->reserved_refwd = -1; c->reserved_cap = 0;
-	if (c->d_b2) { (void)hipFree(c->d_b2); c->d_b2 = nullptr; c->b2_bins = c->b2_alloc = 0; } // a new reservation starts from one chunk
+	c->d_b2.reset(); c->b2_bins = c->b2_alloc = 0; // a new reservation starts from one chunk
 	int rc = batch_refwd(c, max_bins, &refwd);
 	if (rc || (rc = batch_capacity(c, &cap, refwd, max_bins))) return rc;
 	rc = ensure_tables(c, true, max_bins > 0 ? std::min(cap, max_bins) : cap, !refwd);
 	// (several launches without the f table: the call-wide scale factors -- 15 GB for 100 replicates of a genome -- now as well, not inside the first EM iteration)
-	if (rc == 0 && refwd && max_bins > cap && c->s_all_cap < (size_t)max_bins + 128 && (rc = dev_alloc(c, &c->d_s_all, (size_t)max_bins + 128)) == 0) c->s_all_cap = (size_t)max_bins + 128;
+	if (rc == 0 && refwd && max_bins > cap) rc = c->d_s_all.grow(c, (size_t)max_bins + 128);
 	if (rc == 0) {
 		if (c->exact_refwd < 0) c->reserved_refwd = refwd ? 1 : 0; // (a fixed "exact_refwd" needs no memory)
 		c->reserved_cap = cap; // the batches that follow plan their launches for THIS capacity: a second estimate from a different bound
@@ -276,7 +275,7 @@ static int batch_exact(psmc_hip_ctx *c, int n_rep, const double *a, const double
 		const int64_t row = (int64_t)S * 8, cap1 = two ? c->tab_bins - 128 : INT64_MAX;
 		int64_t delta2 = 0, cap2 = 0;
 		if (two) {
-			const int64_t diff = (int64_t)((intptr_t)c->d_b2 - (intptr_t)c->d_b), skew = ((diff % row) + row) % row, shift = (row - skew) % row;
+			const int64_t diff = (int64_t)((intptr_t)c->d_b2.p - (intptr_t)c->d_b.p), skew = ((diff % row) + row) % row, shift = (row - skew) % row;
 			delta2 = (diff + shift) / row; cap2 = c->b2_bins - (shift ? 1 : 0);
 		}
 		int64_t s_run = 0;
@@ -315,13 +314,13 @@ static int batch_exact(psmc_hip_ctx *c, int n_rep, const double *a, const double
 		if ((rc = ensure_tables(c, true, c->d_b2 ? std::min<int64_t>(worst, c->tab_bins - 128) : (c->batch_bins > 0 ? worst : std::max(worst, std::min(cap, all_bins))), !refwd))) return rc;
 		if ((rc = ensure_seg_outputs(c, (int)worst_entries))) return rc;
 		if (c->bw_cap < (size_t)n_all) {
-			if ((rc = dev_alloc(c, &c->d_bw_seg, (size_t)n_all))) return rc;
-			if ((rc = dev_alloc(c, &c->d_bw_par, (size_t)n_all))) return rc;
-			if ((rc = dev_alloc(c, &c->d_bw_tab, (size_t)2 * n_all))) return rc; // tables | scale factors
+			if ((rc = c->d_bw_seg.alloc(c, (size_t)n_all))) return rc;
+			if ((rc = c->d_bw_par.alloc(c, (size_t)n_all))) return rc;
+			if ((rc = c->d_bw_tab.alloc(c, (size_t)2 * n_all))) return rc; // tables | scale factors
 			c->bw_cap = (size_t)n_all;
 		}
-		if (c->bpar_cap < (size_t)n_rep) { if ((rc = dev_alloc(c, &c->d_bpar, (size_t)n_rep * PL))) return rc; c->bpar_cap = (size_t)n_rep; }
-		if (refwd && !c->d_cu_mask && (rc = dev_alloc(c, &c->d_cu_mask, (size_t)4096))) return rc;
+		if ((rc = c->d_bpar.grow(c, (size_t)n_rep * PL))) return rc;
+		if (refwd && !c->d_cu_mask && (rc = c->d_cu_mask.alloc(c, (size_t)4096))) return rc;
 		// (hmm_lk's products and their offsets for the LARGEST launch, here: growing them between two launches frees the old buffer, and hipFree
 		// waits for every kernel on the device -- beside psmc_boot's main run that was its 3.3 s E-step: 2.66 s of "read-back" in launch 1)
 		size_t lk_worst = 0;
@@ -330,9 +329,8 @@ static int batch_exact(psmc_hip_ctx *c, int n_rep, const double *a, const double
 			for (int i = l_first[g]; i < l_first[g + 1]; ++i) t += wseg[i] >= 0 ? (size_t)(c->L[wseg[i]] / LKP_DIV + LKP_MIN) : 1;
 			lk_worst = std::max(lk_worst, t);
 		}
-		if (c->lkp_cap < lk_worst) { if ((rc = dev_alloc(c, &c->d_lkp, lk_worst))) return rc; c->lkp_cap = lk_worst; }
-		if (c->lkoff_cap < worst_entries) { if ((rc = dev_alloc(c, &c->d_lkoff, worst_entries))) return rc; c->lkoff_cap = worst_entries; }
-		if (fwd_all && c->s_all_cap < (size_t)all_bins + 128) { if ((rc = dev_alloc(c, &c->d_s_all, (size_t)all_bins + 128))) return rc; c->s_all_cap = (size_t)all_bins + 128; }
+		if ((rc = c->d_lkp.grow(c, lk_worst)) || (rc = c->d_lkoff.grow(c, worst_entries))) return rc;
+		if (fwd_all && (rc = c->d_s_all.grow(c, (size_t)all_bins + 128))) return rc;
 	}
 	static const bool dbg_t = getenv("PSMC_HIP_DEBUG_TIMES") != nullptr;
 	auto now = []() { return dbg_now(); };
@@ -481,23 +479,14 @@ static psmc_hip_ctx *batch_child(psmc_hip_ctx *c, int r)
 	while ((int)c->kids.size() <= r) { // (positions below r that no call has named yet get their context too: unselected, no tables of their own)
 		psmc_hip_ctx *k = new (std::nothrow) psmc_hip_ctx();
 		if (!k) return nullptr;
-		k->n = c->n; k->ns = c->ns; k->device = c->device; k->mode = c->mode; k->parent = c;
-		k->chunk = c->chunk > 0 ? c->chunk : c->share_T; // (share_T = 0 without "share_learn": its own tiling)
-		k->warmup = c->warmup; k->max_rounds = c->max_rounds; k->rep_impl = c->rep_impl;
-		k->n_sub = c->n_sub; k->target_waves = c->target_waves; k->overlap = c->overlap; k->warm_tol = c->warm_tol; k->struct_opt = c->struct_opt;
-		k->struct_tiles_set = c->struct_tiles_set; k->struct_tiles = c->struct_tiles;
-		k->two_phase = c->two_phase; k->kc_div = c->kc_div; k->kc_min = c->kc_min; k->ckpt = c->ckpt; k->fuse = c->fuse;
-		k->learn = c->learn; k->group_cap = c->group_cap; k->warm_shift = c->warm_shift; k->kc_sub = c->kc_sub; k->kcol_prio = c->kcol_prio;
-		k->fuse128 = c->fuse128; k->coarse = c->coarse; k->gate = c->gate; k->lanes8 = c->lanes8; k->gap_tiles = c->gap_tiles; k->hom_tiles = c->hom_tiles; k->hom_min = c->hom_min; k->exact_refwd = c->exact_refwd;
-		k->merge = c->merge; k->adapt = c->adapt; k->prev_start = c->prev_start;
-		k->tail = 0; // (the replicates of a batch keep the plain tail)
-		k->merge1 = c->merge1; k->merge_order = c->merge_order; k->runs_late = c->runs_late; k->warm_shift_set = c->warm_shift_set; k->kc_sub_set = c->kc_sub_set;
-		k->stream = c->stream; k->stream2 = c->stream2; k->stream3 = c->stream3; k->stream4 = c->stream4; k->stream5 = c->stream5;
-		for (int i = 0; i < 14; ++i) k->evx[i] = c->evx[i];
-		for (int i = 0; i < 10; ++i) k->ev[i] = c->ev[i];
-		k->h_par = c->h_par; k->d_par = c->d_par; k->par_len = c->par_len;
-		// same segments, same offsets, the parent's copy of the observations
-		k->d_obs = c->d_obs; k->obs_borrowed = true; k->off = c->off; k->total = c->total;
+		k->n = c->n; k->ns = c->ns; k->device = c->device; k->mode = c->mode; k->parent = c; k->par_len = c->par_len;
+		static_cast<psmc_hip_opts &>(*k) = *c; // every option a replicate inherits, but for:
+		k->chunk = c->chunk > 0 ? c->chunk : c->share_T; // the batch's shared tile length (share_T = 0 without "share_learn": its own tiling)
+		k->tail = 0; // the replicates of a batch keep the plain tail
+		// borrowed from the parent: streams and events, the parameter staging, and -- same segments, same offsets -- the observations
+		k->borrow_runtime(*c);
+		k->h_par.borrow(c->h_par); k->d_par.borrow(c->d_par);
+		k->d_obs.borrow(c->d_obs); k->off = c->off; k->total = c->total;
 		if (set_segments_common(k, c->n_seg, c->L.data()) != 0) { c->err = k->err; psmc_hip_destroy(k); return nullptr; } // never keep a half-built child
 		c->kids.push_back(k);
 	}

@@ -66,23 +66,6 @@ static int decode_source(psmc_hip_ctx *c, int seg, const char *who, int *first_t
 	return fail(c, PSMC_HIP_ESTATE, msg);
 }
 
-// Device scratch of one decoding call, freed when the call returns.  Plain hipMalloc, not dev_alloc: no poison fill and no device
-// synchronise.  After a failed get() the later ones allocate nothing; the caller checks ok once.
-namespace {
-struct Scratch {
-	std::vector<void *> bufs;
-	bool ok = true;
-	~Scratch() { for (void *p : bufs) (void)hipFree(p); }
-	template <class T> T *get(size_t n)
-	{
-		void *p = nullptr;
-		if (!ok || hipMalloc(&p, sizeof(T) * n) != hipSuccess) { ok = false; return nullptr; }
-		bufs.push_back(p);
-		return (T *)p;
-	}
-};
-} // namespace
-
 // the parameter block's pieces the fast decoding kernels read (fill_params / fill_common)
 static const double *par_e(const psmc_hip_ctx *c) { return c->ns == 128 ? c->d_par + 32768 : c->d_par + 4 * 4096; }
 static const double *par_a0(const psmc_hip_ctx *c) { return par_e(c) + 3 * c->ns; }

@@ -12,17 +12,12 @@ int ensure_fast_buffers(psmc_hip_ctx *c)
 	if (c->d_stage && c->d_stats && c->d_warm && c->d_cnt && c->h_cnt && c->d_gate) return 0;
 	int rc;
 	const size_t sl = (size_t)c->ns * c->ns + 3 * (size_t)c->ns + 1;
-	if ((rc = dev_alloc(c, &c->d_stage, (size_t)RED_ROWS * sl))) return rc;
-	if ((rc = dev_alloc(c, &c->d_stats, sl))) return rc;
-	if ((rc = dev_alloc(c, &c->d_warm, (size_t)2))) return rc;
-	if ((rc = dev_alloc(c, &c->d_cnt, (size_t)4))) return rc;
-	if ((rc = dev_alloc(c, &c->d_gate, (size_t)4))) return rc;
-	if (!c->h_cnt && (hipHostMalloc((void **)&c->h_cnt, 4 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
-	                  hipHostGetDevicePointer((void **)&c->m_cnt, c->h_cnt, 0) != hipSuccess)) {
-		c->h_cnt = nullptr;
-		return fail(c, PSMC_HIP_ENOMEM, "hipHostMalloc (mapped)");
-	}
-	return 0;
+	if ((rc = c->d_stage.alloc(c, (size_t)RED_ROWS * sl))) return rc;
+	if ((rc = c->d_stats.alloc(c, sl))) return rc;
+	if ((rc = c->d_warm.alloc(c, (size_t)2))) return rc;
+	if ((rc = c->d_cnt.alloc(c, (size_t)4))) return rc;
+	if ((rc = c->d_gate.alloc(c, (size_t)4))) return rc;
+	return c->h_cnt ? 0 : c->h_cnt.alloc(c, 4);
 }
 
 // the tile length the planner picks for `bins` bins in n_work segments (see plan_fast)
@@ -109,36 +104,27 @@ static int plan_fast(psmc_hip_ctx *c)
 	int rc;
 	c->gap.assign(nc, 0);
 	if (nc > c->chunk_cap) {
-		if ((rc = dev_alloc(c, &c->d_chunks, (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_entry, (size_t)nc * c->ns))) return rc;
-		if ((rc = dev_alloc(c, &c->d_bexit, (size_t)(nc + 1) * c->ns))) return rc;
-		if ((rc = dev_alloc(c, &c->d_bentry, (size_t)nc * c->ns))) return rc;
-		if ((rc = dev_alloc(c, &c->d_dirty, (size_t)2 * nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_touch, (size_t)3 * nc))) return rc; // touch_f | touch_b | fmerge
-		if ((rc = dev_alloc(c, &c->d_finv, (size_t)nc))) return rc;
+		if ((rc = c->d_chunks.alloc(c, (size_t)nc))) return rc;
+		if ((rc = c->d_entry.alloc(c, (size_t)nc * c->ns))) return rc;
+		if ((rc = c->d_bexit.alloc(c, (size_t)(nc + 1) * c->ns))) return rc;
+		if ((rc = c->d_bentry.alloc(c, (size_t)nc * c->ns))) return rc;
+		if ((rc = c->d_dirty.alloc(c, (size_t)2 * nc))) return rc;
+		if ((rc = c->d_touch.alloc(c, (size_t)3 * nc))) return rc; // touch_f | touch_b | fmerge
+		if ((rc = c->d_finv.alloc(c, (size_t)nc))) return rc;
 		// (what only the round-6 options use is allocated only with them: a fast bootstrap keeps a plan per replicate, and a hundred pairs of
 		// pinned buffers cost seconds to make and to free)
-		if (c->h_mlen) { (void)hipHostFree(c->h_mlen); c->h_mlen = nullptr; c->m_mlen = nullptr; }
-		if (c->h_mis) { (void)hipHostFree(c->h_mis); c->h_mis = nullptr; c->m_mis = nullptr; }
-		if (c->prev_start && (rc = dev_alloc(c, &c->d_prevx, (size_t)nc * c->ns))) return rc;
-		if ((c->merge || c->adapt) &&
-		    (hipHostMalloc((void **)&c->h_mlen, (size_t)nc * sizeof(int), hipHostMallocMapped) != hipSuccess ||
-		     hipHostGetDevicePointer((void **)&c->m_mlen, c->h_mlen, 0) != hipSuccess ||
-		     hipHostMalloc((void **)&c->h_mis, (size_t)2 * nc * sizeof(double), hipHostMallocMapped) != hipSuccess ||
-		     hipHostGetDevicePointer((void **)&c->m_mis, c->h_mis, 0) != hipSuccess))
-			return fail(c, PSMC_HIP_ENOMEM, "hipHostMalloc (mapped)");
-		if ((rc = dev_alloc(c, &c->d_LLpart, (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_items, (size_t)32 * nc + 64))) return rc; // (+ 4 nc: matrix slot of every KcTile | the KcTile that computes a slot; + 2 nc: the fix pass's tiles)
-		if ((rc = dev_alloc(c, &c->d_ftiles, (size_t)3 * (nc + 16)))) return rc; // lists A | B, then the cover table of the backward verify
+		c->h_mlen.reset(); c->h_mis.reset();
+		if (c->prev_start && (rc = c->d_prevx.alloc(c, (size_t)nc * c->ns))) return rc;
+		if ((c->merge || c->adapt) && ((rc = c->h_mlen.alloc(c, (size_t)nc)) || (rc = c->h_mis.alloc(c, (size_t)2 * nc)))) return rc;
+		if ((rc = c->d_LLpart.alloc(c, (size_t)nc))) return rc;
+		if ((rc = c->d_items.alloc(c, (size_t)32 * nc + 64))) return rc; // (+ 4 nc: matrix slot of every KcTile | the KcTile that computes a slot; + 2 nc: the fix pass's tiles)
+		if ((rc = c->d_ftiles.alloc(c, (size_t)3 * (nc + 16)))) return rc; // lists A | B, then the cover table of the backward verify
 		c->vcover_off = (size_t)2 * (nc + 16);
-		if (c->h_ritems) { (void)hipHostFree(c->h_ritems); c->h_ritems = nullptr; }
-		if (hipHostMalloc((void **)&c->h_ritems, (size_t)4 * nc * sizeof(int), hipHostMallocMapped) != hipSuccess ||
-		    hipHostGetDevicePointer((void **)&c->m_ritems, c->h_ritems, 0) != hipSuccess)
-			return fail(c, PSMC_HIP_ENOMEM, "hipHostMalloc (mapped)");
+		if ((rc = c->h_ritems.alloc(c, (size_t)4 * nc))) return rc;
 		c->chunk_cap = nc;
 	}
 	// (the partial counts, d_Cpart, are sized per E-step by what its back half writes: enqueue_fast)
-	if ((rc = dev_alloc(c, &c->d_Epart, (size_t)nc * c->n_sub_used * 3 * c->ns))) return rc;
+	if ((rc = c->d_Epart.alloc(c, (size_t)nc * c->n_sub_used * 3 * c->ns))) return rc;
 	if ((rc = ensure_fast_buffers(c))) return rc;
 	HIPCHK(c, hipMemcpy(c->d_chunks, c->chunks.data(), sizeof(Chunk) * nc, hipMemcpyHostToDevice));
 	c->hom.assign(nc, 0);
@@ -386,7 +372,7 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 		std::stable_sort(qk.begin(), qk.end(), [](const std::pair<long long, int> &x, const std::pair<long long, int> &y) { return x.first < y.first; });
 		std::vector<int> qv(qk.size());
 		for (size_t i = 0; i < qk.size(); ++i) qv[i] = qk[i].second;
-		if (c->queue_cap < qv.size()) { int rc; if ((rc = dev_alloc(c, &c->d_queue, qv.size()))) return rc; c->queue_cap = qv.size(); }
+		if (int rc = c->d_queue.grow(c, qv.size())) return rc;
 		c->n_queue = (int)qv.size();
 		if (!qv.empty()) HIPCHK(c, hipMemcpy(c->d_queue, qv.data(), sizeof(int) * qv.size(), hipMemcpyHostToDevice));
 	}
@@ -464,7 +450,7 @@ static int build_items(psmc_hip_ctx *c, bool two_phase_bwd, int coarse)
 		HIPCHK(c, hipMemcpy(c->d_items + (size_t)28 * nc, kuniq.data(), sizeof(int) * kuniq.size(), hipMemcpyHostToDevice));
 		const size_t nsub = kcol2_on(c) ? (size_t)c->kc_sub_used : 1; // k_kcol2_struct: kc_sub matrices per tile
 		const size_t need = (size_t)c->n_kuniq * nsub * ((size_t)c->ns * c->ns + c->ns); // the matrices (one per slot), then one exponent per column
-		if (need > c->kcol_cap) { int rc; if ((rc = dev_alloc(c, &c->d_Kcol, need))) return rc; c->kcol_cap = need; }
+		if (int rc = c->d_Kcol.grow(c, need)) return rc;
 	}
 	c->items_dirty = false;
 	if (getenv("PSMC_HIP_DEBUG"))
@@ -604,11 +590,7 @@ int enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double
 		// (from a pinned copy, on the E-step's stream: a blocking copy of pageable memory waits for every kernel on the device, and with
 		// per-tile warm-ups this happens before every E-step)
 		psmc_hip_ctx *R = dbg_root(c); // (one staging buffer per root context: its replicates run one after the other)
-		if (R->h_chunks_cap < c->chunks.size()) {
-			if (R->h_chunks) { (void)hipHostFree(R->h_chunks); R->h_chunks = nullptr; }
-			if (hipHostMalloc((void **)&R->h_chunks, sizeof(Chunk) * c->chunks.size(), hipHostMallocDefault) != hipSuccess) return fail(c, PSMC_HIP_ENOMEM, "hipHostMalloc");
-			R->h_chunks_cap = c->chunks.size();
-		}
+		if ((rc = R->h_chunks.grow(c, c->chunks.size()))) return rc;
 		HIPCHK(c, hipStreamSynchronize(st)); // (the previous copy out of the same buffer is done)
 		memcpy(R->h_chunks, c->chunks.data(), sizeof(Chunk) * c->chunks.size());
 		HIPCHK(c, hipMemcpyAsync(c->d_chunks, R->h_chunks, sizeof(Chunk) * c->chunks.size(), hipMemcpyHostToDevice, st));
@@ -631,13 +613,13 @@ int enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double
 		// (profiles/r05_boot_first_iteration.txt).  Sized here, per E-step, for the back half that runs; grows, never shrinks.
 		const size_t nc_ = c->chunks.size(), S_ = (size_t)c->ns;
 		const size_t need = p.fused == 2 ? nc_ * 7 * S_ + 64 : (p.fused == 1 ? (nc_ / 4 + 8) * S_ * S_ : nc_ * (size_t)c->n_sub_used * S_ * S_);
-		if (c->cpart_cap < need) { if ((rc = dev_alloc(c, &c->d_Cpart, need))) return rc; c->cpart_cap = need; }
+		if ((rc = c->d_Cpart.grow(c, need))) return rc;
 	}
 	{
 		// the forward fix pass: where the back half knows about its merge records (the fused one of a 64-state model), tiles of whole 16-bin blocks
 		c->merge_used = c->merge != 0 && c->h_mlen && c->use_struct && p.fused == 1 && c->ns == 64 && c->chunk_used % 16 == 0;
 		p.merge = c->merge_used ? 1 : 0;
-		p.d_fmerge = c->d_touch + 2 * (size_t)p.n_chunks; p.d_finv = c->d_finv; p.m_mlen = c->m_mlen; p.h_mlen = c->h_mlen; p.m_mis = c->m_mis;
+		p.d_fmerge = c->d_touch + 2 * (size_t)p.n_chunks; p.d_finv = c->d_finv; p.m_mlen = c->h_mlen.dev; p.h_mlen = c->h_mlen; p.m_mis = c->h_mis.dev;
 		p.d_fix_f = c->d_items + 30 * (size_t)p.n_chunks; p.n_fix_f = c->n_fix_f;
 		if (c->h_mlen) memset(c->h_mlen, 0, sizeof(int) * p.n_chunks); // (the E-step that wrote it is over: launch_fast reads the verify counts before it returns)
 		if (c->h_mis) for (int b = 0; b < p.n_chunks; ++b) c->h_mis[b] = -1.0; // "not measured": the tiles neither fix launch looks at keep their warm-ups
@@ -661,7 +643,7 @@ int enqueue_fast(psmc_hip_ctx *c, const double *a, const double *e, const double
 	p.tail = c->tail != 0 && c->use_struct && p.fused == 1 && c->overlap ? 1 : 0; p.d_vcover = c->d_ftiles + c->vcover_off;
 	p.d_items_f = c->d_items; p.d_items_b = c->d_items + 2 * p.n_chunks;
 	p.d_ritems_f = c->d_items + 4 * p.n_chunks; p.d_ritems_b = c->d_items + 6 * p.n_chunks;
-	p.n_items_f = c->n_items_f; p.n_items_b = c->n_items_b; p.tile_len = c->chunk_used; p.h_ritems = c->h_ritems; p.m_ritems = c->m_ritems; p.m_cnt = c->m_cnt;
+	p.n_items_f = c->n_items_f; p.n_items_b = c->n_items_b; p.tile_len = c->chunk_used; p.h_ritems = c->h_ritems; p.m_ritems = c->h_ritems.dev; p.m_cnt = c->h_cnt.dev;
 	c->flagged_f.clear(); c->flagged_b.clear();
 	p.flagged_f = &c->flagged_f; p.flagged_b = &c->flagged_b;
 	p.d_entry = c->d_entry; p.d_bentry = c->d_bentry; p.d_bexit = c->d_bexit; p.d_Cpart = c->d_Cpart; p.d_Epart = c->d_Epart;

@@ -4,20 +4,6 @@
 // learned state is touched, in either mode, and the device memory of the call is released before it returns.
 #include "psmc_hip_ctx.h"
 
-namespace {
-struct SampScratch { // device memory of one call
-	std::vector<void *> bufs;
-	~SampScratch() { for (void *p : bufs) (void)hipFree(p); }
-	template <class T> T *get(size_t n)
-	{
-		void *p = nullptr;
-		if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-		bufs.push_back(p);
-		return (T *)p;
-	}
-};
-} // namespace
-
 extern "C" int psmc_hip_sample_paths(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, uint64_t seed, int32_t n_samp,
                                      const uint64_t *stream, int32_t *path)
 {
@@ -32,42 +18,17 @@ extern "C" int psmc_hip_sample_paths(psmc_hip_ctx *c, const double *a, const dou
 	char msg[256];
 
 	// the parameters padded with zeros: a [S][S] as it is, e [3][S] with the missing symbol's row of ones, a0 [S]
-	std::vector<double> tab((size_t)S * S + 4 * (size_t)S, 0.0);
-	double *pa = tab.data(), *pe = pa + (size_t)S * S, *p0 = pe + 3 * (size_t)S;
-	for (int l = 0; l < n; ++l)
-		for (int k = 0; k < n; ++k) pa[(size_t)l * S + k] = a[(size_t)l * n + k];
-	for (int k = 0; k < n; ++k) {
-		pe[k] = e[k];
-		pe[S + k] = e[n + k];
-		pe[2 * S + k] = 1.0;
-		p0[k] = a0[k];
-	}
-
-	// segments longest first; rows and path entries in load order; the tiles of the backtrace; the stream ids
-	std::vector<int64_t> row_off(n_seg);
-	int64_t bins = 0;
-	for (int i = 0; i < n_seg; ++i) { row_off[i] = bins; bins += c->L[i]; }
-	std::vector<VitSeg> segs(n_seg);
-	std::vector<uint64_t> sid(n_seg);
-	for (int i = 0; i < n_seg; ++i) {
-		segs[i] = VitSeg{c->off[i], row_off[i], c->L[i], i};
-		sid[i] = stream ? stream[i] : (uint64_t)i;
-	}
-	std::stable_sort(segs.begin(), segs.end(), [](const VitSeg &x, const VitSeg &y) { return x.L > y.L; });
-	std::vector<VitTile> tiles;
-	std::vector<int32_t> seg_tile((size_t)2 * n_seg);
-	{
-		int64_t n_tiles = 0;
-		for (int i = 0; i < n_seg; ++i) n_tiles += (c->L[i] + T - 1) / T;
-		if (n_tiles > 0x7fffffff) return fail(c, PSMC_HIP_EINVAL, "sample_paths: more than 2^31 backtrace tiles (\"vit_tile\" is too small for this input)");
-		tiles.reserve((size_t)n_tiles);
-		for (int i = 0; i < n_seg; ++i) {
-			seg_tile[i] = (int32_t)tiles.size();
-			for (int lo = 1; lo <= c->L[i]; lo += T) tiles.push_back(VitTile{row_off[i], lo, std::min(c->L[i], lo + T - 1)});
-			seg_tile[n_seg + i] = (int32_t)tiles.size() - seg_tile[i];
-		}
-	}
+	const std::vector<double> tab = path_params(n, S, a, e, a0, [](double x) { return x; }, 0.0, 1.0);
+	// segments, rows and backtrace tiles as psmc_hip_viterbi has them; the stream ids
+	PathPlan pl;
+	if (int rc = path_plan(c, "sample_paths", true, pl)) return rc;
+	const std::vector<VitSeg> &segs = pl.segs;
+	const std::vector<VitTile> &tiles = pl.tiles;
+	const std::vector<int32_t> &seg_tile = pl.seg_tile;
+	const int64_t bins = pl.bins;
 	const size_t n_tiles = tiles.size();
+	std::vector<uint64_t> sid(n_seg);
+	for (int i = 0; i < n_seg; ++i) sid[i] = stream ? stream[i] : (uint64_t)i;
 
 	// the group: one map table per sample
 	const size_t tab_bytes = (size_t)bins * S * (wide_bp ? 2 : 1);
@@ -83,12 +44,10 @@ extern "C" int psmc_hip_sample_paths(psmc_hip_ctx *c, const double *a, const dou
 		}
 	}
 	G = std::max(1, std::min(G, (int)std::min<int32_t>(n_samp, SAMP_MAX_GROUP)));
-	SampScratch sc;
+	Scratch sc;
 	uint8_t *d_map = nullptr;
 	for (;; G = (G + 1) / 2) { // (a group that does not fit after all: half of it)
-		void *p = nullptr;
-		if (hipMalloc(&p, tab_bytes * G) == hipSuccess) { d_map = (uint8_t *)p; sc.bufs.push_back(p); break; }
-		(void)hipGetLastError();
+		if ((d_map = sc.get<uint8_t>(tab_bytes * G))) break;
 		if (G == 1) {
 			snprintf(msg, sizeof msg, "sample_paths: no device memory for one sample's map table: %.3f GB (%lld bins x %d states x %d)", tab_bytes * 1e-9,
 			         (long long)bins, S, wide_bp ? 2 : 1);

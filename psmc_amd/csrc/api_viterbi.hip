@@ -3,19 +3,52 @@
 // touched, in either mode, and the device memory of the call is released before it returns.
 #include "psmc_hip_ctx.h"
 
-namespace {
-struct VitScratch { // device memory of one call
-	std::vector<void *> bufs;
-	~VitScratch() { for (void *p : bufs) (void)hipFree(p); }
-	template <class T> T *get(size_t n)
-	{
-		void *p = nullptr;
-		if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) return nullptr;
-		bufs.push_back(p);
-		return (T *)p;
+// What psmc_hip_viterbi and psmc_hip_sample_paths (api_sample.hip) plan on the host: the segments longest first, rows and path entries
+// in load order, and -- when a path is wanted -- the tiles of the backtrace.  `who` names the caller in the one refusal.
+int path_plan(psmc_hip_ctx *c, const char *who, bool want_path, PathPlan &pl)
+{
+	const int n_seg = c->n_seg, T = c->vit_tile;
+	std::vector<int64_t> row_off(n_seg);
+	pl.bins = 0;
+	for (int i = 0; i < n_seg; ++i) { row_off[i] = pl.bins; pl.bins += c->L[i]; }
+	pl.segs.resize(n_seg);
+	for (int i = 0; i < n_seg; ++i) pl.segs[i] = VitSeg{c->off[i], row_off[i], c->L[i], i};
+	std::stable_sort(pl.segs.begin(), pl.segs.end(), [](const VitSeg &x, const VitSeg &y) { return x.L > y.L; });
+	pl.tiles.clear();
+	pl.seg_tile.assign((size_t)2 * n_seg, 0);
+	if (!want_path) return 0;
+	int64_t n_tiles = 0;
+	for (int i = 0; i < n_seg; ++i) n_tiles += (c->L[i] + T - 1) / T;
+	if (n_tiles > 0x7fffffff) {
+		char msg[128];
+		snprintf(msg, sizeof msg, "%s: more than 2^31 backtrace tiles (\"vit_tile\" is too small for this input)", who);
+		return fail(c, PSMC_HIP_EINVAL, msg);
 	}
-};
-} // namespace
+	pl.tiles.reserve((size_t)n_tiles);
+	for (int i = 0; i < n_seg; ++i) {
+		pl.seg_tile[i] = (int32_t)pl.tiles.size();
+		for (int lo = 1; lo <= c->L[i]; lo += T) pl.tiles.push_back(VitTile{row_off[i], lo, std::min(c->L[i], lo + T - 1)});
+		pl.seg_tile[n_seg + i] = (int32_t)pl.tiles.size() - pl.seg_tile[i];
+	}
+	return 0;
+}
+
+// The parameters of those two calls, padded to S states: f(a) [S][S] | f(e) [3][S], the missing symbol's row `miss` | f(a0) [S], `pad`
+// in the padding.  One call of f per entry, in this order.
+std::vector<double> path_params(int n, int S, const double *a, const double *e, const double *a0, double (*f)(double), double pad, double miss)
+{
+	std::vector<double> tab((size_t)S * S + 4 * (size_t)S, pad);
+	double *pa = tab.data(), *pe = pa + (size_t)S * S, *p0 = pe + 3 * (size_t)S;
+	for (int l = 0; l < n; ++l)
+		for (int k = 0; k < n; ++k) pa[(size_t)l * S + k] = f(a[(size_t)l * n + k]);
+	for (int k = 0; k < n; ++k) {
+		pe[k] = f(e[k]);
+		pe[S + k] = f(e[n + k]);
+		pe[2 * S + k] = miss;
+		p0[k] = f(a0[k]);
+	}
+	return tab;
+}
 
 extern "C" int psmc_hip_viterbi(psmc_hip_ctx *c, const double *a, const double *e, const double *a0, int32_t *path, double *score)
 {
@@ -29,41 +62,16 @@ extern "C" int psmc_hip_viterbi(psmc_hip_ctx *c, const double *a, const double *
 	char msg[256];
 
 	// the log tables: one libm log() per entry, -inf in the padding
-	const double ninf = -HUGE_VAL;
-	std::vector<double> tab((size_t)S * S + 4 * (size_t)S, ninf);
-	double *la = tab.data(), *le = la + (size_t)S * S, *l0 = le + 3 * (size_t)S;
-	for (int l = 0; l < n; ++l)
-		for (int k = 0; k < n; ++k) la[(size_t)l * S + k] = log(a[(size_t)l * n + k]);
-	for (int k = 0; k < n; ++k) {
-		le[k] = log(e[k]);
-		le[S + k] = log(e[n + k]);
-		le[2 * S + k] = 0.0;
-		l0[k] = log(a0[k]);
-	}
-
-	// segments longest first; rows and path entries in load order; the tiles of the backtrace
-	std::vector<int64_t> row_off(n_seg);
-	int64_t bins = 0;
-	for (int i = 0; i < n_seg; ++i) { row_off[i] = bins; bins += c->L[i]; }
-	std::vector<VitSeg> segs(n_seg);
-	for (int i = 0; i < n_seg; ++i) segs[i] = VitSeg{c->off[i], row_off[i], c->L[i], i};
-	std::stable_sort(segs.begin(), segs.end(), [](const VitSeg &x, const VitSeg &y) { return x.L > y.L; });
-	std::vector<VitTile> tiles;
-	std::vector<int32_t> seg_tile((size_t)2 * n_seg);
-	if (path) {
-		int64_t n_tiles = 0;
-		for (int i = 0; i < n_seg; ++i) n_tiles += (c->L[i] + T - 1) / T;
-		if (n_tiles > 0x7fffffff) return fail(c, PSMC_HIP_EINVAL, "viterbi: more than 2^31 backtrace tiles (\"vit_tile\" is too small for this input)");
-		tiles.reserve((size_t)n_tiles);
-		for (int i = 0; i < n_seg; ++i) {
-			seg_tile[i] = (int32_t)tiles.size();
-			for (int lo = 1; lo <= c->L[i]; lo += T) tiles.push_back(VitTile{row_off[i], lo, std::min(c->L[i], lo + T - 1)});
-			seg_tile[n_seg + i] = (int32_t)tiles.size() - seg_tile[i];
-		}
-	}
+	const std::vector<double> tab = path_params(n, S, a, e, a0, log, -HUGE_VAL, 0.0);
+	PathPlan pl;
+	if (int rc = path_plan(c, "viterbi", path != nullptr, pl)) return rc;
+	const std::vector<VitSeg> &segs = pl.segs;
+	const std::vector<VitTile> &tiles = pl.tiles;
+	const std::vector<int32_t> &seg_tile = pl.seg_tile;
+	const int64_t bins = pl.bins;
 	const size_t n_tiles = tiles.size();
 
-	VitScratch sc;
+	Scratch sc;
 	VitLaunch v;
 	memset(&v, 0, sizeof v);
 	const size_t bp_bytes = path ? (size_t)bins * S * (wide_bp ? 2 : 1) : 0;

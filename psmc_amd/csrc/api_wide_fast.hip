@@ -45,25 +45,6 @@
 static constexpr int WF_PAR = 8; // e0 | e1 | a0 | P | R | qa | c | dd (wide_fast.h)
 static constexpr int WF_NACC = 7; // SL SU DG CL CU E0 E1 per tile
 
-void free_wide_fast(psmc_hip_ctx *c)
-{
-	void *p[] = {c->d_wf_chunks, c->d_wf_X, c->d_wf_inv, c->d_wf_par, c->d_wf_entry, c->d_wf_bentry, c->d_wf_bexit, c->d_wf_part,
-	             c->d_wf_ll, c->d_wf_dirty, c->d_wf_list, c->d_wf_xhi, c->d_wc_V, c->d_wc_Xs, c->d_wc_P, c->d_wc_a, c->d_wc_out, c->d_wc_kr, c->d_wc_vrow};
-	for (void *q : p) if (q) (void)hipFree(q);
-	void *gp[] = {c->d_wg_glue, c->d_wg_list[0], c->d_wg_list[1], c->d_wg_spec[0], c->d_wg_spec[1], c->d_wg_runs[0], c->d_wg_runs[1], c->d_wg_again, c->d_wg_M, c->d_wg_Mh, c->d_wg_cls, c->d_wg_mix_slot, c->d_wg_mix_tiles, c->d_wg_mix_jobs, c->d_wg_Mx};
-	for (void *q : gp) if (q) (void)hipFree(q);
-	c->d_wg_glue = c->d_wg_list[0] = c->d_wg_list[1] = c->d_wg_spec[0] = c->d_wg_spec[1] = nullptr;
-	c->d_wg_runs[0] = c->d_wg_runs[1] = c->d_wg_again = nullptr; c->d_wg_M = c->d_wg_Mh = nullptr; c->d_wg_cls = nullptr; c->wg_cap = 0; c->wg_m_cap = c->wg_mh_cap = 0; c->wg_mh_T = 0;
-	c->d_wg_mix_slot = c->d_wg_mix_tiles = c->d_wg_mix_jobs = nullptr; c->d_wg_Mx = nullptr; c->wg_mx_cap = 0; c->wg_mx_T = c->wg_mx_n = 0;
-	if (c->h_wf_par) (void)hipHostFree(c->h_wf_par);
-	c->d_wf_chunks = nullptr; c->d_wf_X = c->d_wf_inv = c->d_wf_par = c->d_wf_entry = c->d_wf_bentry = c->d_wf_bexit = nullptr;
-	c->d_wf_part = c->d_wf_ll = nullptr; c->d_wf_dirty = c->d_wf_list = nullptr; c->h_wf_par = nullptr;
-	c->d_wf_xhi = nullptr; c->wf_xhi_cap = 0; c->wf_rows = 0; c->wf_tab_iv = c->wf_last_iv = 0;
-	c->wf_cap = 0; c->wf_bins = 0;
-	c->d_wc_V = c->d_wc_Xs = c->d_wc_P = c->d_wc_a = c->d_wc_out = nullptr; c->d_wc_kr = nullptr; c->d_wc_vrow = nullptr;
-	c->wc_v_cap = c->wc_xs_cap = c->wc_p_cap = c->wc_kr_cap = c->wc_vrow_cap = 0;
-}
-
 // rows of the X table over `bins` positions at one row per `iv` positions (iv = 8: the rows at p % 8 == 0, by absolute position)
 static inline int64_t wide_table_rows(int64_t bins, int iv) { return (bins + iv - 1) / iv; }
 
@@ -183,11 +164,11 @@ static int plan_wide_gaps(psmc_hip_ctx *c, int T, int W)
 	int rc;
 	if (nc > c->wg_cap) {
 		c->wg_cap = 0;
-		if ((rc = dev_alloc(c, &c->d_wg_glue, (size_t)nc))) return rc;
+		if ((rc = c->d_wg_glue.alloc(c, (size_t)nc))) return rc;
 		for (int d = 0; d < 2; ++d) // (a run has at least one tile, a walk one more: no list is longer than the plan)
-			if ((rc = dev_alloc(c, &c->d_wg_list[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_spec[d], (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_runs[d], (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wg_again, (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_cls, (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wg_mix_slot, (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_mix_tiles, (size_t)nc)) || (rc = dev_alloc(c, &c->d_wg_mix_jobs, (size_t)2 * nc))) return rc;
+			if ((rc = c->d_wg_list[d].alloc(c, (size_t)nc)) || (rc = c->d_wg_spec[d].alloc(c, (size_t)nc)) || (rc = c->d_wg_runs[d].alloc(c, (size_t)nc))) return rc;
+		if ((rc = c->d_wg_again.alloc(c, (size_t)nc)) || (rc = c->d_wg_cls.alloc(c, (size_t)nc))) return rc;
+		if ((rc = c->d_wg_mix_slot.alloc(c, (size_t)nc)) || (rc = c->d_wg_mix_tiles.alloc(c, (size_t)nc)) || (rc = c->d_wg_mix_jobs.alloc(c, (size_t)2 * nc))) return rc;
 		c->wg_cap = nc;
 	}
 	HIPCHK(c, hipMemcpy(c->d_wg_glue, glue.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice));
@@ -236,14 +217,14 @@ static int plan_wide(psmc_hip_ctx *c)
 	const int nc = (int)c->wf_chunks.size(), S = wf_width(c);
 	int rc;
 	if (nc > c->wf_cap) {
-		if ((rc = dev_alloc(c, &c->d_wf_chunks, (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wf_entry, (size_t)nc * S))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wf_bentry, (size_t)nc * S))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wf_bexit, (size_t)(nc + 1) * S))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wf_part, (size_t)nc * WF_NACC * S))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wf_ll, (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wf_dirty, (size_t)nc))) return rc;
-		if ((rc = dev_alloc(c, &c->d_wf_list, (size_t)nc))) return rc;
+		if ((rc = c->d_wf_chunks.alloc(c, (size_t)nc))) return rc;
+		if ((rc = c->d_wf_entry.alloc(c, (size_t)nc * S))) return rc;
+		if ((rc = c->d_wf_bentry.alloc(c, (size_t)nc * S))) return rc;
+		if ((rc = c->d_wf_bexit.alloc(c, (size_t)(nc + 1) * S))) return rc;
+		if ((rc = c->d_wf_part.alloc(c, (size_t)nc * WF_NACC * S))) return rc;
+		if ((rc = c->d_wf_ll.alloc(c, (size_t)nc))) return rc;
+		if ((rc = c->d_wf_dirty.alloc(c, (size_t)nc))) return rc;
+		if ((rc = c->d_wf_list.alloc(c, (size_t)nc))) return rc;
 		c->wf_cap = nc;
 	}
 	HIPCHK(c, hipMemcpy(c->d_wf_chunks, c->wf_chunks.data(), sizeof(Chunk) * nc, hipMemcpyHostToDevice));
@@ -349,11 +330,8 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 		return fail(c, PSMC_HIP_ENOTSUP, "estep_factored: the wide fast path needs a transition matrix of the PSMC form (two rank-1 triangles, core.c:112-122)");
 	int rc;
 	if ((rc = ensure_fast_buffers(c))) return rc;
-	if (!c->h_wf_par && hipHostMalloc((void **)&c->h_wf_par, sizeof(double) * WF_PAR * S, hipHostMallocDefault) != hipSuccess) {
-		c->h_wf_par = nullptr;
-		return fail(c, PSMC_HIP_ENOMEM, "hipHostMalloc");
-	}
-	if (!c->d_wf_par && (rc = dev_alloc(c, &c->d_wf_par, (size_t)WF_PAR * S))) return rc;
+	if (!c->h_wf_par && (rc = c->h_wf_par.alloc(c, (size_t)WF_PAR * S))) return rc;
+	if (!c->d_wf_par && (rc = c->d_wf_par.alloc(c, (size_t)WF_PAR * S))) return rc;
 	if ((c->plan_dirty || c->wf_chunks.empty()) && (rc = plan_wide(c))) return rc;
 	const int64_t bins = c->total + 128;
 	// "wide_ckpt": one X row per 8 positions -- unless "wide_decode" is on without "wide_decode_ckpt": the full-table decoding kernels
@@ -365,19 +343,15 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	if (c->wf_bins < bins || c->wf_tab_iv != iv) { // the X table: 8 S bytes per bin (61 GB at 256 states and 30 M bins; 8 KB per bin at S = 1024), with "wide_ckpt" S bytes per bin; sized anew when the interval changes, whether it grows or shrinks
 		const int64_t rows = wide_table_rows(bins, iv);
 		c->wf_bins = 0; c->wf_rows = 0; c->wf_tab_iv = 0;
-		if ((rc = dev_alloc(c, &c->d_wf_X, (size_t)rows * S))) {
+		if ((rc = c->d_wf_X.alloc(c, (size_t)rows * S))) {
 			snprintf(msg, sizeof msg, "estep_factored: no device memory for the X table of the wide fast path: %lld bytes (%lld bins x %d padded states x 8%s)",
 			         (long long)rows * S * 8, (long long)bins, S, iv == 8 ? " / 8: \"wide_ckpt\"" : "");
 			return fail(c, PSMC_HIP_ENOMEM, msg);
 		}
-		if ((rc = dev_alloc(c, &c->d_wf_inv, (size_t)bins))) return rc;
+		if ((rc = c->d_wf_inv.alloc(c, (size_t)bins))) return rc;
 		c->wf_bins = bins; c->wf_rows = rows; c->wf_tab_iv = iv;
 	}
-	if (iv == 8 && c->wf_xhi_cap < nt) { // every tile's last row X_hi
-		c->wf_xhi_cap = 0;
-		if ((rc = dev_alloc(c, &c->d_wf_xhi, (size_t)nt * S))) return rc;
-		c->wf_xhi_cap = nt;
-	}
+	if (iv == 8 && (rc = c->d_wf_xhi.grow(c, (size_t)nt * S))) return rc; // every tile's last row X_hi
 	HIPCHK(c, hipStreamSynchronize(c->stream)); // the previous upload out of the pinned staging block
 	double *hp = c->h_wf_par;
 	memset(hp, 0, sizeof(double) * WF_PAR * S); // padded states: zero emission and matrix entries
@@ -407,31 +381,19 @@ int estep_wide_fast(psmc_hip_ctx *c, const double *a, const double *e, const dou
 	WideGap g;
 	memset(&g, 0, sizeof(g));
 	if (gaps) {
-		if ((c->wg_mats & 1) && c->wg_m_cap < (size_t)n * S) {
-			c->wg_m_cap = 0;
-			if ((rc = dev_alloc(c, &c->d_wg_M, (size_t)n * S))) return rc;
-			c->wg_m_cap = (size_t)n * S;
-		}
+		if ((c->wg_mats & 1) && (rc = c->d_wg_M.grow(c, (size_t)n * S))) return rc;
 		const size_t mh = (size_t)n * S + (size_t)(c->wf_T + 3) / 4; // M_h, then the pilot's factors
-		if ((c->wg_mats & 2) && c->wg_mh_cap < mh) {
-			c->wg_mh_cap = 0;
-			if (dev_alloc(c, &c->d_wg_Mh, mh)) {
-				snprintf(msg, sizeof msg, "estep_factored: no device memory for the matrix of a homozygous tile (\"wide_hom_tiles\"): %lld bytes (%d states x %d padded states x 8, and %d scale factors)",
-				         (long long)mh * 8, n, S, (c->wf_T + 3) / 4);
-				return fail(c, PSMC_HIP_ENOMEM, msg);
-			}
-			c->wg_mh_cap = mh;
+		if ((c->wg_mats & 2) && c->d_wg_Mh.grow(c, mh)) {
+			snprintf(msg, sizeof msg, "estep_factored: no device memory for the matrix of a homozygous tile (\"wide_hom_tiles\"): %lld bytes (%d states x %d padded states x 8, and %d scale factors)",
+			         (long long)mh * 8, n, S, (c->wf_T + 3) / 4);
+			return fail(c, PSMC_HIP_ENOMEM, msg);
 		}
 		const int n_mix = (int)c->wg_mix_tiles.size();
 		const size_t mx = (size_t)2 * n_mix * ((size_t)n * S + (size_t)(c->wf_T + 3) / 4); // every class-6 tile's F and B, then their pilots' factors
-		if ((c->wg_mats & 4) && c->wg_mx_cap < mx) {
-			c->wg_mx_cap = 0;
-			if (dev_alloc(c, &c->d_wg_Mx, mx)) {
-				snprintf(msg, sizeof msg, "estep_factored: no device memory for the matrices of the mix tiles (\"wide_mix_tiles\"): %lld bytes (%d tiles x 2 x %d states x %d padded states x 8, and their scale factors); \"wide_mix_mb\" caps them",
-				         (long long)mx * 8, n_mix, n, S);
-				return fail(c, PSMC_HIP_ENOMEM, msg);
-			}
-			c->wg_mx_cap = mx;
+		if ((c->wg_mats & 4) && c->d_wg_Mx.grow(c, mx)) {
+			snprintf(msg, sizeof msg, "estep_factored: no device memory for the matrices of the mix tiles (\"wide_mix_tiles\"): %lld bytes (%d tiles x 2 x %d states x %d padded states x 8, and their scale factors); \"wide_mix_mb\" caps them",
+			         (long long)mx * 8, n_mix, n, S);
+			return fail(c, PSMC_HIP_ENOMEM, msg);
 		}
 		g.mats = c->wg_mats; g.Mh = c->d_wg_Mh; g.cls = c->d_wg_cls;
 		g.obs = c->d_obs; g.n_mix = n_mix; g.mix_tiles = c->d_wg_mix_tiles; g.mix_slot = c->d_wg_mix_slot; g.Mx = c->d_wg_Mx;
@@ -575,23 +537,18 @@ int estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const d
 	const bool ck = c->wf_last_iv == 8; // the interval the E-step above actually kept
 	plan_counts(c, S, ck, pl);
 	const int nt = (int)c->wf_chunks.size(), n_slabs = (int)pl.slab_t0.size() - 1;
-	auto grow = [&](auto **p, size_t &cap, size_t want, const char *what) -> int {
-		if (cap >= want && *p) return 0;
-		cap = 0;
-		if (dev_alloc(c, p, want)) {
-			snprintf(msg, sizeof msg, "estep: no device memory for %s of the wide counts pass: %lld bytes (\"wide_counts_slab\" bounds the slab)",
-			         what, (long long)(want * sizeof(**p)));
-			return fail(c, PSMC_HIP_ENOMEM, msg);
-		}
-		cap = want;
-		return 0;
+	auto grow = [&](auto &buf, size_t want, const char *what) -> int {
+		if (buf.grow(c, want) == 0) return 0;
+		snprintf(msg, sizeof msg, "estep: no device memory for %s of the wide counts pass: %lld bytes (\"wide_counts_slab\" bounds the slab)",
+		         what, (long long)(want * sizeof(*buf.p)));
+		return fail(c, PSMC_HIP_ENOMEM, msg);
 	};
-	if ((rc = grow(&c->d_wc_V, c->wc_v_cap, (size_t)std::max<int64_t>(pl.max_rows, 1) * S, "the V slab"))) return rc;
-	if (ck && (rc = grow(&c->d_wc_Xs, c->wc_xs_cap, (size_t)std::max<int64_t>(pl.max_rows, 1) * S, "the X slab (\"wide_counts_ckpt\")"))) return rc;
-	if ((rc = grow(&c->d_wc_P, c->wc_p_cap, (size_t)pl.n_split * S * S, "the partial matrices"))) return rc;
-	if ((rc = grow(&c->d_wc_kr, c->wc_kr_cap, (size_t)std::max(pl.max_kr, 1), "the K ranges"))) return rc;
-	if ((rc = grow(&c->d_wc_vrow, c->wc_vrow_cap, (size_t)nt, "the tiles' rows"))) return rc;
-	if (!c->d_wc_a && ((rc = dev_alloc(c, &c->d_wc_a, (size_t)n * n)) || (rc = dev_alloc(c, &c->d_wc_out, (size_t)n * n)))) return rc;
+	if ((rc = grow(c->d_wc_V, (size_t)std::max<int64_t>(pl.max_rows, 1) * S, "the V slab"))) return rc;
+	if (ck && (rc = grow(c->d_wc_Xs, (size_t)std::max<int64_t>(pl.max_rows, 1) * S, "the X slab (\"wide_counts_ckpt\")"))) return rc;
+	if ((rc = grow(c->d_wc_P, (size_t)pl.n_split * S * S, "the partial matrices"))) return rc;
+	if ((rc = grow(c->d_wc_kr, (size_t)std::max(pl.max_kr, 1), "the K ranges"))) return rc;
+	if ((rc = grow(c->d_wc_vrow, (size_t)nt, "the tiles' rows"))) return rc;
+	if (!c->d_wc_a && ((rc = c->d_wc_a.alloc(c, (size_t)n * n)) || (rc = c->d_wc_out.alloc(c, (size_t)n * n)))) return rc;
 	hipStream_t st = c->stream;
 	HIPCHK(c, hipMemcpyAsync(c->d_wc_a, a, sizeof(double) * n * n, hipMemcpyHostToDevice, st));
 	HIPCHK(c, hipMemcpyAsync(c->d_wc_vrow, pl.vrow.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, st));
@@ -640,7 +597,7 @@ int estep_counts_wide(psmc_hip_ctx *c, const double *a, const double *e, const d
 extern "C" int psmc_hip_wide_table_info(psmc_hip_ctx *c, int64_t out[4])
 {
 	if (!c || !out) return PSMC_HIP_EINVAL;
-	const int64_t rows = c->wf_rows + c->wf_xhi_cap;
+	const int64_t rows = c->wf_rows + (int64_t)(c->d_wf_xhi.cap / (size_t)wf_width(c));
 	out[0] = rows; out[1] = rows ? wf_width(c) : 0; out[2] = c->wf_last_iv; out[3] = rows * out[1] * 8;
 	return PSMC_HIP_OK;
 }
