@@ -385,7 +385,11 @@ int psmc_hip_select(psmc_hip_ctx *ctx, int n_sel, const int32_t *seg_idx);
  *   chk      n_sel values of the khmm.c:237-238 underflow check (may be NULL)
  * Fast mode computes neither A0 (nothing downstream reads it: khmm.c:321-322 fills it, hmm_Q never uses it) nor the
  * self-check (its speculation has its own verify / repair net): A0 comes back as zeros and chk as 1.0, from this call
- * and from psmc_hip_group_estep alike.  Exact mode returns the reference's values. */
+ * and from psmc_hip_group_estep alike.  Exact mode returns the reference's values -- also where the parameters are no HMM
+ * (negative, infinite or NaN entries): a cell that is NaN in the reference is NaN here and no other is, with the reference's
+ * sign as long as no parameter is a positive NaN (x86 sets the sign bit of a NaN it makes and carries an operand's NaN along).
+ * Parameters that hold NaNs of both signs are undefined: which of two NaNs an addition keeps depends on the operand order one
+ * build of the reference chose. */
 int psmc_hip_estep(psmc_hip_ctx *ctx, const double *a, const double *e, const double *a0, double *A, double *E,
                    double *A0, double *LL, double *chk);
 

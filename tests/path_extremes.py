@@ -81,7 +81,7 @@ def short_segs(golden, long_bins=700):
     src = golden.segs_mid[0]
     miss = src[34204:34294]
     assert (miss == 2).all() and len(miss) == 90
-    def cut(i, L):   # L bins around a heterozygous (i odd) or a missing (i even) bin, at bin i % L of the slice
+    def cut(i, L):   # L bins around a heterozygous (i even) or a missing (i odd) bin, at bin i % L of the slice
         p = int(np.flatnonzero(src[1000 * i:] == 1 + i % 2)[0]) + 1000 * i - i % L
         return src[p:p + L]
     segs = [golden.segs_small[0], miss[:3], cut(1, 2), cut(2, 63), cut(3, 64), cut(4, 65), miss[:70],

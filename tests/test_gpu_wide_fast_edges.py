@@ -77,8 +77,9 @@ MODELS = {
 }
 # The models api.hip factor_structure refuses (at all four sizes, and at 200 states), with the entry that refuses them:
 # tests/test_fastmodel.py test_factorisation_criterion_on_the_extreme_models holds the numpy restatement to exactly this list.
-# Three of thirteen.  None of the three is an HMM at all -- the host model itself breaks down there, so neither the oracle nor
-# the exact kernels have an answer -- and each has a milder neighbour in the list that is accepted and runs: lambda alternating
+# Three of thirteen.  None of the three is an HMM at all -- the host model itself breaks down there; the oracle and the exact
+# kernels still have the reference's answer (NaN in every cell under the first two, finite under rho0 = 0.5), gated bit for bit in
+# tests/test_gpu_exact_extremes.py -- and each has a milder neighbour in the list that is accepted and runs: lambda alternating
 # 0.1 / 10, the ramp from 100 down to 0.01 (matrix entries down to 1e-237, a0 down to 1e-231), rho0 = 0.1.
 REFUSED = {
     "lambda_alt_1e-3_1e3": "corner a[0][n-1] = 0 and a[n-1][0] = NaN: survival past an interval with lambda = 1e-3 underflows in the host model",
