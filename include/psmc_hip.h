@@ -367,7 +367,14 @@ int psmc_hip_set_option(psmc_hip_ctx *ctx, const char *key, double value);
 int psmc_hip_set_cu_range(psmc_hip_ctx *ctx, int first, int count);
 
 /* Replaces the per-segment hmm_new_data copies of em.c:38-44 / khmm.c:37-45:
- * uploads all segments once; the caller keeps ownership of seq. */
+ * uploads all segments once; the caller keeps ownership of seq.
+ * Call order: a load (this call or psmc_hip_load_segments_device) ends what the last E-step left.  Until the next single E-step
+ * psmc_hip_get_tables and the decoding entry points (psmc_hip_decode, _posterior, _scales, _post_counts, _post_mean,
+ * _post_quantile) return PSMC_HIP_ESTATE ("no single E-step yet"), as on a fresh context and as after psmc_hip_estep_batch: the
+ * tables hold the previous segments at the previous offsets.
+ * NOT checked (open): a call that has to grow the tables after a single E-step -- psmc_hip_reserve_batch_tables with a bound
+ * beyond what they hold -- frees and re-allocates them, and a decoding call or psmc_hip_get_tables before the next single E-step
+ * then reads blocks nobody wrote.  Reserve before the first E-step (as psmc_boot does), or run an E-step before decoding. */
 int psmc_hip_load_segments(psmc_hip_ctx *ctx, int n_seg, const uint8_t *const *seq, const int32_t *L);
 /* Same, for observations already resident in HBM: d_obs holds the segments
  * back to back, segment i starting at byte off[i] (off[i] % 64 == 0) with at

@@ -217,6 +217,9 @@ int set_segments_common(psmc_hip_ctx *c, int n_seg, const int32_t *L)
 	destroy_kids(c); // batch children hold plans over the previous segments
 	c->reserved_refwd = -1; c->reserved_cap = 0;
 	c->d_b2.reset(); c->b2_bins = c->b2_alloc = 0;
+	// the tables hold the previous segments at the previous offsets (and were sized for them): nothing to decode until an E-step
+	// of the new ones -- psmc_hip_get_tables and the decoding entry points answer "no single E-step yet", as on a fresh context
+	c->tables_batch = true; c->dec_kind = DEC_NONE; c->wd_kind = WD_NONE;
 	c->n_seg = n_seg;
 	c->L.assign(L, L + n_seg);
 	int rc;

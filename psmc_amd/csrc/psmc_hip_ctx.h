@@ -442,25 +442,32 @@ template <class T, BufKind K> hipError_t Buf<T, K>::try_alloc(size_t n)
 	cap = n; owned = true;
 	return hipSuccess;
 }
+// PSMC_HIP_POISON=1 (tests): fresh device memory is usually zero, recycled memory is not -- fill every allocation with
+// 0xFF bytes (NaN as double, -1 as int) so that anything that depends on memory nobody wrote shows up at once.
+// PSMC_HIP_POISON=vary: a different finite garbage value per allocation (bytes 0x3B..0x42: doubles from 1e-23 to 1e5),
+// so that two contexts with the same call history disagree if anything reads memory nobody wrote.  One rotation for the
+// buffers of the contexts (Buf::alloc) and the per-call scratch (Scratch::get).  Without the variable: no call at all.
+inline void poison_fill(void *p, size_t bytes)
+{
+	static const char *poison = getenv("PSMC_HIP_POISON");
+	static std::atomic<int> poison_count{0};
+	if (!poison) return;
+	// the fill runs on the null stream, the kernels on non-blocking streams: finish it before anybody writes results there
+	(void)hipMemset(p, strcmp(poison, "vary") == 0 ? 0x3B + (poison_count++ % 8) : 0xFF, bytes);
+	(void)hipDeviceSynchronize();
+}
+
 template <class T, BufKind K> int Buf<T, K>::alloc(psmc_hip_ctx *c, size_t n)
 {
 	const hipError_t e = try_alloc(n);
 	if (e != hipSuccess) return K == BUF_DEVICE ? fail(c, PSMC_HIP_ENOMEM, "hipMalloc", e) : fail(c, PSMC_HIP_ENOMEM, K == BUF_MAPPED ? "hipHostMalloc (mapped)" : "hipHostMalloc");
-	// PSMC_HIP_POISON=1 (tests): fresh device memory is usually zero, recycled memory is not -- fill every allocation with
-	// 0xFF bytes (NaN as double, -1 as int) so that anything that depends on memory nobody wrote shows up at once.
-	// PSMC_HIP_POISON=vary: a different finite garbage value per allocation (bytes 0x3B..0x42: doubles from 1e-23 to 1e5),
-	// so that two contexts with the same call history disagree if anything reads memory nobody wrote
-	static const char *poison = getenv("PSMC_HIP_POISON");
-	static int poison_count = 0;
-	if (poison && K == BUF_DEVICE) { // the fill runs on the null stream, the kernels on non-blocking streams: finish it before anybody writes results there
-		(void)hipMemset(p, strcmp(poison, "vary") == 0 ? 0x3B + (poison_count++ % 8) : 0xFF, cap * sizeof(T));
-		(void)hipDeviceSynchronize();
-	}
+	if (K == BUF_DEVICE) poison_fill(p, cap * sizeof(T));
 	return 0;
 }
 
-// Device scratch of one decoding, Viterbi or sampling call, freed when the call returns.  Plain hipMalloc, not Buf::alloc: no poison
-// fill and no device synchronise.  A failed get() returns null, leaves ok false and clears the runtime's last error; the gets after
+// Device scratch of one decoding, Viterbi or sampling call, freed when the call returns.  Plain hipMalloc and, unless
+// PSMC_HIP_POISON is set (poison_fill: the block is filled, and the fill finished, before get() returns), nothing else: no fill
+// and no device synchronise.  A failed get() returns null, leaves ok false and clears the runtime's last error; the gets after
 // it still allocate (the caller checks ok, or the pointers, once).  ok never goes back to true: psmc_hip_sample_paths, which tries
 // its map tables at a smaller size after a failure, looks at its pointers and not at ok.
 struct Scratch {
@@ -475,6 +482,7 @@ struct Scratch {
 		void *p = nullptr;
 		if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) { ok = false; (void)hipGetLastError(); return nullptr; }
 		bufs.push_back(p);
+		poison_fill(p, sizeof(T) * (n ? n : 1));
 		return (T *)p;
 	}
 };
